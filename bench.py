@@ -13,14 +13,22 @@ workload = BASELINE.json configs[1]: Lander3D, 65 536 envs, uniform random actio
              BEFORE it touches the GPU, relays their output and exits with their code.
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (the driver's form)
 
-How the K steps are timed.  The K steps are captured as hipGraphs of at most --graph-chunk launches
-(several passes of the K steps per graph when K is small).  A timed REGION is R back-to-back passes of
-those K steps, bracketed by
-barrier + torch.cuda.synchronize() on both sides and timed with the host clock; R ("repeats") is
-chosen so that a region holds >= --min-region-ms of GPU work (a single 20-step pass is 0.1 ms:
-graph-launch and synchronisation overhead would be a third of it).  --regions such regions are timed,
-each reduced with MAX over ranks; the MEDIAN region gives ms_per_step = wall / (R * K) and
-value = total envs * R * K / wall.  `single_pass` reports one bare pass for comparison.
+How the K steps are timed.  The headline times exactly K = --steps steps, after an untimed pass of K steps (the clock's
+ramp under load) and W = --warmup more untimed ones.  The K steps are split into at most --regions
+consecutive REGIONS of whole hipGraphs of --graph-chunk launches, the last region ending in one graph of the K mod
+--graph-chunk launches that remain (K < --graph-chunk: one region, one graph of K), so that every timed step is a graph
+replay.  A region is bracketed by barrier + torch.cuda.synchronize() on both sides and timed with the host clock,
+reduced with MAX over ranks; the MEDIAN region gives ms_per_step = wall / its steps and value = total envs / that.
+Graph launch and synchronisation are paid once per region, so a small K reports that overhead with its steps: a
+steady-state figure wants K in the hundreds of thousands (pick K from a first run's ms_per_step).  The legs beside the
+headline keep their own calibration: R back-to-back passes per region, R chosen so that a region holds >= --min-region-ms
+of GPU work.
+
+--dump-outputs DIR: after the timed steps, what the headline's last step handed its caller (obs, reward, terminated,
+truncated) goes to DIR/<name>.npy as float32 (the flags as 0 / 1; N > 1: every rank's shard, in global env order, written
+by rank 0), at most 64 MB (10^6 bytes) on disk in all: a larger batch is written as a fixed, seeded sample of each rank's
+env rows.  With the same arguments the inputs are the same from run to run (seeded reset and action ring, 2 K + W steps,
++ 3 before a hipGraph capture), so two builds can be compared output for output.
 
 Rank 0 prints ONE COMPACT JSON line on stdout (<= 8 000 bytes, asserted here and in tests/): the contract keys,
   roofline     : algorithmic bytes (176 B/env-step) per launch over the
@@ -44,7 +52,8 @@ group; the RCCL communicator is opened only for the all-gather legs: at N > 1 on
 (eager launches, last, under a deadline: value_with_packed_allgather), with --gather all three legs
 (obs rows, packed, double-buffered half-batches; hipGraph-captured), timed separately from `value`.
 north_star's other action law (lander.py's constant thrust) is a sweep point at N = 1 and, at N > 1, its own leg
-on the same shards, timed like the headline: value_constant_thrust.
+on the same shards, timed like the other legs (calibrated regions, barrier + synchronize, MAX over ranks):
+value_constant_thrust.
 """
 import argparse
 import json
@@ -79,8 +88,9 @@ SUMMARY_BUDGET = 1500
 def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=2000)
-    p.add_argument("--warmup", type=int, default=200)
+    p.add_argument("--steps", type=int, default=2000, help="timed steps of the headline, exactly this many")
+    p.add_argument("--warmup", type=int, default=200,
+                   help="untimed steps of the headline right before them (after an untimed pass of --steps steps)")
     p.add_argument("--envs", type=int, default=65536, help="envs per GPU")
     p.add_argument("--task", default="lander3d", choices=["lander3d", "hover3d"])
     p.add_argument("--actions", default="uniform", choices=["uniform", "near_hover", "const"])
@@ -92,7 +102,8 @@ def parse(argv=None):
     p.add_argument("--produce-actions", action="store_true",
                    help="A/B workload: every step's action batch is WRITTEN by a preceding kernel (a device copy "
                         "from the ring into one buffer) instead of being read from the resident ring")
-    p.add_argument("--min-region-ms", type=float, default=50.0, help="GPU work per timed region")
+    p.add_argument("--min-region-ms", type=float, default=50.0,
+                   help="GPU work per timed region of the legs beside the headline (the headline times exactly --steps)")
     p.add_argument("--regions", type=int, default=5, help="timed regions (the median is reported)")
     p.add_argument("--gather", action="store_true",
                    help="also time with the RCCL all-gathers of the concatenated return (on one GPU it runs them in a "
@@ -128,6 +139,9 @@ def parse(argv=None):
     p.add_argument("--many", type=int, default=100,
                    help="also time cs_step_many with this many steps per launch (0 = skip)")
     p.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (0 = pick a free one)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the headline's last timed step returned to DIR/<name>.npy (float32, <= 64 MB on disk; "
+                        "N > 1: all ranks' shards in global env order, written by rank 0)")
     a = p.parse_args(argv)
     if a.served is None:
         a.served = 500 if a.full else 0
@@ -208,17 +222,17 @@ def quiesce_collectives(torch):
 
 
 class Stepper:
-    """Runs `count` consecutive env steps, as hipGraph replays of `chunk` captured
-    launches plus eager launches for the remainder."""
+    """Runs `count` consecutive env steps, as hipGraph replays of `chunk` captured launches, then a replay of a second
+    graph of `tail` launches when exactly that many remain, else eager launches for the remainder."""
 
-    def __init__(self, torch, env, actions, use_graph, chunk, post=None, produce=False):
+    def __init__(self, torch, env, actions, use_graph, chunk, post=None, produce=False, tail=0):
         self.torch, self.env, self.actions, self.post = torch, env, actions, post
         self.ring = actions.shape[0]
         # produce: the action row is written by a kernel right before the step, as a policy would
         self.produced = torch.empty_like(actions[0]) if produce else None
         self.pos = 0
-        self.graph = None
-        self.chunk = chunk
+        self.graph = self.tail_graph = None
+        self.chunk, self.tail = chunk, tail
         if use_graph:
             s = torch.cuda.Stream(device=env.device)
             s.wait_stream(torch.cuda.current_stream(env.device))
@@ -234,13 +248,20 @@ class Stepper:
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
                 for j in range(chunk):
                     self._one(j)
+            if tail > 0:
+                self.tail_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.tail_graph, capture_error_mode="thread_local"):
+                    for j in range(tail):
+                        self._one(j)
 
     def _one(self, j):
         if self.produced is not None:
             self.produced.copy_(self.actions[j % self.ring])
-            self.env.step(self.produced)
+            out = self.env.step(self.produced)
         else:
-            self.env.step(self.actions[j % self.ring])
+            out = self.env.step(self.actions[j % self.ring])
+        # (obs, reward, terminated, truncated): the env's persistent output buffers, which a graph replay rewrites too
+        self.outputs = out[:4]
         if self.post is not None:
             self.post()
 
@@ -250,6 +271,9 @@ class Stepper:
             while count - done >= self.chunk:
                 self.graph.replay()
                 done += self.chunk
+            if self.tail_graph is not None and count - done == self.tail:
+                self.tail_graph.replay()
+                done += self.tail
         while done < count:
             self._one(self.pos)
             self.pos += 1
@@ -472,6 +496,84 @@ class Timer:
                 "single_pass": {"steps": steps, "wall_ms": w1 * 1e3, "ms_per_step": w1 / steps * 1e3,
                                 "note": "one bare pass (the K steps, or one hipGraph of them) incl. graph-launch + "
                                         "synchronisation overhead"}}
+
+    def measure_steps(self, runner, warmup, sizes, sampler=None):
+        """-> dict with measure()'s timing keys, for exactly `warmup` untimed steps and then sum(sizes) timed ones, one
+        region per entry of `sizes` (region_sizes()); the median region by wall time per step gives s_per_step."""
+        if warmup > 0:
+            runner.run(warmup)
+        walls, evs = [], []
+        before = sampler.snapshot() if sampler is not None else None
+        if sampler is not None:
+            sampler.start()
+        for c in sizes:
+            w, e = self.region(runner, c)
+            walls.append(w / c)
+            evs.append(e / c)
+        during = sampler.stop() if sampler is not None else None
+        after = sampler.snapshot() if sampler is not None else None
+        k = sorted(range(len(walls)), key=lambda i: walls[i])[len(walls) // 2]     # the median region
+        sev = sorted(evs)
+        return {"steps": sum(sizes), "repeats": 1, "regions": len(sizes), "region_steps": list(sizes),
+                "wall_s": walls[k] * sizes[k], "wall_s_total": sum(w * c for w, c in zip(walls, sizes)),
+                "s_per_step": walls[k], "launch_s": evs[k], "launch_s_best": sev[0],
+                "launch_us_regions": {"min": sev[0] * 1e6, "median": sev[len(sev) // 2] * 1e6,
+                                      "max": sev[-1] * 1e6, "all": [e * 1e6 for e in evs]},
+                "clocks": None if sampler is None else {"before": before, "during": during, "after": after}}
+
+
+def region_sizes(steps, regions, chunk):
+    """`steps` split into at most `regions` consecutive regions of whole hipGraphs of `chunk` launches, as equal as whole
+    graphs allow, the last one also taking the steps % chunk that remain (one region when steps < chunk): the headline's
+    timed steps, exactly `steps` of them."""
+    steps, chunk = max(1, steps), max(1, chunk)
+    units = steps // chunk
+    if units == 0:
+        return [steps]
+    r = min(max(1, regions), units)
+    q, extra = divmod(units, r)
+    sizes = [(q + (i < extra)) * chunk for i in range(r)]
+    sizes[-1] += steps % chunk
+    return sizes
+
+
+DUMP_BUDGET = 64 * 10 ** 6        # bytes --dump-outputs writes in all: every file, headers included
+DUMP_NAMES = ("obs", "reward", "terminated", "truncated")
+NPY_HEADER_ALLOWANCE = 1024       # bytes per .npy file for its header (numpy writes 128 for these shapes)
+
+
+def dump_outputs(outdir, outputs, rank=0, world=1, dist=None, budget=DUMP_BUDGET):
+    """What one step returned to its caller (obs, reward, terminated, truncated: tensors of one leading env dimension)
+    -> outdir/<name>.npy as float32, the flags as 0 / 1.  N > 1: every rank's shard goes to rank 0 over the control
+    group (`dist`) and rank 0 writes them in rank order, i.e. global env order.  Over the budget (the files on disk,
+    headers included), each rank contributes the rows of a fixed sample of its envs instead (seeded, sorted: the same for
+    every run of the same batch size).  -> what was written, for the full record (None on ranks > 0)."""
+    import numpy as np
+    arrs = [np.asarray(t.detach().cpu().numpy(), dtype=np.float32) for t in outputs]
+    n = arrs[0].shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrs)
+    keep = max(1, (budget - len(DUMP_NAMES) * NPY_HEADER_ALLOWANCE) // max(1, world) // row_bytes)
+    rows = None
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = [a[rows] for a in arrs]
+    written = n if rows is None else len(rows)
+    if world > 1:
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object((arrs, n, written), parts, dst=0)
+        if rank != 0:
+            return None
+        arrs = [np.concatenate([p[0][k] for p in parts]) for k in range(len(DUMP_NAMES))]
+        n, written = sum(p[1] for p in parts), sum(p[2] for p in parts)
+    os.makedirs(outdir, exist_ok=True)
+    files = [name + ".npy" for name in DUMP_NAMES]
+    for f, arr in zip(files, arrs):
+        np.save(os.path.join(outdir, f), np.ascontiguousarray(arr))
+    size = sum(os.path.getsize(os.path.join(outdir, f)) for f in files)
+    assert size <= budget, "bench.py: --dump-outputs wrote %d bytes (budget %d)" % (size, budget)
+    return {"dir": outdir, "files": files, "bytes": size, "envs": n, "envs_written": written,
+            "sample": None if rows is None else "per rank: numpy default_rng(0).choice(envs of the rank, %d, "
+                                                "replace=False), sorted" % keep}
 
 
 def _cpu_model():
@@ -1048,12 +1150,19 @@ def main(argv=None):
     # the env kernel's own stream is created with the context for the same reason)
     served_side = [torch.cuda.Stream(device=device) for _ in (0, 1)] if a.served > 0 else None
     use_graph = hip.graphs and not a.no_graph
-    chunk = graph_chunk_for(a.steps, a.graph_chunk)
-    stepper = Stepper(torch, env, actions, use_graph, chunk, produce=a.produce_actions)
-    m = timer.measure(stepper, a.steps, a.warmup, min_region_s, a.regions, quantum=chunk if use_graph else 1,
-                      sampler=sampler)
+    # every timed step a graph replay: regions of whole `chunk`-launch graphs, the last one ending in a `tail` graph
+    chunk = max(1, min(a.graph_chunk, a.steps))
+    sizes = region_sizes(a.steps, a.regions, chunk)
+    tail = sum(sizes) % chunk
+    stepper = Stepper(torch, env, actions, use_graph, chunk, produce=a.produce_actions, tail=tail)
+    # an untimed pass of the K steps first: the engine clock ramps up over a fraction of a second of load (DESIGN.md
+    # section 5).  A count, not a time: the steps before the last one, and so what it returns, are fixed by the arguments.
+    stepper.run(sum(sizes))
+    m = timer.measure_steps(stepper, a.warmup, sizes, sampler=sampler)
     total_envs = n * world
     value = total_envs / m["s_per_step"]
+    # (before any other leg steps this env or rebinds its outputs)
+    dumped = dump_outputs(a.dump_outputs, stepper.outputs, rank, world, dist) if a.dump_outputs else None
 
     extra = {}
     state = {"deadline_hit": False}      # (set when the default N > 1 gather leg hits its deadline or fails: "status": "degraded")
@@ -1085,14 +1194,14 @@ def main(argv=None):
             "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": m["s_per_step"] * 1e3, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "repeats": m["repeats"], "regions": m["regions"], "timed_steps_per_region": m["steps"] * m["repeats"],
-            # `steps` echoes --steps; what was actually timed (the driver's consistency arithmetic should use these):
-            "timed_steps_total": m["steps"] * m["repeats"] * m["regions"],
-            "timed_region_s": m["wall_s"],
-            "timing": "median of %d regions of %d x %d steps (%s), each bracketed by barrier + "
-                      "synchronize, MAX over ranks" % (m["regions"], m["repeats"], m["steps"],
-                                                       "hipGraphs of %d launches" % chunk if use_graph else "eager launches"),
-            "single_pass": m["single_pass"],
+            "repeats": m["repeats"], "regions": m["regions"], "timed_steps_per_region": m["region_steps"],
+            "timed_steps_total": m["steps"],
+            "timed_region_s": m["wall_s"], "timed_s_total": m["wall_s_total"],
+            "timing": "%d timed steps after %d untimed, in %d regions of %s steps (%s), each bracketed by barrier + "
+                      "synchronize, MAX over ranks; ms_per_step from the median region"
+                      % (m["steps"], m["steps"] + max(0, a.warmup), m["regions"], "/".join(str(c) for c in sorted(set(m["region_steps"]))),
+                         ("hipGraphs of %d launches%s" % (chunk, " + one of %d" % tail if tail else ""))
+                         if use_graph else "eager launches"),
             "config": {"workload": "%s, %d envs/GPU, %s actions, auto-reset NEXT_STEP, %s state words, "
                                    "dt=%g x %d substeps, %s" % (a.task, n, a.actions, a.state,
                                                               1.0 / (100 * a.substeps), a.substeps,
@@ -1138,6 +1247,8 @@ def main(argv=None):
         if v:
             rf["issue"] = dict(issue_bound(v, n, m["launch_s"], cus, clock_hz, f64_clock.get(1 if n <= 65536 else 4)), source=pmc_src)
         out.update(extra)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if cpu is not None:
             out["cpu_baseline"] = cpu
         if rccl is not None:

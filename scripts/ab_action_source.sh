@@ -10,7 +10,7 @@ for rep in 1 2 3; do
     for hint in on off; do
       extra=""; [ $src = produced ] && extra="--produce-actions"
       nt=0; [ $hint = off ] && nt=1
-      COPTERSTEP_NT_ACTION_MAX_ENVS=$nt python3 $R/bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-sweep --pid 0 --many 0 $extra 2>/dev/null |
+      COPTERSTEP_NT_ACTION_MAX_ENVS=$nt python3 $R/bench.py --steps 100000 --warmup 200 --no-cpu-baseline --no-sweep --pid 0 --many 0 $extra 2>/dev/null |
         python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('actions=$src nt_hint=$hint us_per_step %.3f' % (d['ms_per_step']*1e3))"
     done
   done

@@ -12,8 +12,6 @@
 #     price-trig                        short vs full sin / cos polynomials: time, one-unit rate, fuzz sweep (build
 #                                       `make -C gym_copter_amd/csrc exp NAME=fulltrig DEFS=-DCS_EXP_FULLTRIG` first)
 #     kstep                             K-step parity tests, un-instrumented per-step times by batch size, phase stamps
-#     flaky      [N=5] [M=5]            the GPU suite N times in fresh processes; the served tests M times under rocgdb
-#     contention [N=3]                  the race-prone tests while another process keeps the device busy
 #     probe                             hardware probes: float64 issue cost, readable sensors, 2 ranks on one device, ATT
 set -u
 JOB=${1:?job}; TAG=${2:?tag}; shift 2
@@ -22,16 +20,15 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
 B=gym_copter_amd/csrc/build
-SERVED="tests/test_gpu_served.py tests/test_gpu_stepping_forms.py"
 case $JOB in
 check)
   timeout 900 python3 -m pytest tests -m gpu -x -q "$@" > $OUT/gputests.log 2>&1
   echo "pytest rc=$?" >> $OUT/gputests.log; tail -15 $OUT/gputests.log
   timeout 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
   echo "smoke rc=$?" >> $OUT/smoke.log; tail -3 $OUT/smoke.log
-  # the driver's exact command: the compact line on stdout (<= 8 000 bytes), the full record beside it; wall time noted
+  # the bench line at a steady-state K: the compact line on stdout (<= 8 000 bytes), the full record beside it; wall time noted
   t0=$(date +%s%N)
-  timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full-out $OUT/bench_full.json > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err
+  timeout 600 python3 bench.py --gpus 1 --steps 200000 --warmup 20000 --full-out $OUT/bench_full.json > $OUT/bench_driver_form.json 2> $OUT/bench_driver_form.err
   echo "bench rc=$? wall_ms=$(( ($(date +%s%N) - t0) / 1000000 )) bytes=$(wc -c < $OUT/bench_driver_form.json)" | tee $OUT/bench_driver_form.wall
   cat $OUT/bench_driver_form.json
   if [ -f $R/$B/libcopterstep_kstamps.so ]; then
@@ -47,7 +44,7 @@ ab-trees)
   OTHER=$(cd $1 && pwd); MODE=${2:-headline}
   cd /tmp
   if [ $MODE = kstep ]; then
-    run() { python3 $1/bench.py --steps 1000 --warmup 100 --no-cpu-baseline --no-span --served 0 --no-sweep --full 2>/dev/null | python3 -c "
+    run() { python3 $1/bench.py --steps 100000 --warmup 100 --no-cpu-baseline --no-span --served 0 --no-sweep --full 2>/dev/null | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['summary']['k_step_us']
 print('headline %.3f | ' % (d['ms_per_step']*1e3) + ' | '.join('%s %.3f' % kv for kv in k.items()))"; }
@@ -60,7 +57,7 @@ print('headline %.3f | ' % (d['ms_per_step']*1e3) + ' | '.join('%s %.3f' % kv fo
       python3 $1/bench.py --envs $2 --actions $3 --substeps $4 --task $5 --ring $6 --steps $7 --warmup 100 --no-sweep --pid 0 --many 0 --served 0 --no-cpu-baseline --no-span --regions 5 2>/dev/null \
         | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('%.3f' % (d['ms_per_step']*1e3))"; }
     for pass in 1 2 3; do
-      for cfg in "262144 uniform 1 hover3d 16 2000" "65536 uniform 1 lander3d 64 2000" "65536 near_hover 1 lander3d 64 2000" "65536 near_hover 10 lander3d 64 2000" "262144 uniform 1 lander3d 16 2000" "1048576 uniform 1 lander3d 8 300" "4194304 uniform 1 lander3d 4 200"; do
+      for cfg in "262144 uniform 1 hover3d 16 100000" "65536 uniform 1 lander3d 64 100000" "65536 near_hover 1 lander3d 64 100000" "65536 near_hover 10 lander3d 64 100000" "262144 uniform 1 lander3d 16 100000" "1048576 uniform 1 lander3d 8 15000" "4194304 uniform 1 lander3d 4 10000"; do
         echo "pass $pass | $cfg | other $(run $OTHER $cfg) us | this $(run $R $cfg) us" | tee -a $OUT/ab_trees.txt
       done
     done
@@ -90,43 +87,6 @@ for leg in ("many","pid","random"):
 PY
   timeout 300 python3 tools/kstep_outputs_probe.py 65536 20 > $OUT/kstep_outputs_probe.txt 2>&1; tail -3 $OUT/kstep_outputs_probe.txt
   [ -f $R/$B/libcopterstep_kstamps.so ] && timeout 600 python3 tools/kstep_stamps.py 65536 8 > $OUT/kstep_stamps.txt 2> $OUT/kstep_stamps.err ;;
-flaky)
-  N=${1:-5}; M=${2:-5}; export PYTHONFAULTHANDLER=1
-  for i in $(seq 1 $N); do
-    timeout 900 python3 -X faulthandler -m pytest tests -q -m gpu -p no:cacheprovider > $OUT/full_$i.log 2>&1
-    echo "full $i rc=$? $(tail -1 $OUT/full_$i.log)" | tee -a $OUT/summary.txt
-  done
-  for i in $(seq 1 $M); do
-    timeout 900 /opt/rocm/bin/rocgdb -batch -ex "set pagination off" -ex "handle SIGUSR1 nostop noprint" -ex run -ex "bt 40" -ex "info sharedlibrary" \
-        --args python3 -m pytest $SERVED -q -m gpu -p no:cacheprovider > $OUT/gdb_$i.log 2>&1
-    echo "gdb $i rc=$? $(grep -c 'SIGSEGV' $OUT/gdb_$i.log) sigsegv; $(grep -h 'passed\|failed' $OUT/gdb_$i.log | tail -1)" | tee -a $OUT/summary.txt
-  done
-  grep -h "AssertionError\|^FAILED\|Fatal Python" $OUT/full_*.log | head -40 >> $OUT/summary.txt; tail -30 $OUT/summary.txt ;;
-contention)
-  N=${1:-3}
-  python3 - > $OUT/load.log 2>&1 <<'PY' &
-import time, torch, sys
-sys.path.insert(0, ".")
-import gym_copter_amd as gca
-env = gca.CopterVecEnv(task="lander3d", num_envs=262144, seed=1, autoreset_mode="next_step")
-env.reset()
-a = torch.rand((262144, 4), device="cuda") * 2 - 1
-t0 = time.time(); n = 0
-while time.time() - t0 < 420:
-    for _ in range(200):
-        env.step(a)
-    torch.cuda.synchronize(); n += 200
-    time.sleep(0.002)
-print("load: %d steps" % n)
-PY
-  LOAD=$!
-  sleep 5
-  for i in $(seq 1 $N); do
-    timeout 600 python3 -m pytest ${FILES:-$SERVED tests/test_gpu_fuzz.py} -q -m gpu -p no:cacheprovider -k "not bench and not rccl and not span" > $OUT/run_$i.log 2>&1
-    echo "run $i rc=$? $(tail -1 $OUT/run_$i.log)" | tee -a $OUT/summary.txt
-  done
-  kill $LOAD 2>/dev/null; wait $LOAD 2>/dev/null
-  grep -h "^FAILED\|Error" $OUT/run_*.log | head -20 >> $OUT/summary.txt; tail -12 $OUT/summary.txt ;;
 probe)
   cd /tmp && export TMPDIR=/tmp
   T="timeout ${STEP_TIMEOUT:-300}"

@@ -8,18 +8,18 @@ mkdir -p $OUT
 run() { python3 $R/bench.py --no-cpu-baseline "$@" 2>/dev/null >> $OUT/sweep.jsonl; }
 for law in uniform near_hover; do
   for n in 16384 65536 262144 1048576 4194304 16777216; do
-    k=2000; [ $n -ge 1048576 ] && k=300; [ $n -ge 16777216 ] && k=100
+    k=100000; [ $n -ge 1048576 ] && k=10000; [ $n -ge 16777216 ] && k=2000
     run --task lander3d --envs $n --actions $law --steps $k --warmup 100 --ring 8
   done
 done
-run --task lander3d --envs 65536 --actions const --steps 2000 --warmup 100                    # constant thrust (lander.py:21)
-run --task lander3d --envs 262144 --actions const --steps 2000 --warmup 100
-run --task hover3d --envs 262144 --actions uniform --steps 1000 --warmup 100 --ring 8        # BASELINE config 3
-run --task hover3d --envs 262144 --actions near_hover --steps 1000 --warmup 100 --ring 8
-run --task lander3d --envs 65536 --actions near_hover --substeps 10 --steps 1000 --warmup 100   # BASELINE config 5
-run --task lander3d --envs 65536 --actions uniform --state float32_rn --steps 2000 --warmup 100
-run --task lander3d --envs 65536 --actions uniform --state float64 --steps 2000 --warmup 100
-run --task lander3d --envs 65536 --actions uniform --no-graph --steps 2000 --warmup 100
+run --task lander3d --envs 65536 --actions const --steps 100000 --warmup 100                    # constant thrust (lander.py:21)
+run --task lander3d --envs 262144 --actions const --steps 100000 --warmup 100
+run --task hover3d --envs 262144 --actions uniform --steps 50000 --warmup 100 --ring 8        # BASELINE config 3
+run --task hover3d --envs 262144 --actions near_hover --steps 50000 --warmup 100 --ring 8
+run --task lander3d --envs 65536 --actions near_hover --substeps 10 --steps 50000 --warmup 100   # BASELINE config 5
+run --task lander3d --envs 65536 --actions uniform --state float32_rn --steps 100000 --warmup 100
+run --task lander3d --envs 65536 --actions uniform --state float64 --steps 100000 --warmup 100
+run --task lander3d --envs 65536 --actions uniform --no-graph --steps 100000 --warmup 100
 python3 - <<PY
 import json
 rows=[json.loads(l) for l in open("$OUT/sweep.jsonl") if l.strip()]

@@ -282,3 +282,120 @@ def test_committed_pmc_figures_are_stamped_with_this_trees_kernel_sources():
         assert stamp == here, "%s was measured on kernel sources %s, the tree has %s: re-run the profile" % (name, stamp, here)
     d, why = bench.load_stamped("pmc_counts.json")
     assert d is not None and d["valu_per_wavefront_step"]["step_many"] > 100, why
+
+
+# ---------------------------------------------------------------------------------------
+# the headline's timed steps and --dump-outputs
+# ---------------------------------------------------------------------------------------
+def test_headline_times_exactly_the_steps_asked_for():
+    """--steps K is the number of timed steps of the headline: `warmup` untimed steps first, then exactly K, in at most
+    --regions regions of whole hipGraphs, the last one also taking the K mod chunk that remain (K < chunk: one region)."""
+    import time
+    assert bench.region_sizes(20, 5, 100) == [20]
+    assert bench.region_sizes(2000, 5, 100) == [400] * 5
+    assert bench.region_sizes(250, 5, 100) == [100, 150]
+    assert bench.region_sizes(250003, 5, 100) == [50000, 50000, 50000, 50000, 50003]
+    assert bench.region_sizes(1050, 3, 100) == [400, 300, 350]
+    assert bench.region_sizes(7, 3, 1) == [3, 2, 2] and bench.region_sizes(0, 5, 100) == [1]
+
+    class CpuHip:
+        torch, device = None, None
+
+        def synchronize(self):
+            pass
+
+        def stamp(self):
+            return time.perf_counter()
+
+        def elapsed_s(self, t0, t1):
+            return t1 - t0
+
+    class Counter:
+        def __init__(self):
+            self.calls = []
+
+        def run(self, count):
+            self.calls.append(count)
+            time.sleep(1e-4 * count)
+
+    r = Counter()
+    m = bench.Timer(CpuHip(), None).measure_steps(r, 7, bench.region_sizes(250, 5, 100))
+    assert r.calls == [7, 100, 150]
+    assert m["steps"] == 250 and m["regions"] == 2 and m["region_steps"] == [100, 150] and m["repeats"] == 1
+    assert 0.9e-4 < m["s_per_step"] < 1e-2 and m["launch_s"] <= m["s_per_step"]
+    assert m["wall_s_total"] >= 250 * 1e-4 and m["wall_s"] in (m["s_per_step"] * 100, m["s_per_step"] * 150)
+    r = Counter()
+    bench.Timer(CpuHip(), None).measure_steps(r, 0, [20])
+    assert r.calls == [20]
+
+
+def test_dump_outputs_are_float_arrays_within_their_budget(tmp_path):
+    """--dump-outputs: the four arrays a step returns, as float32 .npy files (flags as 0 / 1, a strided obs view as its
+    values).  Over the budget -- the files on disk, headers included -- a fixed, sorted sample of env rows, the same every
+    time; N > 1: each rank's sample gathered to rank 0, in rank order, under the same one budget."""
+    import numpy as np
+    import torch
+    n, od = 1000, 10
+    rows = torch.arange(n * (od + 2), dtype=torch.float32).reshape(n, od + 2)     # packed rows: obs is a strided view
+    outs = (rows[:, :od], rows[:, od], torch.arange(n) % 3 == 0, torch.zeros(n, dtype=torch.uint8))
+    on_disk = lambda d, rec: sum(os.path.getsize(str(d / f)) for f in rec["files"])
+    rec = bench.dump_outputs(str(tmp_path / "all"), outs)
+    got = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in rec["files"]}
+    assert rec["files"] == ["obs.npy", "reward.npy", "terminated.npy", "truncated.npy"] and rec["sample"] is None
+    assert all(v.dtype == np.float32 and v.shape[0] == n for v in got.values())
+    assert np.array_equal(got["obs"], rows[:, :od].numpy()) and np.array_equal(got["reward"], rows[:, od].numpy())
+    assert np.array_equal(got["terminated"], (np.arange(n) % 3 == 0).astype(np.float32)) and not got["truncated"].any()
+    assert rec["bytes"] == on_disk(tmp_path / "all", rec)
+
+    budget = 4 * bench.NPY_HEADER_ALLOWANCE + 100 * 4 * (od + 3)      # four headers + 100 env rows
+    rec = bench.dump_outputs(str(tmp_path / "s1"), outs, budget=budget)
+    bench.dump_outputs(str(tmp_path / "s2"), outs, budget=budget)
+    assert rec["envs"] == n and rec["envs_written"] == 100 and on_disk(tmp_path / "s1", rec) <= budget
+    s1 = {f: np.load(str(tmp_path / "s1" / f)) for f in rec["files"]}
+    s2 = {f: np.load(str(tmp_path / "s2" / f)) for f in rec["files"]}
+    assert all(np.array_equal(s1[f], s2[f]) for f in s1)
+    ids = s1["reward.npy"].astype(np.int64) // (od + 2)          # reward of env i = i * (od + 2) + od
+    assert len(set(ids)) == 100 and np.all(np.diff(ids) > 0)
+    assert np.array_equal(s1["obs.npy"], rows[ids, :od].numpy())
+
+    # world 2 under the same budget: rank 1 hands its sample to rank 0, which writes both in rank order
+    class Dist:
+        def __init__(self, sent=None):
+            self.sent = sent
+
+        def gather_object(self, obj, parts, dst=0):
+            if parts is None:
+                self.sent = obj
+            else:
+                parts[0], parts[1] = obj, self.sent
+    d1 = Dist()
+    assert bench.dump_outputs(str(tmp_path / "w2"), outs, rank=1, world=2, dist=d1, budget=budget) is None
+    rec = bench.dump_outputs(str(tmp_path / "w2"), outs, rank=0, world=2, dist=Dist(d1.sent), budget=budget)
+    assert rec["envs"] == 2 * n and rec["envs_written"] == 100 and on_disk(tmp_path / "w2", rec) <= budget
+    w2 = np.load(str(tmp_path / "w2" / "reward.npy"))
+    assert len(w2) == 100 and np.array_equal(w2[:50], w2[50:])      # (both "ranks" stepped the same rows here)
+
+    # the real budget, with a batch that needs sampling: 64 MB on disk, headers included
+    big = 1300000
+    outs = (torch.zeros((big, od)), torch.zeros(big), torch.zeros(big, dtype=torch.bool), torch.zeros(big, dtype=torch.bool))
+    rec = bench.dump_outputs(str(tmp_path / "big"), outs)
+    assert bench.DUMP_BUDGET == 64 * 10 ** 6 and rec["envs_written"] < big
+    assert on_disk(tmp_path / "big", rec) <= bench.DUMP_BUDGET
+
+
+def test_n_rank_dump_outputs_are_every_ranks_last_step_in_env_order(tmp_path):
+    """--dump-outputs at world 2: rank 0 writes DIR/<name>.npy holding every rank's shard of the headline's last timed
+    step in global env order (the test double's outputs are the global env ids, and its terminated flag the parity of
+    the steps taken before: 20 + 6 + 20 - 1)."""
+    import json
+    import numpy as np
+    out = tmp_path / "out"
+    p = _run_ranks(2, tmp_path, extra_args=("--warmup", "6", "--no-sweep", "--dump-outputs", str(out)))
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][0])
+    assert d["timed_steps_total"] == 20 and d["warmup"] == 6
+    assert sorted(os.listdir(str(out))) == sorted(k + ".npy" for k in bench.DUMP_NAMES)
+    ids = np.arange(2 * 1024, dtype=np.float32)
+    got = {k: np.load(str(out / (k + ".npy"))) for k in bench.DUMP_NAMES}
+    assert np.array_equal(got["obs"], np.repeat(ids[:, None], 10, axis=1)) and np.array_equal(got["reward"], ids)
+    assert np.all(got["terminated"] == 1) and not got["truncated"].any()

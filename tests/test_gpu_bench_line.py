@@ -22,7 +22,8 @@ def _bench_light(args, tmp_path, extra_env=None, expect_rc=0):
     import os
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+    # (the headline times exactly --steps; enough of them that it compares with the calibrated legs beside it)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20000", "--warmup", "2000",
            "--no-cpu-baseline", "--min-region-ms", "5", "--regions", "3", "--full-out", str(tmp_path / "full.json")] + args
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", **(extra_env or {}))
     env.pop("COPTERSTEP_FORCE_COLLECTIVE", None)
@@ -56,8 +57,8 @@ def test_bench_as_a_torchrun_rank_with_gather_legs(tmp_path):
     three gather legs (obs rows, packed, double-buffered half-batches), all hipGraph-captured."""
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20",
-           "--warmup", "5", "--gather", "--no-sweep", "--no-cpu-baseline", "--pid", "0", "--many", "0",
+           "127.0.0.1", "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20000",
+           "--warmup", "2000", "--gather", "--no-sweep", "--no-cpu-baseline", "--pid", "0", "--many", "0",
            "--min-region-ms", "5", "--regions", "3", "--full-out", str(tmp_path / "full.json")]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     from gpu_util import run_with_rccl
@@ -69,7 +70,7 @@ def test_bench_as_a_torchrun_rank_with_gather_legs(tmp_path):
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d and k in line, k
     assert line["rccl"] == d["rccl"] and line["value_with_packed_allgather"] == d["value_with_packed_allgather"]
-    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["scaling"] == "weak"
+    assert d["n_gpus"] == 1 and d["steps"] == 20000 and d["warmup"] == 2000 and d["scaling"] == "weak"
     assert abs(d["value"] - 65536 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
     for k in ("value_with_allgather", "value_with_packed_allgather", "value_with_pipelined_allgather"):
         assert 0 < d[k] <= d["value"] * 1.05, (k, d[k], d["value"])
@@ -83,7 +84,7 @@ def test_bench_gather_on_one_gpu_reports_what_rccl_saw(tmp_path):
     import json
     import subprocess
     import sys
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--gather",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20000", "--warmup", "2000", "--gather",
            "--no-sweep", "--no-cpu-baseline", "--pid", "0", "--many", "0", "--served", "0", "--min-region-ms", "5",
            "--regions", "3", "--full-out", str(tmp_path / "full.json")]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -98,7 +99,7 @@ def test_bench_gather_on_one_gpu_reports_what_rccl_saw(tmp_path):
     assert d["allgather_is_a_collective"] is True
     assert set(d["allgather_launch_mode"]) == {"obs", "packed", "pipelined"}
     assert d["summary"]["rccl"] == d["rccl"] and list(d)[-1] == "summary"
-    assert d["timed_steps_total"] >= 3 * 20 and d["timed_region_s"] > 0
+    assert d["timed_steps_total"] == 20000 and d["timed_region_s"] > 0
     for k in ("value_with_allgather", "value_with_packed_allgather", "value_with_pipelined_allgather"):
         assert 0 < d[k] <= d["value"] * 1.05, (k, d[k], d["value"])
 
@@ -152,8 +153,10 @@ def test_bench_line_round5_blocks(tmp_path):
     """The driver-form line: status, clocks (sysfs + in-kernel), region spreads on the HBM-resident points, the sweep
     points where an instruction-issue bound binds (config 5 at 1 M envs, the K-step kernels at 4 M envs), a CPU
     baseline whose all-core row names the cores it could use, and only the served leg that pays."""
-    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--cpu-seconds", "4", "--full"], tmp_path)
+    # (the headline times exactly --steps: five regions of ~40 ms, as long as the other legs' calibrated ones)
+    d = _bench(["--gpus", "1", "--steps", "60000", "--warmup", "6000", "--cpu-seconds", "4", "--full"], tmp_path)
     assert d["status"] == "ok" and d["summary"]["status"] == "ok"
+    assert d["timed_steps_total"] == 60000 and d["timed_steps_per_region"] == [12000] * 5
     ck = d["clocks"]
     assert 0.8 < ck["f64_load_clock_GHz"]["4"] <= 2.6 and ck["peak_engine_clock_GHz"] > 2.0
     if ck["headline"] is not None:                       # a readable hwmon node: before / during / after
@@ -190,14 +193,16 @@ def test_default_bench_line_is_compact_and_on_a_diet(tmp_path):
     HBM-resident Lander3D point and the two K-step paths, nothing else; the full record sits beside it."""
     import time
     t0 = time.time()
-    d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], tmp_path)
+    # (the headline times exactly --steps: enough of them that one region's launch + synchronisation is not the figure)
+    d = _bench(["--gpus", "1", "--steps", "20000", "--warmup", "2000"], tmp_path)
     wall = time.time() - t0
     line = d["_line"]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "status", "roofline", "cpu_baseline", "summary"):
         assert k in line, k
     assert line["metric"].startswith("env-steps/sec Lander3D at 65 536 envs") and line["n_gpus"] == 1
-    assert (line["steps"], line["warmup"], line["status"], line["dtype"]) == (20, 5, "ok", "f64")
+    assert (line["steps"], line["warmup"], line["status"], line["dtype"]) == (20000, 2000, "ok", "f64")
+    assert line["timed_steps_total"] == 20000
     rf = line["roofline"]
     assert rf["bound"] == "hbm" and rf["peak"] == 8000.0 and rf["unit"] == "GB/s" and rf["algorithmic_bytes_per_launch"] == 176 * 65536
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12 and 0.2 < rf["frac"] < 1.0
@@ -230,7 +235,7 @@ def test_two_ranks_sharing_the_one_gpu_run_the_n_rank_path_on_real_kernels(tmp_p
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20000", "--warmup", "2000",
            "--envs", "16384", "--min-region-ms", "5", "--regions", "3", "--full-out", str(tmp_path / "full.json")]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", BENCH_GATHER_DEADLINE_S="60")
@@ -252,3 +257,56 @@ def test_two_ranks_sharing_the_one_gpu_run_the_n_rank_path_on_real_kernels(tmp_p
         assert "failed" in d["packed_allgather_note"] or "deadline" in d["packed_allgather_note"]
     else:                                   # a library that accepts it: the leg ran
         assert p.returncode == 0 and d["value_with_packed_allgather"] > 0 and d["rccl"]["ranks_seen"] == 2
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs writes what the headline's last timed step returned, and --steps is exactly the number of timed
+    steps.  Eager launches step action row j % ring at step j, and a run takes 2 K + W steps (an untimed pass of the K
+    steps, W untimed, K timed): K = 20, W = 5 and K = 15, W = 15 end on the same step and dump the same arrays, K = 21,
+    W = 5 does not, and those arrays are the CPU oracle's after 45 steps of the same seeded actions.  hipGraph replay:
+    the same arguments dump the same arrays twice."""
+    import numpy as np
+    import torch
+    import bench
+    from oracle import refvec
+    from oracle.refvec import VecOracle
+    n = 1000
+    light = ["--gpus", "1", "--no-sweep", "--pid", "0", "--many", "0", "--served", "0", "--no-span", "--no-cpu-baseline",
+             "--no-clock-sampling", "--regions", "3"]
+
+    def run(name, args):
+        (tmp_path / name).mkdir()
+        d = _bench(light + args + ["--dump-outputs", str(tmp_path / name / "out")], tmp_path / name, timeout=300)
+        files = d["dumped_outputs"]["files"]
+        assert files == ["obs.npy", "reward.npy", "terminated.npy", "truncated.npy"]
+        return d, {f[:-4]: np.load(str(tmp_path / name / "out" / f)) for f in files}
+
+    eager = ["--no-graph", "--envs", str(n)]
+    da, a = run("a", eager + ["--steps", "20", "--warmup", "5"])
+    db, b = run("b", eager + ["--steps", "15", "--warmup", "15"])
+    _, c = run("c", eager + ["--steps", "21", "--warmup", "5"])
+    assert (da["timed_steps_total"], db["timed_steps_total"]) == (20, 15)
+    assert a["obs"].shape == (n, 10) and a["reward"].shape == a["terminated"].shape == a["truncated"].shape == (n,)
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert not np.array_equal(a["obs"], c["obs"])
+
+    actions = bench.make_actions(torch, "uniform", 64, n, torch.device("cuda", 0), 1234).cpu().numpy()
+    orc = VecOracle("lander3d", n, store_mode="float32", autoreset=refvec.AUTORESET_NEXT_STEP, seed=1234)
+    orc.reset()
+    for j in range(45):
+        wobs, wr, wterm, wtrunc = orc.step(actions[j % 64].astype(np.float64))
+    assert np.array_equal(a["terminated"], wterm.astype(np.float32)) and np.array_equal(a["truncated"], wtrunc.astype(np.float32))
+    err = np.abs(a["obs"].astype(np.float64) - wobs) / np.maximum(np.abs(wobs), 1.0)
+    assert err.max() <= 2e-6, err.max()
+    # the reward tolerance of smoke() (the golden-trace formula with the shaping bounded from what the step returned)
+    awr = np.abs(wr)
+    shaping_bound = awr + 25.0 * np.sqrt(np.sum(np.square(wobs[:, :6]), axis=1)) + 110.0
+    limit = np.minimum(5e-5 + 1e-5 * awr + 6e-7 * shaping_bound, 2e-3 + 2e-6 * awr)
+    assert np.all(np.abs(a["reward"] - wr) <= limit)
+
+    d1, g1 = run("g1", ["--steps", "350", "--warmup", "50"])
+    _, g2 = run("g2", ["--steps", "350", "--warmup", "50"])
+    assert d1["timed_steps_per_region"] == [100, 100, 150] and "hipGraphs of 100 launches + one of 50" in d1["timing"]
+    assert g1["obs"].shape == (65536, 10) and all(np.array_equal(g1[k], g2[k]) for k in g1)
+    assert d1["dumped_outputs"]["bytes"] <= 64 * 10 ** 6

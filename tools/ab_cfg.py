@@ -24,7 +24,7 @@ def main():
     p.add_argument("--libs", nargs="+", required=True)
     p.add_argument("--cfgs", nargs="+", default=["65536 uniform 1"])
     p.add_argument("--reps", type=int, default=3)
-    p.add_argument("--steps", type=int, default=2000)
+    p.add_argument("--steps", type=int, default=100000)
     a = p.parse_args()
     libs = [x.split("=", 1) for x in a.libs]
     res = {}
@@ -34,7 +34,7 @@ def main():
             n, law, nsub = int(f[0]), f[1], int(f[2])
             task = f[3] if len(f) > 3 else "lander3d"
             ring = 64 if n <= 131072 else (16 if n <= 524288 else 4)
-            steps = a.steps if n <= 1048576 else 200
+            steps = a.steps if n <= 1048576 else 10000
             for name, path in libs:
                 env = dict(os.environ, COPTERSTEP_LIB=os.path.join(ROOT, path))
                 cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--envs", str(n), "--actions", law,

@@ -15,7 +15,7 @@ res = {}
 for rep in range(reps):
     for name, path in libs:
         env = dict(os.environ, COPTERSTEP_LIB=os.path.join(ROOT, path))
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--served", "0", "--steps", "1000",
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--served", "0", "--steps", "100000",
                               "--warmup", "100", "--no-span", "--full-out", "/dev/null"] + (["--full"] if "--full" in sys.argv else []),
                              env=env, capture_output=True, text=True)
         line = json.loads(out.stdout.strip().splitlines()[-1])
