@@ -66,6 +66,19 @@ class StepIO(C.Structure):
 OUTPUT_AUTO, OUTPUT_PLAIN, OUTPUT_PACKED_ROWS = 0, 1, 2     # cs_step_io.output_form
 
 
+class JacobianIO(C.Structure):
+    """Mirror of `struct cs_jacobian_io` (cs_step_jacobian)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32),
+                ("actions_dev", C.c_void_p), ("x_dev", C.c_void_p), ("status_dev", C.c_void_p),
+                ("force_dev", C.c_void_p), ("dx_dev", C.c_void_p), ("du_dev", C.c_void_p),
+                ("reward_dx_dev", C.c_void_p), ("reward_du_dev", C.c_void_p), ("branch_dev", C.c_void_p)]
+
+
+JAC_F64, JAC_F32 = 0, 1                                      # cs_jacobian_io.out_dtype
+# cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
+JAC_INTEGRATED, JAC_LANDED, JAC_CONTACT, JAC_LEVELING, JAC_CRASHED, JAC_RESET, JAC_CLIPPED = 1, 2, 4, 8, 16, 32, 64
+
+
 # every symbol include/copterstep.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 class PidGains(C.Structure):
@@ -118,6 +131,7 @@ SYMBOLS = {
     "cs_reset_pose": (C.c_int, [_P, _P, _P, C.c_int32, _P, _P, _P]),
     "cs_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "cs_step_ex": (C.c_int, [_P, C.POINTER(StepIO), _P]),
+    "cs_step_jacobian": (C.c_int, [_P, C.POINTER(JacobianIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "copterstep_internal.h"
+#include "copterstep_jacobian.h"
 
 struct cs_ctx {
   cs_config cfg;
@@ -318,6 +319,21 @@ int serve_make_stream(cs_ctx* ctx) {
 }
 }  // namespace
 
+
+// For entry points defined in other translation units (copterstep_jacobian.hip: cs_step_jacobian): the error
+// reporting and the context checks of this file (copterstep_jacobian.h).
+namespace cs {
+int report_error(int code, const char* message) { return fail(code, message); }
+int report_hip(hipError_t e, const char* what) { return hip_fail(e, what); }
+int enter_context(cs_ctx* ctx, const char* who, void* stream, ContextView* out) {
+  if (int rc_ = check_idle(ctx, who, stream, true)) return rc_;
+  out->task = ctx->cfg.task;
+  out->mode = ctx->cfg.state_mode;
+  out->c = &constants(ctx);
+  out->s = &ctx->st;
+  return CS_OK;
+}
+}  // namespace cs
 
 extern "C" {
 

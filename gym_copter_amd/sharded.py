@@ -182,6 +182,11 @@ class ShardedCopterVecEnv:
             term, trunc = g_term.view(torch.bool), g_trunc.view(torch.bool)
         return obs, reward, term, trunc, infos
 
+    def step_jacobian(self, actions, state=None, dtype=None):
+        """CopterVecEnv.step_jacobian of this rank's envs: shard-local, no gather (actions: [n_local, A] or the
+        global [N, A], as step() takes them; an explicit `state` covers the local envs)."""
+        return self.local.step_jacobian(self._local_actions(actions), state=state, dtype=dtype)
+
     def close(self):
         self.local.close()
 

@@ -18,6 +18,7 @@ PyTorch is used only for device memory and streams.  There is no CPU implementat
 this package: construction fails if libcopterstep.so or a HIP device is missing.
 """
 import atexit
+import collections
 import ctypes as C
 import os
 import weakref
@@ -85,6 +86,9 @@ _TASK_KEYS = {"initial_random_force": "initial_random_force",             # task
 PACKED_ROWS_MAX_ENVS = 131072
 
 STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dTheta', 'Psi', 'dPsi']
+
+# CopterVecEnv.step_jacobian's result (device tensors)
+StepJacobian = collections.namedtuple("StepJacobian", "dx du reward_dx reward_du branch")
 
 
 def _torch():
@@ -852,6 +856,72 @@ class CopterVecEnv(_VectorEnvBase):
             self._done["return"] = torch.zeros(n, dtype=torch.float32, device=dev)
 
     # -- Dynamics-level access (reference dynamics/__init__.py public methods) ---------
+    def step_jacobian(self, actions, state=None, dtype=None):
+        """Jacobians of the step that step(actions) would take, for every env, as device tensors; NO env state
+        changes.  Returns StepJacobian(dx [N,12,12] = d x' / d x, du [N,12,A] = d x' / d actions (the actions as
+        step() receives them, before the clip to [0, 1]; the clip's derivative is 1 on [0, 1] and 0 outside),
+        reward_dx [N,12], reward_du [N,A] = the gradient of the step's reward, branch [N] uint8 = the CS_JAC_*
+        bits of the branches the step takes).  x is the full state in upstream slot order (STATE_NAMES_12); an
+        observation is a slice of x', so its Jacobian is the matching rows of dx / du.
+
+        The transition differentiated is the physics + reward of the step with auto-reset DISABLED: a termination
+        in this step and the auto-reset behind it do not enter (a NEXT_STEP reset already pending gives
+        dx = du = 0).  The physics is the float64 arithmetic of the step kernels (per-env vehicles, both thrust
+        laws, the rotor-gyro term, `substeps` calls with the pending perturbation in the first); under
+        action_arith="float32" it is still the float64 motor law.
+
+        state=None linearises at the stored state the next step() starts from (float32 storage modes: the decoded
+        words get_state() reports).  state={"x": [12,N] float64, "status": [N] uint8, "force": [3,N] newtons
+        (optional, pending)} -- the keys and shapes of get_state() / set_state() -- linearises at that point instead
+        (hover, a planned trajectory).  dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).
+        Asynchronous on the current stream; the returned tensors are buffers of this env, overwritten by the next
+        call with the same dtype."""
+        self._check_open()
+        torch = _torch()
+        dtype = torch.float64 if dtype is None else dtype
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("dtype must be torch.float64 or torch.float32")
+        n, ad = self.num_envs, self.action_dim
+        a, _ = self._dev_f32(actions, (n, ad), "actions")
+        io = _lib.JacobianIO()
+        io.struct_size = C.sizeof(_lib.JacobianIO)
+        io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+        io.actions_dev = a.data_ptr()
+        keep = [a]
+        if state is not None:
+            unknown = set(state) - {"x", "status", "force"}
+            if unknown or "x" not in state or "status" not in state:
+                raise ValueError("state needs the keys 'x' and 'status' (and optionally 'force'), got %s"
+                                 % sorted(state))
+
+            def dev(v, shape, dt, name):
+                t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+                if tuple(t.shape) != shape:
+                    raise ValueError("state[%r] must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+                t = t.to(device=self.device, dtype=dt, non_blocking=True).contiguous()
+                keep.append(t)
+                return t.data_ptr()
+            io.x_dev = dev(state["x"], (12, n), torch.float64, "x")
+            io.status_dev = dev(state["status"], (n,), torch.uint8, "status")
+            if state.get("force") is not None:
+                io.force_dev = dev(state["force"], (3, n), torch.float64, "force")
+        cache = getattr(self, "_jac_out", None)
+        if cache is None:
+            cache = self._jac_out = {}
+        out = cache.get(dtype)
+        if out is None:
+            out = cache[dtype] = StepJacobian(
+                torch.empty((n, 12, 12), dtype=dtype, device=self.device),
+                torch.empty((n, 12, ad), dtype=dtype, device=self.device),
+                torch.empty((n, 12), dtype=dtype, device=self.device),
+                torch.empty((n, ad), dtype=dtype, device=self.device),
+                torch.empty(n, dtype=torch.uint8, device=self.device))
+        io.dx_dev, io.du_dev, io.reward_dx_dev, io.reward_du_dev, io.branch_dev = (t.data_ptr() for t in out)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_step_jacobian(self._ctx, C.byref(io), self._stream()))
+        self._keep = keep
+        return out
+
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""
         self._check_open()

@@ -19,6 +19,8 @@
  *                            which calls Dynamics.setMotors     dynamics/__init__.py:114-197,249-302
  *   cs_step_many             K x _Task.step in one launch       envs/task.py:77-137 (lander.py:40-65 loop)
  *   cs_set_motors            Dynamics.setMotors (used directly) dynamics/__init__.py:114-197
+ *   cs_step_jacobian         d(_Task.step)/d(state, action)     dynamics/__init__.py:114-197,249-302, envs/task.py:77-137,
+ *                            and the reward gradient            envs/lander.py:46-74 (no state written)
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -493,6 +495,53 @@ int cs_device_pci_address(const cs_ctx* ctx, char* out, int32_t len);
 /* Physics only: `substeps` x Dynamics.setMotors(motors[i]) on every env, raw motor
  * values (no clipping, no task logic). */
 int cs_set_motors(cs_ctx* ctx, const float* motors_dev, void* stream);
+
+/* Jacobians of one env step (dynamics/__init__.py:114-197 setMotors, :249-290 the state derivative, :292-302
+ * _bodyZToInertial; envs/task.py:77-137 step, incl. the clip of :91 and the LANDED skip of :86-87; envs/lander.py:46-74
+ * the reward): for every env, the derivatives of the transition cs_step(actions) would perform from the evaluation
+ * point.  NOTHING of the env state is read-modified-written: the next cs_step is unaffected.
+ *   dx_dev        [N,12,12]    d x' / d x   (x in upstream slot order, as cs_get_state's x)
+ *   du_dev        [N,12,A]     d x' / d action, the action as cs_step receives it (before the clip; the clip's
+ *                              derivative is 1 on the closed interval [0, 1] and 0 outside); A = cs_action_dim
+ *   reward_dx_dev [N,12], reward_du_dev [N,A]   the gradient of the step's reward (Lander: of the shaping potential
+ *                              of x', lander.py:46-57; its constants -- the |dz| > dz_max penalty, the out-of-bounds
+ *                              penalty, the landing bonus, prev_shaping -- have none; a tilt (reward = -penalty), a
+ *                              prev_shaping of None (reward 0), a pending reset and every Hover task give zero)
+ *   branch_dev    [N] uint8    CS_JAC_* bits: which branches of the step the Jacobian is that of
+ * Every output pointer may be NULL (not written); outputs are env-major and contiguous, float64 (out_dtype =
+ * CS_JAC_F64) or float32 (CS_JAC_F32: the float64 values rounded).  The physics is the float64 arithmetic of the step
+ * kernels, per-env vehicle table, both thrust laws and the rotor-gyro term included, chained through cfg.substeps calls
+ * with the pending perturbation in the first; under action_arith = CS_ARITH_F32 it is still the float64 motor law.
+ * The transition is physics + reward with auto-reset DISABLED: a termination in this step and the auto-reset behind it
+ * do not enter; a NEXT_STEP reset already pending gives dx = du = 0 (the step replaces the state).
+ * Evaluation point: the stored state the next cs_step starts from (x_dev == NULL: the decoded words, status, pending
+ * perturbation, reset-pending flag), or the caller's x_dev [12,N] float64 + status_dev [N] (CS_STATUS_*) + optional
+ * force_dev [3,N] newtons, pending (the layout of cs_get_state; no reset pending, prev_shaping taken as defined).
+ * Asynchronous on `stream`.  io->struct_size must be sizeof(cs_jacobian_io) (else CS_ERR_ABI). */
+typedef struct cs_jacobian_io {
+  uint32_t struct_size;       /* sizeof(cs_jacobian_io) */
+  uint32_t out_dtype;         /* CS_JAC_F64 / CS_JAC_F32 */
+  const float* actions_dev;   /* [N,A] float32, required */
+  const double* x_dev;        /* [12,N] explicit point, or NULL = the stored state */
+  const uint8_t* status_dev;  /* [N] required with x_dev */
+  const double* force_dev;    /* [3,N] newtons, optional with x_dev (NULL = no perturbation pending) */
+  void* dx_dev;
+  void* du_dev;
+  void* reward_dx_dev;
+  void* reward_du_dev;
+  uint8_t* branch_dev;
+} cs_jacobian_io;
+enum { CS_JAC_F64 = 0, CS_JAC_F32 = 1 };
+enum {
+  CS_JAC_INTEGRATED = 1,  /* at least one setMotors call integrated */
+  CS_JAC_LANDED = 2,      /* LANDED at the start: physics skipped, dx = I, du = 0 */
+  CS_JAC_CONTACT = 4,     /* a call froze on ground contact (:162-177): identity rows from there on */
+  CS_JAC_LEVELING = 8,    /* a call levelled the wings: the phi, theta rows are zero */
+  CS_JAC_CRASHED = 16,    /* a call found the env CRASHED: it only ticks */
+  CS_JAC_RESET = 32,      /* a NEXT_STEP reset is pending: dx = du = 0 */
+  CS_JAC_CLIPPED = 64     /* some motor value was outside [0, 1]: its columns are zero */
+};
+int cs_step_jacobian(cs_ctx* ctx, const cs_jacobian_io* io, void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in
