@@ -74,7 +74,18 @@ class JacobianIO(C.Structure):
                 ("reward_dx_dev", C.c_void_p), ("reward_du_dev", C.c_void_p), ("branch_dev", C.c_void_p)]
 
 
-JAC_F64, JAC_F32 = 0, 1                                      # cs_jacobian_io.out_dtype
+JAC_F64, JAC_F32 = 0, 1                                      # cs_jacobian_io.out_dtype, cs_rollout_io.out_dtype
+
+
+class RolloutIO(C.Structure):
+    """Mirror of `struct cs_rollout_io` (cs_rollout_states / cs_rollout_vjp)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_steps", C.c_int32),
+                ("reserved_", C.c_uint32), ("actions_dev", C.c_void_p), ("start_x_dev", C.c_void_p),
+                ("start_status_dev", C.c_void_p), ("start_force_dev", C.c_void_p),
+                ("start_prev_shaping_dev", C.c_void_p), ("x_dev", C.c_void_p), ("reward_dev", C.c_void_p),
+                ("terminated_dev", C.c_void_p), ("truncated_dev", C.c_void_p), ("status_dev", C.c_void_p),
+                ("gx_dev", C.c_void_p), ("gr_dev", C.c_void_p), ("g_actions_dev", C.c_void_p),
+                ("g_x0_dev", C.c_void_p)]
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
 JAC_INTEGRATED, JAC_LANDED, JAC_CONTACT, JAC_LEVELING, JAC_CRASHED, JAC_RESET, JAC_CLIPPED = 1, 2, 4, 8, 16, 32, 64
 
@@ -132,6 +143,8 @@ SYMBOLS = {
     "cs_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "cs_step_ex": (C.c_int, [_P, C.POINTER(StepIO), _P]),
     "cs_step_jacobian": (C.c_int, [_P, C.POINTER(JacobianIO), _P]),
+    "cs_rollout_states": (C.c_int, [_P, C.POINTER(RolloutIO), _P]),
+    "cs_rollout_vjp": (C.c_int, [_P, C.POINTER(RolloutIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

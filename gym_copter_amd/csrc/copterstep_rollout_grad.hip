@@ -1,0 +1,573 @@
+// copterstep_rollout_grad.hip -- differentiable K-step rollouts on gfx950 (cs_rollout_states / cs_rollout_vjp,
+// include/copterstep.h): the states, rewards and flags of K steps with auto-reset disabled, and the reverse-mode gradient
+// of a loss on them with respect to the actions and the start state.  Nothing of the env state is written.
+//
+// Upstream lines differentiated (paths relative to the upstream checkout):
+//   dynamics/__init__.py:114-197 (setMotors), :249-290 (state derivative), :292-302 (_bodyZToInertial),
+//   envs/task.py:77-137 (step: the clip of :91, the LANDED skip of :86-87), envs/lander.py:46-74 (reward, whose
+//   prev_shaping makes reward_k a function of x_{k-1} as well as of x_k).
+//
+// One lane per env on the tile layout of the step kernels (tile t -> workgroup t).  The forward kernel keeps the env in
+// registers for K steps (the pieces of advance(): physics_substeps, the stored-word rounding, judge_step) and writes
+// each step's state row through the LDS.  The backward kernel sweeps k = K .. 1 with the adjoint in registers; each
+// step's primal is recomputed from the caller's tape (the forward's x and status rows), the substep start states from
+// the step's start (O(substeps^2) calls).  DESIGN.md section 10.
+#include <string>
+
+#include "copterstep_jacobian.h"
+
+// the primal must round as the step kernels do (copterstep_kernels.hip): the backward's recomputed primal is the tape
+// bit for bit, or its branch decisions could differ from the forward's
+#pragma clang fp contract(off)
+
+#include "dev_tile.h"
+#include "dev_codec.h"
+#include "dev_math.h"
+#include "dev_physics.h"
+#include "dev_task.h"
+#include "jacobian_tangents.h"
+#include "rollout_adjoint.h"
+
+#ifdef CS_DEBUG_ROLLOUT  // debug build (make DEFS=-DCS_DEBUG_ROLLOUT exp NAME=debug): the recompute is checked
+#include <cassert>
+#endif
+
+namespace cs {
+namespace {
+
+// The caller's explicit start point of env i (cs_rollout_io.start_*): x, status, pending force, prev_shaping.  Without a
+// prev_shaping it is shaping(x0), rounded to a stored word as step() stores it (differentiated by the backward).
+template <int TASK, int MODE>
+__device__ __forceinline__ void explicit_start(const DevConst& c, const Coef& q, const cs_rollout_io& io, uint32_t i,
+                                               uint32_t n, bool valid, double (&x)[12], int& fs, bool& pend,
+                                               double& px, double& py, double& pz, double& prev_sh) {
+  using T = typename ModeOf<MODE>::T;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) x[k] = valid ? io.start_x_dev[(size_t)k * n + i] : 0.0;
+  fs = valid ? (int)io.start_status_dev[i] : CS_STATUS_AIRBORNE;
+  pend = io.start_force_dev != nullptr;
+  px = py = pz = -0.0;
+  if (pend && valid) {
+    px = io.start_force_dev[i] * q.two_inv_M;
+    py = io.start_force_dev[(size_t)n + i] * q.two_inv_M;
+    pz = io.start_force_dev[(size_t)2 * n + i] * q.two_inv_M;
+  }
+  if (io.start_prev_shaping_dev != nullptr) {
+    prev_sh = valid ? io.start_prev_shaping_dev[i] : 0.0;
+  } else if constexpr (task_is_lander(TASK)) {
+    prev_sh = (double)(T)lander_shaping(c, x);
+  } else {
+    prev_sh = 0.0;
+  }
+}
+
+// One _Task.step() with auto-reset disabled, from the pieces advance() (dev_task.h) is built from, in its order: the
+// clip and motor law, physics_substeps (the K-step form, IN_LOOP), the stored-word rounding, judge_step and the
+// prev_shaping / step counter updates, and a NEXT_STEP reset already pending (only ever in the first step).  The
+// perturbation is passed in (px, py, pz); e.pend says on return whether it is still pending.
+template <int TASK, int MODE>
+__device__ __forceinline__ void rollout_step(const DevConst& c, const Coef& q, Env<MODE>& e, const float4 act,
+                                             double px, double py, double pz, double& reward, bool& term,
+                                             bool& trunc) {
+  using T = typename ModeOf<MODE>::T;
+  constexpr bool FULL = MODE == CS_STATE_F64 || kFullTrigInEveryMode;
+  const bool resetting = e.reset_pending;
+  const int status0 = e.fs;
+  if (!resetting && status0 != CS_STATUS_LANDED) {
+    const float a0 = clip01(act.x), a1 = clip01(act.y), a2 = clip01(act.z), a3 = clip01(act.w);
+    Wrench w;
+    if (c.act_f32) {
+      w = motor_model_f32(c, a0, a1, a2, a3);
+    } else {
+      w.bz = thrust_model(q, a0, a1, a2, a3);
+      torque_model(q, a0, a1, a2, a3, w);
+    }
+    if (c.gyro) {
+      physics_substeps<FULL, true, false, true>(c, q, w, e.x, e.fs, e.pend, px, py, pz);
+    } else {
+      physics_substeps<FULL, false, false, true>(c, q, w, e.x, e.fs, e.pend, px, py, pz);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) e.x[k] = round_stored<MODE>(e.x[k]);
+  reward = 0.0;
+  term = trunc = false;
+  if (!resetting) {
+    double sh = 0.0;
+    if constexpr (task_is_lander(TASK)) sh = lander_shaping(c, e.x);
+    const Verdict v = judge_step<TASK>(c, c.tl_trunc != 0, status0, e.steps, sh, e.prev_sh,
+                                       test_inside(c, e.x[0], e.x[2]), test_oob(c, e.x[0], e.x[2]),
+                                       test_tilt(c, e.x[6], e.x[8]));
+    if constexpr (task_is_lander(TASK)) e.prev_sh = (double)(T)sh;
+    reward = v.reward;
+    term = v.term;
+    trunc = v.trunc;
+    e.steps = min(e.steps + 1, (int)c.steps_mask);
+  } else {  // the masked reset of advance(): fresh state, the next episode (its perturbation pending), steps = 1
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+      const T w0 = (k == 4) ? (T)c.z0 : (T)0;
+      e.x[k] = (double)w0;
+    }
+    next_episode<MODE, true>(e);
+    e.fs = c.status0;
+    e.pend = true;
+    e.expl = false;
+    e.steps = 1;
+    e.prev_sh = c.reset_shaping;
+    e.reset_pending = false;
+  }
+}
+
+template <int TASK, int MODE>
+__global__ __launch_bounds__(kBlock) void rollout_states_kernel(const DevConst c, const DevState s,
+                                                                const cs_rollout_io io) {
+  constexpr int A = task_act_dim(TASK);
+  __shared__ __attribute__((aligned(16))) double xrow[kBlock * 12];  // 6 KiB: the wavefront's state rows of a step
+  const int lane = threadIdx.x;
+  const uint32_t tile_index = blockIdx.x;
+  const uint32_t i = tile_index * kBlock + threadIdx.x;
+  const uint32_t n = s.n;
+  const uint32_t env0 = i - lane;
+  const bool valid = i < n;
+  const bool whole = env0 + (uint32_t)kWave <= n;
+
+  Coef q = uniform_coef(c);
+  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, valid ? i : 0u);
+  // the stored env, decoded as step_many_kernel decodes it (its counters are the rollout's in both start forms)
+  using TILE = TileIO<MODE>;
+  const TILE tile(s, tile_index, lane);
+  Env<MODE> e;
+  unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
+  resolve_episode<MODE>(c, tile, e);
+  double px, py, pz;
+  if (io.start_x_dev != nullptr) {
+    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
+    e.reset_pending = false;
+  } else {
+    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+  }
+
+  const float* act_lane = io.actions_dev + (size_t)(valid ? i : 0u) * A;
+  const size_t act_step = (size_t)n * A;
+#pragma clang loop unroll(disable)
+  for (int k = 0; k < io.num_steps; ++k) {
+    const float4 act = load_action_at<TASK>(act_lane);
+    act_lane += act_step;
+    const bool resetting = e.reset_pending;
+    double reward;
+    bool term, trunc;
+    rollout_step<TASK, MODE>(c, q, e, act, px, py, pz, reward, term, trunc);
+    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
+      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+    } else if (!e.pend) {
+      px = py = pz = -0.0;
+    }
+
+    const size_t row = (size_t)k * n;  // 64-bit: K x N x 12 doubles pass 4 GiB at 1 M envs
+    if (io.x_dev != nullptr) {
+      if (whole) {  // 64 rows of 96 B through the LDS: six 1 KiB stores of 16 B per lane
+#pragma unroll
+        for (int j = 0; j < 12; j += 2)
+          *reinterpret_cast<double2*>(xrow + lane * 12 + j) = make_double2(e.x[j], e.x[j + 1]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const double2* src = reinterpret_cast<const double2*>(xrow);
+        double2* dst = reinterpret_cast<double2*>(io.x_dev + (row + env0) * 12);
+#pragma unroll
+        for (int v = 0; v < 6; ++v) dst[v * kWave + lane] = src[v * kWave + lane];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      } else if (valid) {
+        double* dst = io.x_dev + (row + i) * 12;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) dst[j] = e.x[j];
+      }
+    }
+    if (valid) {
+      if (io.reward_dev != nullptr) io.reward_dev[row + i] = reward;
+      if (io.terminated_dev != nullptr) io.terminated_dev[row + i] = term ? 1 : 0;
+      if (io.truncated_dev != nullptr) io.truncated_dev[row + i] = trunc ? 1 : 0;
+      if (io.status_dev != nullptr) io.status_dev[row + i] = (uint8_t)e.fs;
+    }
+  }
+}
+
+// What the backward recomputes one step from: its start state and status, and its action.
+struct StepIn {
+  double x[12];
+  int fs;
+  float4 act;
+};
+
+// lam += the cotangent of step k's x row; returns that of its reward
+__device__ __forceinline__ double add_cotangents(const cs_rollout_io& io, size_t row, uint32_t i, double (&lam)[12]) {
+  if (io.gx_dev != nullptr) {
+    const double2* g = reinterpret_cast<const double2*>(io.gx_dev + (row + i) * 12);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const double2 v = g[j];
+      lam[2 * j] += v.x;
+      lam[2 * j + 1] += v.y;
+    }
+  }
+  return io.gr_dev != nullptr ? io.gr_dev[row + i] : 0.0;
+}
+
+// step k (0-based) >= 1: its start is the tape's row k - 1
+template <int TASK>
+__device__ __forceinline__ void load_tape_step(const cs_rollout_io& io, uint32_t n, uint32_t i, int k, StepIn& in) {
+  const size_t prev = (size_t)(k - 1) * n;
+  const double2* xr = reinterpret_cast<const double2*>(io.x_dev + (prev + i) * 12);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const double2 v = xr[j];
+    in.x[2 * j] = v.x;
+    in.x[2 * j + 1] = v.y;
+  }
+  in.fs = (int)io.status_dev[prev + i];
+  in.act = load_action_at<TASK>(io.actions_dev + ((size_t)k * n + i) * task_act_dim(TASK));
+}
+
+// The adjoint of one step.  On entry `lam` is the adjoint of the state after the step (the cotangent of its x row
+// included), on exit that of its start state; ga = the gradient of its action row.  The step's primal is recomputed
+// from its start with the arithmetic of physics_call() (as jacobian_block does), call by call:
+//   resetting  a NEXT_STEP reset pending (first step of a stored start only): the step replaces the state, all zero
+//   prev_diff  prev_shaping is shaping(start) and differentiated (every step but the first; the first of an explicit
+//              start without a prev_shaping), prev_none = upstream's None (reward 0)
+template <int TASK, int MODE, bool GYRO>
+__device__ __forceinline__ void step_adjoint(const DevConst& c, const Coef& q, const StepIn& in, double gr, double px0,
+                                             double py0, double pz0, bool resetting, bool prev_diff, bool prev_none,
+                                             const double* tape_next, double (&lam)[12], double (&ga)[4]) {
+  constexpr int A = task_act_dim(TASK);
+  constexpr bool FULL = MODE == CS_STATE_F64 || kFullTrigInEveryMode;
+  const float araw[4] = {in.act.x, in.act.y, in.act.z, in.act.w};
+  float mf[4];
+  double m[4], clipd[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    mf[j] = clip01(araw[j]);
+    m[j] = (double)mf[j];
+    clipd[j] = (araw[j] >= 0.f && araw[j] <= 1.f) ? 1.0 : 0.0;
+  }
+  Wrench w;  // the wrench the step applied (its derivative below is the float64 law's, as in cs_step_jacobian)
+  if (c.act_f32) {
+    w = motor_model_f32(c, mf[0], mf[1], mf[2], mf[3]);
+  } else {
+    w.bz = thrust_model(q, mf[0], mf[1], mf[2], mf[3]);
+    torque_model(q, mf[0], mf[1], mf[2], mf[3], w);
+  }
+  const bool active = !resetting && in.fs != CS_STATUS_LANDED;
+  const int nsub = c.nsub;
+
+  // the primal of `upto` calls from the step's start (the perturbation in the first), then the sin / cos and the plan
+  // of call `upto` at the state reached: x = the start of that call
+  auto primal_to = [&](int upto, double (&x)[12], Trig& t, CallPlan& p, double& ax, double& ay, double& netz) {
+    int fs = in.fs;
+    double px = px0, py = py0, pz = pz0;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) x[k] = in.x[k];
+#pragma clang loop unroll(disable)
+    for (int sub = 0;; ++sub) {
+      sincos_roll_pitch<FULL, false>(c, x[6], x[8], t);
+      sincos_yaw<FULL, false>(c, x[10], t);
+      thrust_ned(q, w.bz, t, ax, ay, netz);
+      p = plan_call(c, fs, netz, x[4], x[5], x[3], x[6]);
+      if (!active) p = CallPlan{false, false, false, fs};
+      if (sub == upto) break;
+      const double dt = p.integ ? c.dt : 0.0;
+      euler_translation(dt, ax, ay, netz, px, py, pz, x);
+      euler_rotation<GYRO>(q, w, dt, p.leveling, x + 6);
+      fs = p.fs_next;
+      px = py = pz = -0.0;
+    }
+  };
+
+  // ---- the last call: its sin / cos, plan and angular rates (what its adjoint reads), then x' in place ----
+  double x[12];
+  Trig t;
+  CallPlan p;
+  double ax, ay, netz;
+  primal_to(nsub - 1, x, t, p, ax, ay, netz);
+  const double dtl = p.integ ? c.dt : 0.0;
+  const bool levl = p.leveling;
+  double rates[12];  // (only slots 7, 9, 11 are read)
+  rates[7] = x[7];
+  rates[9] = x[9];
+  rates[11] = x[11];
+  euler_translation(dtl, ax, ay, netz, nsub == 1 ? px0 : -0.0, nsub == 1 ? py0 : -0.0, nsub == 1 ? pz0 : -0.0, x);
+  euler_rotation<GYRO>(q, w, dtl, levl, x + 6);
+  double (&xn)[12] = x;
+#ifdef CS_DEBUG_ROLLOUT
+  if (tape_next != nullptr) {
+    for (int k = 0; k < 12; ++k) assert(round_stored<MODE>(xn[k]) == tape_next[k] || xn[k] != xn[k]);
+  }
+#endif
+  // ---- reward: grad shaping(x'), and -grad shaping(start) through prev_shaping; none under a tilt (reward =
+  //      -penalty, tested on the stored words), a None, a reset, or a Hover task ----
+  bool rew = false;
+  if constexpr (task_is_lander(TASK)) {
+    const bool tilt = !test_oob(c, round_stored<MODE>(xn[0]), round_stored<MODE>(xn[2])) &&
+                      test_tilt(c, round_stored<MODE>(xn[6]), round_stored<MODE>(xn[8]));
+    rew = !resetting && !prev_none && !tilt;
+    if (rew) {
+      double gs[12];
+      shaping_gradient(c, xn, gs);
+#pragma unroll
+      for (int k = 0; k < 12; ++k) lam[k] = fma(gr, gs[k], lam[k]);
+    }
+  }
+
+  // ---- the calls in reverse: call `sub` at its start state, recomputed from the step's start ----
+  Wrench mw{0.0, 0.0, 0.0, 0.0, 0.0};
+  euler_adjoint<GYRO>(q, w, t, rates, dtl, levl, lam, mw);
+#pragma clang loop unroll(disable)
+  for (int sub = nsub - 2; sub >= 0; --sub) {
+    primal_to(sub, x, t, p, ax, ay, netz);
+    euler_adjoint<GYRO>(q, w, t, x, p.integ ? c.dt : 0.0, p.leveling, lam, mw);
+  }
+  if (rew && prev_diff) {  // reward = shaping(x') - shaping(start): the telescoping term
+    double gs[12];
+    shaping_gradient(c, in.x, gs);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) lam[k] = fma(-gr, gs[k], lam[k]);
+  }
+  motor_adjoint<A>(q, m, clipd, mw, ga);
+  if (resetting) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) lam[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ga[k] = 0.0;
+  }
+}
+
+template <class OUT, int A>
+__device__ __forceinline__ void store_ga(void* dst, size_t row, uint32_t i, const double (&ga)[4]) {
+  OUT* d = reinterpret_cast<OUT*>(dst) + (row + i) * A;
+#pragma unroll
+  for (int j = 0; j < A; ++j) d[j] = (OUT)ga[j];
+}
+
+template <int TASK, int MODE, bool GYRO>
+__global__ __launch_bounds__(kBlock) void rollout_vjp_kernel(const DevConst c, const DevState s,
+                                                             const cs_rollout_io io) {
+  constexpr int A = task_act_dim(TASK);
+  const int lane = threadIdx.x;
+  const uint32_t tile_index = blockIdx.x;
+  const uint32_t i = tile_index * kBlock + threadIdx.x;
+  const uint32_t n = s.n;
+  const bool valid = i < n;
+  const uint32_t ii = valid ? i : 0u;  // (padding lanes recompute env 0's steps and store nothing)
+  const int K = io.num_steps;
+  const bool f32out = io.out_dtype == CS_JAC_F32;
+
+  Coef q = uniform_coef(c);
+  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
+  double lam[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) lam[k] = 0.0;
+  double ga[4];
+
+  // ---- steps K-1 .. 2: starts from the tape, the next step's inputs fetched while this one computes ----
+  StepIn cur;
+  if (K > 1) load_tape_step<TASK>(io, n, ii, K - 1, cur);
+#pragma clang loop unroll(disable)
+  for (int k = K - 1; k >= 2; --k) {
+    StepIn nxt;  // (the earlier step's tape row and action, in flight while this step computes)
+    load_tape_step<TASK>(io, n, ii, k - 1, nxt);
+    const double gr = add_cotangents(io, (size_t)k * n, ii, lam);
+    const double* tape_next = nullptr;
+#ifdef CS_DEBUG_ROLLOUT
+    tape_next = io.x_dev + ((size_t)k * n + ii) * 12;
+#endif
+    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, -0.0, -0.0, -0.0, false, true, false, tape_next, lam, ga);
+    if (valid && io.g_actions_dev != nullptr) {
+      if (f32out)
+        store_ga<float, A>(io.g_actions_dev, (size_t)k * n, i, ga);
+      else
+        store_ga<double, A>(io.g_actions_dev, (size_t)k * n, i, ga);
+    }
+    cur = nxt;
+  }
+
+  // ---- step 1 (peeled: the loop's steps have no perturbation) ----
+  // A stored-start lane with a NEXT_STEP reset pending resets in step 0, and the new episode's perturbation (the draw
+  // step() makes) enters the first call of step 1: its recompute needs it, or its x' is not the tape's.  Every other
+  // perturbation is consumed in step 0 or only ever meets calls that do not integrate.
+  if (K > 1) {
+    double px = -0.0, py = -0.0, pz = -0.0;
+    if (io.start_x_dev == nullptr) {
+      using TILE = TileIO<MODE>;
+      const TILE tile(s, tile_index, lane);
+      Env<MODE> e;
+      unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
+      if (e.reset_pending) {  // (rollout_step's masked reset, then the forward's draw for the new episode)
+        resolve_episode<MODE>(c, tile, e);
+        next_episode<MODE, true>(e);
+        pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, true, false, px, py, pz);
+      }
+    }
+    const double gr = add_cotangents(io, (size_t)n, ii, lam);
+    const double* tape_next = nullptr;
+#ifdef CS_DEBUG_ROLLOUT
+    tape_next = io.x_dev + ((size_t)n + ii) * 12;
+#endif
+    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, px, py, pz, false, true, false, tape_next, lam, ga);
+    if (valid && io.g_actions_dev != nullptr) {
+      if (f32out)
+        store_ga<float, A>(io.g_actions_dev, (size_t)n, i, ga);
+      else
+        store_ga<double, A>(io.g_actions_dev, (size_t)n, i, ga);
+    }
+  }
+
+  // ---- step 0: from the start point, decoded as the forward decoded it ----
+  StepIn in;
+  double px, py, pz;
+  bool resetting = false, prev_diff = false, prev_none = false;
+  if (io.start_x_dev != nullptr) {
+    bool pend;
+    double prev_sh;
+    explicit_start<TASK, MODE>(c, q, io, i, n, valid, in.x, in.fs, pend, px, py, pz, prev_sh);
+    prev_diff = io.start_prev_shaping_dev == nullptr;
+    prev_none = prev_sh != prev_sh;
+  } else {
+    using TILE = TileIO<MODE>;
+    const TILE tile(s, tile_index, lane);
+    Env<MODE> e;
+    unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
+    resolve_episode<MODE>(c, tile, e);
+    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) in.x[k] = e.x[k];
+    in.fs = e.fs;
+    resetting = e.reset_pending;
+    prev_none = e.prev_sh != e.prev_sh;
+  }
+  in.act = load_action_at<TASK>(io.actions_dev + (size_t)ii * A);
+  const double gr0 = add_cotangents(io, 0, ii, lam);
+  const double* tape_next = nullptr;
+#ifdef CS_DEBUG_ROLLOUT
+  if (!resetting) tape_next = io.x_dev + (size_t)ii * 12;  // (a resetting step is not recomputed: its gradient is 0)
+#endif
+  step_adjoint<TASK, MODE, GYRO>(c, q, in, gr0, px, py, pz, resetting, prev_diff, prev_none, tape_next, lam, ga);
+  if (valid) {
+    if (io.g_actions_dev != nullptr) {
+      if (f32out)
+        store_ga<float, A>(io.g_actions_dev, 0, i, ga);
+      else
+        store_ga<double, A>(io.g_actions_dev, 0, i, ga);
+    }
+    if (io.g_x0_dev != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        if (f32out)
+          reinterpret_cast<float*>(io.g_x0_dev)[(size_t)k * n + i] = (float)lam[k];
+        else
+          reinterpret_cast<double*>(io.g_x0_dev)[(size_t)k * n + i] = lam[k];
+      }
+    }
+  }
+}
+
+#define CS_RG_TASKS(M)                           \
+  switch (task) {                                \
+    case CS_TASK_LANDER3D: M(CS_TASK_LANDER3D); break; \
+    case CS_TASK_HOVER3D: M(CS_TASK_HOVER3D); break;   \
+    case CS_TASK_LANDER2D: M(CS_TASK_LANDER2D); break; \
+    case CS_TASK_LANDER1D: M(CS_TASK_LANDER1D); break; \
+    case CS_TASK_HOVER2D: M(CS_TASK_HOVER2D); break;   \
+    case CS_TASK_HOVER1D: M(CS_TASK_HOVER1D); break;   \
+    default: return hipErrorInvalidValue;        \
+  }
+
+hipError_t launch_rollout_states(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                                 hipStream_t stream) {
+  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
+#define CS_RS_MODE(TASK)                                                                                          \
+  do {                                                                                                            \
+    if (mode == CS_STATE_F32G)                                                                                    \
+      hipLaunchKernelGGL((rollout_states_kernel<TASK, CS_STATE_F32G>), grid, block, 0, stream, c, s, io);          \
+    else if (mode == CS_STATE_F32_RN)                                                                             \
+      hipLaunchKernelGGL((rollout_states_kernel<TASK, CS_STATE_F32_RN>), grid, block, 0, stream, c, s, io);        \
+    else                                                                                                          \
+      hipLaunchKernelGGL((rollout_states_kernel<TASK, CS_STATE_F64>), grid, block, 0, stream, c, s, io);           \
+  } while (0)
+  CS_RG_TASKS(CS_RS_MODE)
+#undef CS_RS_MODE
+  return hipGetLastError();
+}
+
+hipError_t launch_rollout_vjp(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                              hipStream_t stream) {
+  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
+#define CS_RV_GYRO(TASK, MODE)                                                                                    \
+  do {                                                                                                            \
+    if (c.gyro)                                                                                                   \
+      hipLaunchKernelGGL((rollout_vjp_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io);               \
+    else                                                                                                          \
+      hipLaunchKernelGGL((rollout_vjp_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io);              \
+  } while (0)
+#define CS_RV_MODE(TASK)                                                                                          \
+  do {                                                                                                            \
+    if (mode == CS_STATE_F32G)                                                                                    \
+      CS_RV_GYRO(TASK, CS_STATE_F32G);                                                                            \
+    else if (mode == CS_STATE_F32_RN)                                                                             \
+      CS_RV_GYRO(TASK, CS_STATE_F32_RN);                                                                          \
+    else                                                                                                          \
+      CS_RV_GYRO(TASK, CS_STATE_F64);                                                                             \
+  } while (0)
+  CS_RG_TASKS(CS_RV_MODE)
+#undef CS_RV_MODE
+#undef CS_RV_GYRO
+  return hipGetLastError();
+}
+#undef CS_RG_TASKS
+
+// the argument block, checked before the context (a caller's layout error is reported as such, without a device)
+int check_rollout_io(const cs_rollout_io* io, const char* who, bool vjp) {
+  const std::string w(who);
+  if (io == nullptr) return report_error(CS_ERR_ARG, (w + ": null io").c_str());
+  if (io->struct_size != sizeof(cs_rollout_io))
+    return report_error(CS_ERR_ABI, (w + ": io->struct_size " + std::to_string(io->struct_size) + " != " +
+                                     std::to_string(sizeof(cs_rollout_io)) + " (sizeof(cs_rollout_io))").c_str());
+  if (io->num_steps < 1) return report_error(CS_ERR_ARG, (w + ": num_steps must be >= 1").c_str());
+  if (io->actions_dev == nullptr) return report_error(CS_ERR_ARG, (w + ": actions_dev is required").c_str());
+  if (io->start_x_dev == nullptr &&
+      (io->start_status_dev != nullptr || io->start_force_dev != nullptr || io->start_prev_shaping_dev != nullptr))
+    return report_error(CS_ERR_ARG,
+                        (w + ": start_status_dev / start_force_dev / start_prev_shaping_dev describe an explicit start: "
+                             "start_x_dev is required").c_str());
+  if (io->start_x_dev != nullptr && io->start_status_dev == nullptr)
+    return report_error(CS_ERR_ARG, (w + ": an explicit start needs start_status_dev").c_str());
+  if (vjp) {
+    if (io->out_dtype != CS_JAC_F64 && io->out_dtype != CS_JAC_F32)
+      return report_error(CS_ERR_ARG, (w + ": unknown out_dtype (CS_JAC_F64 or CS_JAC_F32)").c_str());
+    if (io->x_dev == nullptr || io->status_dev == nullptr)
+      return report_error(CS_ERR_ARG, (w + ": the tape (x_dev and status_dev of cs_rollout_states) is required").c_str());
+  }
+  return CS_OK;
+}
+
+}  // namespace
+}  // namespace cs
+
+extern "C" int cs_rollout_states(cs_ctx* ctx, const cs_rollout_io* io, void* stream) {
+  if (int rc_ = cs::check_rollout_io(io, "cs_rollout_states", false)) return rc_;
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, "cs_rollout_states", stream, &v)) return rc_;
+  const hipError_t e = cs::launch_rollout_states(v.task, v.mode, *v.c, *v.s, *io, (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_states: kernel launch");
+  return CS_OK;
+}
+
+extern "C" int cs_rollout_vjp(cs_ctx* ctx, const cs_rollout_io* io, void* stream) {
+  if (int rc_ = cs::check_rollout_io(io, "cs_rollout_vjp", true)) return rc_;
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, "cs_rollout_vjp", stream, &v)) return rc_;
+  const hipError_t e = cs::launch_rollout_vjp(v.task, v.mode, *v.c, *v.s, *io, (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_vjp: kernel launch");
+  return CS_OK;
+}

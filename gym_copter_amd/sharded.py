@@ -187,6 +187,24 @@ class ShardedCopterVecEnv:
         global [N, A], as step() takes them; an explicit `state` covers the local envs)."""
         return self.local.step_jacobian(self._local_actions(actions), state=state, dtype=dtype)
 
+    def _local_rollout_actions(self, actions):
+        if actions.shape[1] == self.n_local:
+            return actions
+        if actions.shape[1] == self.total_envs:
+            return actions[:, self.local_slice()]
+        raise ValueError("actions must have %d (local) or %d (global) envs in dimension 1, got %d"
+                         % (self.n_local, self.total_envs, actions.shape[1]))
+
+    def rollout_states(self, actions, state=None):
+        """CopterVecEnv.rollout_states of this rank's envs: shard-local, no gather (actions: [K, n_local, A] or the
+        global [K, N, A]; an explicit `state` covers the local envs)."""
+        return self.local.rollout_states(self._local_rollout_actions(actions), state=state)
+
+    def rollout_vjp(self, actions, rollout, gx=None, gr=None, state=None, dtype=None):
+        """CopterVecEnv.rollout_vjp of this rank's envs: shard-local (rollout, gx, gr: the local envs')."""
+        return self.local.rollout_vjp(self._local_rollout_actions(actions), rollout, gx=gx, gr=gr, state=state,
+                                      dtype=dtype)
+
     def close(self):
         self.local.close()
 

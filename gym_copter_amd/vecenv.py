@@ -89,6 +89,8 @@ STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dThe
 
 # CopterVecEnv.step_jacobian's result (device tensors)
 StepJacobian = collections.namedtuple("StepJacobian", "dx du reward_dx reward_du branch")
+# CopterVecEnv.rollout_states' result (device tensors, [K, N, ...])
+Rollout = collections.namedtuple("Rollout", "x reward terminated truncated status")
 
 
 def _torch():
@@ -921,6 +923,140 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_step_jacobian(self._ctx, C.byref(io), self._stream()))
         self._keep = keep
         return out
+
+    def _rollout_io(self, actions, state):
+        """The cs_rollout_io of rollout_states / rollout_vjp: actions [K,N,A] and the start point; returns (io, K, the
+        tensors the call reads)."""
+        torch = _torch()
+        n, ad = self.num_envs, self.action_dim
+        shape = tuple(actions.shape) if hasattr(actions, "shape") else np.shape(actions)
+        if len(shape) != 3 or shape[0] < 1:
+            raise ValueError("actions must have shape (K, %d, %d) with K >= 1, got %s" % (n, ad, tuple(shape)))
+        K = int(shape[0])
+        a, _ = self._dev_f32(actions, (K, n, ad), "actions")
+        io = _lib.RolloutIO()
+        io.struct_size = C.sizeof(_lib.RolloutIO)
+        io.num_steps = K
+        io.actions_dev = a.data_ptr()
+        keep = [a]
+        if state is not None:
+            unknown = set(state) - {"x", "status", "force", "prev_shaping"}
+            if unknown or "x" not in state or "status" not in state:
+                raise ValueError("state needs the keys 'x' and 'status' (and optionally 'force', 'prev_shaping'), got %s"
+                                 % sorted(state))
+
+            def dev(v, shape, dt, name):
+                t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+                if tuple(t.shape) != shape:
+                    raise ValueError("state[%r] must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+                t = t.detach().to(device=self.device, dtype=dt, non_blocking=True).contiguous()
+                keep.append(t)
+                return t.data_ptr()
+            io.start_x_dev = dev(state["x"], (12, n), torch.float64, "x")
+            io.start_status_dev = dev(state["status"], (n,), torch.uint8, "status")
+            if state.get("force") is not None:
+                io.start_force_dev = dev(state["force"], (3, n), torch.float64, "force")
+            if state.get("prev_shaping") is not None:
+                io.start_prev_shaping_dev = dev(state["prev_shaping"], (n,), torch.float64, "prev_shaping")
+        return io, K, keep
+
+    def _rollout_cache(self, key, make):
+        cache = getattr(self, "_rollout_out", None)
+        if cache is None:
+            cache = self._rollout_out = {}
+        out = cache.get(key)
+        if out is None:
+            out = cache[key] = make()
+        return out
+
+    def rollout_states(self, actions, state=None):
+        """K calls of step() with auto-reset DISABLED, as a pure function: Rollout(x [K,N,12] float64, reward [K,N]
+        float64, terminated [K,N] bool, truncated [K,N] bool, status [K,N] uint8) of device tensors; NO env state
+        changes (no words, counters, episode numbers, prev_shaping, statistics or RNG position).  actions [K,N,A]: step
+        k takes actions[k-1], as step() receives them.
+
+        x[k-1] is the decoded stored state after step k in upstream slot order (STATE_NAMES_12; in the float32 storage
+        modes the words get_state() would report), reward[k-1] the value step() rounds to float32.  Both are
+        bit-identical to a twin env with autoreset_mode="disabled" stepped K times.  An observation is a slice of x
+        (STATE_NAMES).
+
+        state=None starts from the stored state the next step() starts from: its pending perturbation enters the first
+        substep of step 1, and an env with a NEXT_STEP reset pending performs that reset in step 1 with the draw step()
+        would make.  state={"x": [12,N] float64, "status": [N] uint8, "force": [3,N] newtons (optional, pending),
+        "prev_shaping": [N] float64 (optional; NaN = None: reward 0 in step 1)} -- get_state()'s layout, as
+        step_jacobian takes it -- starts from that point instead; without prev_shaping it is shaping(x0).  The step
+        counter (time-limit truncation) is the env's in both cases.  Asynchronous on the current stream; the returned
+        tensors are buffers of this env, overwritten by the next call with the same K."""
+        self._check_open()
+        torch = _torch()
+        io, K, keep = self._rollout_io(actions, state)
+        n, dev = self.num_envs, self.device
+        out = self._rollout_cache(("states", K), lambda: Rollout(
+            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
+            torch.empty((K, n), dtype=torch.float64, device=dev),
+            torch.empty((K, n), dtype=torch.bool, device=dev),
+            torch.empty((K, n), dtype=torch.bool, device=dev),
+            torch.empty((K, n), dtype=torch.uint8, device=dev)))
+        io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in out)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_states(self._ctx, C.byref(io), self._stream()))
+        self._keep = keep
+        return out
+
+    def rollout_vjp(self, actions, rollout, gx=None, gr=None, state=None, dtype=None):
+        """Reverse-mode gradient of a rollout: given the cotangents gx [K,N,12] (on rollout.x) and gr [K,N] (on
+        rollout.reward) -- either may be None (zero) -- returns (g_actions [K,N,A] = dL / d actions, the actions as
+        step() receives them (the clip's derivative is 1 on [0, 1] and 0 outside), g_x0 [12,N] = dL / d state["x"] for an
+        explicit start, None for the stored one).  `rollout` is what rollout_states(actions, state) returned for the
+        same actions and start (its x and status are the tape the backward recomputes each step from); with the stored
+        start the env must not have been stepped, reset or set since.  The derivative rules are step_jacobian's (DESIGN
+        section 9) plus the prev_shaping term: reward_k = shaping(x_k) - shaping(x_{k-1}), and without a given
+        prev_shaping the first step's differentiates shaping(x0).  The perturbation force and the vehicle are constants.
+        dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).  Asynchronous on the current
+        stream; the returned tensors are buffers of this env, overwritten by the next call with the same K and dtype."""
+        self._check_open()
+        torch = _torch()
+        dtype = torch.float64 if dtype is None else dtype
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("dtype must be torch.float64 or torch.float32")
+        io, K, keep = self._rollout_io(actions, state)
+        n, ad = self.num_envs, self.action_dim
+        io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+        x, status = getattr(rollout, "x", None), getattr(rollout, "status", None)
+        for t, name, shape, dt in ((x, "rollout.x", (K, n, 12), torch.float64),
+                                   (status, "rollout.status", (K, n), torch.uint8)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a device tensor of shape %s (rollout_states' result)" % (name, shape))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, self.device))
+        io.x_dev, io.status_dev = x.data_ptr(), status.data_ptr()
+
+        def cot(v, shape, name):
+            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if not (t.dtype.is_floating_point):
+                raise ValueError("%s must be a floating-point array" % name)
+            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+        if gx is not None:
+            io.gx_dev = cot(gx, (K, n, 12), "gx")
+        if gr is not None:
+            io.gr_dev = cot(gr, (K, n), "gr")
+        dev = self.device
+        ga = self._rollout_cache(("g_actions", K, dtype), lambda: torch.empty((K, n, ad), dtype=dtype, device=dev))
+        io.g_actions_dev = ga.data_ptr()
+        g0 = None
+        if state is not None:
+            g0 = self._rollout_cache(("g_x0", dtype), lambda: torch.empty((12, n), dtype=dtype, device=dev))
+            io.g_x0_dev = g0.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_vjp(self._ctx, C.byref(io), self._stream()))
+        self._keep = keep
+        return ga, g0
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

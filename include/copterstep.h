@@ -21,6 +21,10 @@
  *   cs_set_motors            Dynamics.setMotors (used directly) dynamics/__init__.py:114-197
  *   cs_step_jacobian         d(_Task.step)/d(state, action)     dynamics/__init__.py:114-197,249-302, envs/task.py:77-137,
  *                            and the reward gradient            envs/lander.py:46-74 (no state written)
+ *   cs_rollout_states        K x _Task.step, auto-reset off,    dynamics/__init__.py:114-197,249-302, envs/task.py:77-137,
+ *                            every state kept (no state written) envs/lander.py:46-74
+ *   cs_rollout_vjp           reverse-mode gradient of that      the same lines, differentiated
+ *                            rollout (vector-Jacobian product)
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -542,6 +546,63 @@ enum {
   CS_JAC_CLIPPED = 64     /* some motor value was outside [0, 1]: its columns are zero */
 };
 int cs_step_jacobian(cs_ctx* ctx, const cs_jacobian_io* io, void* stream);
+
+/* Differentiable K-step rollouts (dynamics/__init__.py:114-197 setMotors, :249-302 the state derivative and
+ * _bodyZToInertial; envs/task.py:77-137 step; envs/lander.py:46-74 the reward).  A rollout is the pure function "K calls
+ * of cs_step on this env with auto-reset DISABLED": NOTHING of the env state is written -- no words, counters, episode
+ * numbers, prev_shaping, statistics or RNG position.
+ *
+ * cs_rollout_states (forward): from the start point, step k = 1..K takes actions_dev[k-1] and writes
+ *   x_dev          [K,N,12] float64  the decoded stored state after step k, in upstream slot order (cs_get_state's x
+ *                                    slots; in the float32 storage modes the words cs_get_state would report)
+ *   reward_dev     [K,N]    float64  the reward before cs_step rounds it to float32
+ *   terminated_dev, truncated_dev, status_dev   [K,N] uint8 (0 / 1, 0 / 1, CS_STATUS_*)
+ * Each of them may be NULL (not written).  These are bit-identical to an env with auto-reset disabled stepped K times.
+ * Start point: start_x_dev == NULL = the stored state the next cs_step starts from: its pending perturbation enters the
+ * first call of step 1, and a lane with a NEXT_STEP reset pending performs that reset in step 1 with the draw cs_step
+ * would make (that lane's gradient with respect to x0 and the first action is zero).  Or an explicit point:
+ * start_x_dev [12,N] float64 + start_status_dev [N] (both required) + optional start_force_dev [3,N] newtons, pending,
+ * and optional start_prev_shaping_dev [N] (NaN = upstream's None: reward 0 in step 1).  Without prev_shaping it is
+ * shaping(x0), DIFFERENTIATED, so that the telescoping reward holds from step 1; a given prev_shaping is a constant.
+ * The step counter (time-limit truncation) is the env's stored one in both cases.
+ *
+ * cs_rollout_vjp (backward): given cotangents gx_dev [K,N,12] (on x) and gr_dev [K,N] (on reward), float64, either
+ * NULL = zero, writes
+ *   g_actions_dev  [K,N,A]  dL / d actions, the actions as cs_step receives them (the clip's derivative is 1 on [0, 1],
+ *                           0 outside)
+ *   g_x0_dev       [12,N]   dL / d x0 (an explicit start's x; with the stored start: the decoded words)
+ * in out_dtype (CS_JAC_F64, or CS_JAC_F32: the float64 values rounded); either may be NULL.  The tape is the forward's
+ * own output: x_dev and status_dev are READ (both required), with the same K, actions and start point; a stored start
+ * is decoded again, so the env must not have been stepped, reset or set in between.  The derivative rules are those of
+ * cs_step_jacobian (the float64 motor law's derivative also under action_arith = CS_ARITH_F32; LANDED, ground contact,
+ * CRASHED and LEVELING as there; a tilt, a prev_shaping of None and the Hover tasks give no reward gradient; the
+ * storage rounding of the float32 modes is the identity), plus the one term a single step cannot see: reward_k depends
+ * on x_{k-1} through prev_shaping.  The perturbation force and the vehicle are constants.
+ *
+ * Asynchronous on `stream`.  io->struct_size must be sizeof(cs_rollout_io) (else CS_ERR_ABI); the argument block is
+ * checked before the context. */
+typedef struct cs_rollout_io {
+  uint32_t struct_size;                /* sizeof(cs_rollout_io) */
+  uint32_t out_dtype;                  /* CS_JAC_F64 / CS_JAC_F32: g_actions_dev, g_x0_dev */
+  int32_t num_steps;                   /* K >= 1 */
+  uint32_t reserved_;                  /* 0 */
+  const float* actions_dev;            /* [K,N,A] float32, required */
+  const double* start_x_dev;           /* [12,N] explicit start, or NULL = the stored state */
+  const uint8_t* start_status_dev;     /* [N] required with start_x_dev */
+  const double* start_force_dev;       /* [3,N] newtons, optional with start_x_dev */
+  const double* start_prev_shaping_dev; /* [N], optional with start_x_dev */
+  double* x_dev;                       /* [K,N,12]: written by cs_rollout_states, read by cs_rollout_vjp */
+  double* reward_dev;                  /* [K,N] */
+  uint8_t* terminated_dev;             /* [K,N] */
+  uint8_t* truncated_dev;              /* [K,N] */
+  uint8_t* status_dev;                 /* [K,N]: written by cs_rollout_states, read by cs_rollout_vjp */
+  const double* gx_dev;                /* [K,N,12] float64 or NULL */
+  const double* gr_dev;                /* [K,N] float64 or NULL */
+  void* g_actions_dev;                 /* [K,N,A] */
+  void* g_x0_dev;                      /* [12,N] */
+} cs_rollout_io;
+int cs_rollout_states(cs_ctx* ctx, const cs_rollout_io* io, void* stream);
+int cs_rollout_vjp(cs_ctx* ctx, const cs_rollout_io* io, void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in
