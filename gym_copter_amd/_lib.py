@@ -86,6 +86,12 @@ class RolloutIO(C.Structure):
                 ("terminated_dev", C.c_void_p), ("truncated_dev", C.c_void_p), ("status_dev", C.c_void_p),
                 ("gx_dev", C.c_void_p), ("gr_dev", C.c_void_p), ("g_actions_dev", C.c_void_p),
                 ("g_x0_dev", C.c_void_p)]
+
+
+class RolloutParamIO(C.Structure):
+    """Mirror of `struct cs_rollout_param_io` (cs_rollout_states_ex / cs_rollout_vjp_ex)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("vehicle_dev", C.c_void_p),
+                ("g_vehicle_dev", C.c_void_p), ("g_force_dev", C.c_void_p)]
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
 JAC_INTEGRATED, JAC_LANDED, JAC_CONTACT, JAC_LEVELING, JAC_CRASHED, JAC_RESET, JAC_CLIPPED = 1, 2, 4, 8, 16, 32, 64
 
@@ -145,6 +151,8 @@ SYMBOLS = {
     "cs_step_jacobian": (C.c_int, [_P, C.POINTER(JacobianIO), _P]),
     "cs_rollout_states": (C.c_int, [_P, C.POINTER(RolloutIO), _P]),
     "cs_rollout_vjp": (C.c_int, [_P, C.POINTER(RolloutIO), _P]),
+    "cs_rollout_states_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutParamIO), _P]),
+    "cs_rollout_vjp_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutParamIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

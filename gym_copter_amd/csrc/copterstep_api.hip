@@ -27,6 +27,9 @@ struct cs_ctx {
   double* pid_state = nullptr;
   uint32_t pid_stride = 0;
   double* veh = nullptr;  // per-env coefficient columns (cs_set_vehicle_params), owned
+  double* veh_raw = nullptr;  // ... and the raw [12][N] table they were folded from (the parameter gradients' unfold)
+  double* veh_ovr = nullptr;  // scratch of cs_rollout_*_ex: an override's folded columns [11][stride]
+  double* veh_gcoef = nullptr;  // ... and the coefficient adjoints [11][N]
   cs::Tuning tune{};
   // the per-launch constants, derived from cfg once and again after cs_seed / cs_set_altitude
   cs::DevConst dc;
@@ -325,6 +328,28 @@ int serve_make_stream(cs_ctx* ctx) {
 namespace cs {
 int report_error(int code, const char* message) { return fail(code, message); }
 int report_hip(hipError_t e, const char* what) { return hip_fail(e, what); }
+int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, ParamView* out) {
+  const cs_config& g = ctx->cfg;
+  if (g.action_arith == CS_ARITH_F32)
+    return fail(CS_ERR_ARG, std::string(who) + ": vehicle overrides and parameter gradients are not available with the "
+                                               "float32 motor model");
+  out->lift = g.thrust_model == CS_THRUST_LIFT ? 1 : 0;
+  out->gyro = g.rotor_gyro != 0 ? 1 : 0;
+  out->n = (uint32_t)g.num_envs;
+  out->stride = ctx->st.ntiles * 64u;
+  const double u[kVehicleRows] = {g.B, g.D, g.M, g.L, g.Ix, g.Iy, g.Iz, g.Jr, g.maxrpm, g.G, g.rho, g.C_L};
+  for (int j = 0; j < kVehicleRows; ++j) out->uniform_raw[j] = u[j];
+  out->raw_dev = ctx->st.veh != nullptr ? ctx->veh_raw : nullptr;
+  DeviceGuard guard(g.device);
+  if (want_coef && ctx->veh_ovr == nullptr)
+    CS_HIP(hipMalloc((void**)&ctx->veh_ovr, (size_t)kCoefRows * out->stride * sizeof(double)));
+  if (want_gcoef && ctx->veh_gcoef == nullptr)
+    CS_HIP(hipMalloc((void**)&ctx->veh_gcoef, (size_t)kCoefRows * out->n * sizeof(double)));
+  out->coef_dev = ctx->veh_ovr;
+  out->gcoef_dev = ctx->veh_gcoef;
+  return CS_OK;
+}
+
 int enter_context(cs_ctx* ctx, const char* who, void* stream, ContextView* out) {
   if (int rc_ = check_idle(ctx, who, stream, true)) return rc_;
   out->task = ctx->cfg.task;
@@ -519,6 +544,9 @@ int cs_destroy(cs_ctx* ctx) {
   if (ctx->st.tiles) (void)hipFree(ctx->st.tiles);
   if (ctx->pid_state) (void)hipFree(ctx->pid_state);
   if (ctx->veh) (void)hipFree(ctx->veh);
+  if (ctx->veh_raw) (void)hipFree(ctx->veh_raw);
+  if (ctx->veh_ovr) (void)hipFree(ctx->veh_ovr);
+  if (ctx->veh_gcoef) (void)hipFree(ctx->veh_gcoef);
   if (ctx->serve_fork) (void)hipEventDestroy(ctx->serve_fork);
   if (ctx->serve_join) (void)hipEventDestroy(ctx->serve_join);
   if (ctx->serve_mem) (void)hipFree(ctx->serve_mem);
@@ -695,6 +723,10 @@ int cs_set_vehicle_params(cs_ctx* ctx, const double* params_host) {
   }
   if (ctx->veh == nullptr) CS_HIP(hipMalloc((void**)&ctx->veh, cols.size() * sizeof(double)));
   CS_HIP(hipMemcpy(ctx->veh, cols.data(), cols.size() * sizeof(double), hipMemcpyHostToDevice));
+  // the raw table too: the parameter gradients of cs_rollout_vjp_ex chain through the fold at these values
+  const size_t raw_bytes = (size_t)cs::kVehicleRows * n * sizeof(double);
+  if (ctx->veh_raw == nullptr) CS_HIP(hipMalloc((void**)&ctx->veh_raw, raw_bytes));
+  CS_HIP(hipMemcpy(ctx->veh_raw, params_host, raw_bytes, hipMemcpyHostToDevice));
   ctx->st.veh = ctx->veh;
   ctx->st.veh_stride = stride;
   return CS_OK;

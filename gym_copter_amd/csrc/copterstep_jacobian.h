@@ -18,4 +18,20 @@ int enter_context(cs_ctx* ctx, const char* who, void* stream, ContextView* out);
 int report_error(int code, const char* message);
 int report_hip(hipError_t e, const char* what);
 
+constexpr int kVehicleRows = 12;  // cs_set_vehicle_params' raw rows: B, D, M, L, Ix, Iy, Iz, Jr, maxrpm, G, rho, C_L
+
+// what cs_rollout_states_ex / cs_rollout_vjp_ex need beyond ContextView: the configuration's motor
+// law, the vehicle's raw parameters and the context's scratch tables
+struct ParamView {
+  int lift, gyro;
+  uint32_t n, stride;                 // envs, the padded stride of DevState::veh
+  double uniform_raw[kVehicleRows];   // cs_config's vehicle and world, in cs_set_vehicle_params' row order
+  const double* raw_dev;              // [kVehicleRows][n] the installed per-env table, nullptr = uniform
+  double* coef_dev;                   // [kCoefRows][stride] an override's folded columns (allocated on first use)
+  double* gcoef_dev;                  // [kCoefRows][n] the coefficient adjoints (allocated on first use)
+};
+// (copterstep_api.hip) refuse the float32 motor law and describe the context; allocates the scratch tables asked for
+// (outside stream order: the first call with an override or a parameter gradient allocates)
+int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, ParamView* out);
+
 }  // namespace cs

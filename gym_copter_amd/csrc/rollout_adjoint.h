@@ -14,12 +14,21 @@
 namespace cs {
 namespace {
 
+// The lane's accumulators of the coefficient adjoints (PARAM builds): row j of Coef at acc[j * kBlock], in the LDS
+// (copterstep_rollout_grad.hip: rollout_vjp_param_kernel); rows kAccPe .. kAccPe + 2 hold the perturbation's adjoint
+constexpr int kAccPe = kCoefRows;
+constexpr int kAccRows = kCoefRows + 3;
+
 // The adjoint of one integrating Dynamics.setMotors() (forward Euler x' = x + dt f(x, w), euler_tangent): on entry `l`
 // is the adjoint of the state AFTER the call, on exit that of the state BEFORE it (x, with t its sin / cos); the
-// adjoint of the call's wrench is added to `mw`.  The perturbation is a constant: it has no adjoint.
-template <bool GYRO>
+// adjoint of the call's wrench is added to `mw`.  The perturbation's adjoint (dt times the velocity adjoints on entry) is
+// taken by the caller, in the call where it enters.  PARAM (cs_rollout_vjp_ex): the adjoints of
+// the per-call coefficients G, c_d*, g_* are added to the lane's LDS accumulators `acc` as well -- the transposes of
+// where euler_rotation and thrust_ned multiply by them.
+template <bool GYRO, bool PARAM = false>
 __device__ __forceinline__ void euler_adjoint(const Coef& q, const Wrench& w, const Trig& t, const double (&x)[12],
-                                              double dt, bool leveling, double (&l)[12], Wrench& mw) {
+                                              double dt, bool leveling, double (&l)[12], Wrench& mw,
+                                              double* acc = nullptr) {
   const double sph = t.sph, cph = t.cph, sth = t.sth, cth = t.cth, sps = t.sps, cps = t.cps;
   const double Rx = cph * cps * sth + sph * sps;  // ax / bz
   const double Ry = cph * sps * sth - cps * sph;  // ay / bz
@@ -44,6 +53,16 @@ __device__ __forceinline__ void euler_adjoint(const Coef& q, const Wrench& w, co
     n7 += q.g_the * w.om * f9;
     n9 -= q.g_phi * w.om * f7;
     mw.om += q.g_the * p * f9 - q.g_phi * th * f7;
+  }
+  if constexpr (PARAM) {  // netz = bz Rz + G; d7 = c_dphi ps th + ..., d9s = c_dthe ps p + ..., d11 = c_dpsi th p + ...
+    acc[4 * kBlock] += e5;
+    acc[5 * kBlock] += (ps * th) * f7;
+    acc[6 * kBlock] += (ps * p) * f9;
+    acc[7 * kBlock] += (th * p) * f11;
+    if constexpr (GYRO) {
+      acc[9 * kBlock] -= (th * w.om) * f7;
+      acc[10 * kBlock] += (p * w.om) * f9;
+    }
   }
   l[1] += dt * l[0];
   l[3] += dt * l[2];

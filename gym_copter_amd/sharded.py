@@ -195,15 +195,21 @@ class ShardedCopterVecEnv:
         raise ValueError("actions must have %d (local) or %d (global) envs in dimension 1, got %d"
                          % (self.n_local, self.total_envs, actions.shape[1]))
 
-    def rollout_states(self, actions, state=None):
-        """CopterVecEnv.rollout_states of this rank's envs: shard-local, no gather (actions: [K, n_local, A] or the
-        global [K, N, A]; an explicit `state` covers the local envs)."""
-        return self.local.rollout_states(self._local_rollout_actions(actions), state=state)
-
     def rollout_vjp(self, actions, rollout, gx=None, gr=None, state=None, dtype=None):
         """CopterVecEnv.rollout_vjp of this rank's envs: shard-local (rollout, gx, gr: the local envs')."""
         return self.local.rollout_vjp(self._local_rollout_actions(actions), rollout, gx=gx, gr=gr, state=state,
                                       dtype=dtype)
+
+    def rollout_states(self, actions, state=None, vehicle=None):
+        """CopterVecEnv.rollout_states of this rank's envs: shard-local, no gather (actions: [K, n_local, A] or the
+        global [K, N, A]; an explicit `state` and a `vehicle` override cover the local envs)."""
+        return self.local.rollout_states(self._local_rollout_actions(actions), state=state, vehicle=vehicle)
+
+    def rollout_vjp_params(self, actions, rollout, gx=None, gr=None, state=None, vehicle=None, dtype=None):
+        """CopterVecEnv.rollout_vjp_params of this rank's envs: shard-local (rollout, gx, gr, vehicle: the local envs');
+        g_vehicle is per local env -- a vehicle shared by every rank sums it over envs and ranks."""
+        return self.local.rollout_vjp_params(self._local_rollout_actions(actions), rollout, gx=gx, gr=gr, state=state,
+                                             vehicle=vehicle, dtype=dtype)
 
     def close(self):
         self.local.close()

@@ -969,7 +969,33 @@ class CopterVecEnv(_VectorEnvBase):
             out = cache[key] = make()
         return out
 
-    def rollout_states(self, actions, state=None):
+    def _param_io(self, vehicle, keep, dtype=None, check=True):
+        """The cs_rollout_param_io of a rollout with a vehicle override and / or parameter gradients: vehicle [12,N]
+        float64 (set_vehicle_params' rows) is checked on the device -- M, Ix, Iy, Iz positive, every value finite; a
+        synchronising reduction, skipped with check=False for a tensor already checked -- and kept alive in `keep`."""
+        torch = _torch()
+        pio = _lib.RolloutParamIO()
+        pio.struct_size = C.sizeof(_lib.RolloutParamIO)
+        pio.out_dtype = _lib.JAC_F32 if dtype == torch.float32 else _lib.JAC_F64
+        if vehicle is not None:
+            n = self.num_envs
+            t = vehicle if isinstance(vehicle, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(vehicle)))
+            rows = len(self.VEHICLE_ROWS)
+            if tuple(t.shape) != (rows, n):
+                raise ValueError("vehicle must have shape (%d, %d) (rows %s), got %s"
+                                 % (rows, n, self.VEHICLE_ROWS, tuple(t.shape)))
+            if not t.dtype.is_floating_point:
+                raise ValueError("vehicle must be a floating-point array")
+            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
+            # the C ABI cannot check a device table synchronously: one reduction here (M, Ix, Iy, Iz are rows 2, 4, 5, 6)
+            inertia = t[[2, 4, 5, 6]]
+            if check and not bool(torch.isfinite(t).all() & (inertia > 0).all()):
+                raise ValueError("vehicle: M, Ix, Iy, Iz must be positive and every value finite")
+            keep.append(t)
+            pio.vehicle_dev = t.data_ptr()
+        return pio
+
+    def rollout_states(self, actions, state=None, vehicle=None):
         """K calls of step() with auto-reset DISABLED, as a pure function: Rollout(x [K,N,12] float64, reward [K,N]
         float64, terminated [K,N] bool, truncated [K,N] bool, status [K,N] uint8) of device tensors; NO env state
         changes (no words, counters, episode numbers, prev_shaping, statistics or RNG position).  actions [K,N,A]: step
@@ -985,11 +1011,15 @@ class CopterVecEnv(_VectorEnvBase):
         would make.  state={"x": [12,N] float64, "status": [N] uint8, "force": [3,N] newtons (optional, pending),
         "prev_shaping": [N] float64 (optional; NaN = None: reward 0 in step 1)} -- get_state()'s layout, as
         step_jacobian takes it -- starts from that point instead; without prev_shaping it is shaping(x0).  The step
-        counter (time-limit truncation) is the env's in both cases.  Asynchronous on the current stream; the returned
-        tensors are buffers of this env, overwritten by the next call with the same K."""
+        counter (time-limit truncation) is the env's in both cases.  vehicle=[12,N] float64 (set_vehicle_params' rows
+        VEHICLE_ROWS) rolls out with that vehicle instead of the env's, for this call only: the env's installed vehicle
+        is untouched.  Asynchronous on the current stream (an override is checked with one device
+        reduction, which synchronises); the returned tensors are buffers of this env, overwritten by the next call with
+        the same K."""
         self._check_open()
         torch = _torch()
         io, K, keep = self._rollout_io(actions, state)
+        pio = None if vehicle is None else self._param_io(vehicle, keep)
         n, dev = self.num_envs, self.device
         out = self._rollout_cache(("states", K), lambda: Rollout(
             torch.empty((K, n, 12), dtype=torch.float64, device=dev),
@@ -999,9 +1029,25 @@ class CopterVecEnv(_VectorEnvBase):
             torch.empty((K, n), dtype=torch.uint8, device=dev)))
         io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in out)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_states(self._ctx, C.byref(io), self._stream()))
+            if pio is None:
+                _lib.check(self._lib.cs_rollout_states(self._ctx, C.byref(io), self._stream()))
+            else:
+                _lib.check(self._lib.cs_rollout_states_ex(self._ctx, C.byref(io), C.byref(pio), self._stream()))
         self._keep = keep
         return out
+
+    def rollout_vjp_params(self, actions, rollout, gx=None, gr=None, state=None, vehicle=None, dtype=None):
+        """rollout_vjp with the gradients with respect to the vehicle and the start's pending force as well: returns
+        (g_actions [K,N,A], g_x0 [12,N] or None, g_vehicle [12,N], g_force [3,N]).  g_vehicle = dL / d the vehicle
+        rows (VEHICLE_ROWS, per env: sum over envs for a shared vehicle; rows that do not enter the configuration are
+        0: B under the lift law, rho and C_L under the B law, Jr without rotor_gyro).  g_force = dL / d state["force"]
+        (newtons), or with the stored start dL / d its pending perturbation; exactly 0 where none is pending (consumed,
+        or a state without "force": pass zeros for the sensitivity at F = 0), where it never integrates, and for an env
+        whose NEXT_STEP reset is pending (the new episode's draw is a constant).  `vehicle`
+        is the override rollout_states(..., vehicle=) was given (None: the env's own).  g_actions and g_x0 are
+        rollout_vjp's, bit for bit.  DESIGN section 11.  Same buffers and stream rules as rollout_vjp; not available
+        with action_arith="float32"."""
+        return self._vjp(actions, rollout, gx, gr, state, dtype, params=True, vehicle=vehicle)
 
     def rollout_vjp(self, actions, rollout, gx=None, gr=None, state=None, dtype=None):
         """Reverse-mode gradient of a rollout: given the cotangents gx [K,N,12] (on rollout.x) and gr [K,N] (on
@@ -1013,7 +1059,11 @@ class CopterVecEnv(_VectorEnvBase):
         section 9) plus the prev_shaping term: reward_k = shaping(x_k) - shaping(x_{k-1}), and without a given
         prev_shaping the first step's differentiates shaping(x0).  The perturbation force and the vehicle are constants.
         dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).  Asynchronous on the current
-        stream; the returned tensors are buffers of this env, overwritten by the next call with the same K and dtype."""
+        stream; the returned tensors are buffers of this env, overwritten by the next call with the same K and dtype.
+        rollout_vjp_params differentiates with respect to the vehicle and the force as well."""
+        return self._vjp(actions, rollout, gx, gr, state, dtype)
+
+    def _vjp(self, actions, rollout, gx, gr, state, dtype, params=False, vehicle=None, check_vehicle=True):
         self._check_open()
         torch = _torch()
         dtype = torch.float64 if dtype is None else dtype
@@ -1053,10 +1103,20 @@ class CopterVecEnv(_VectorEnvBase):
         if state is not None:
             g0 = self._rollout_cache(("g_x0", dtype), lambda: torch.empty((12, n), dtype=dtype, device=dev))
             io.g_x0_dev = g0.data_ptr()
+        if not params:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.cs_rollout_vjp(self._ctx, C.byref(io), self._stream()))
+            self._keep = keep
+            return ga, g0
+        pio = self._param_io(vehicle, keep, dtype, check=check_vehicle)
+        gv = self._rollout_cache(("g_vehicle", dtype), lambda: torch.empty((len(self.VEHICLE_ROWS), n), dtype=dtype,
+                                                                           device=dev))
+        gf = self._rollout_cache(("g_force", dtype), lambda: torch.empty((3, n), dtype=dtype, device=dev))
+        pio.g_vehicle_dev, pio.g_force_dev = gv.data_ptr(), gf.data_ptr()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_vjp(self._ctx, C.byref(io), self._stream()))
+            _lib.check(self._lib.cs_rollout_vjp_ex(self._ctx, C.byref(io), C.byref(pio), self._stream()))
         self._keep = keep
-        return ga, g0
+        return ga, g0, gv, gf
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

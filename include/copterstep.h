@@ -25,6 +25,8 @@
  *                            every state kept (no state written) envs/lander.py:46-74
  *   cs_rollout_vjp           reverse-mode gradient of that      the same lines, differentiated
  *                            rollout (vector-Jacobian product)
+ *   cs_rollout_*_ex          the same with a vehicle override    + the vehicle_params dict (vehicles/dji_phantom.py:9-26)
+ *                            and gradients w.r.t. vehicle, force
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -577,7 +579,8 @@ int cs_step_jacobian(cs_ctx* ctx, const cs_jacobian_io* io, void* stream);
  * cs_step_jacobian (the float64 motor law's derivative also under action_arith = CS_ARITH_F32; LANDED, ground contact,
  * CRASHED and LEVELING as there; a tilt, a prev_shaping of None and the Hover tasks give no reward gradient; the
  * storage rounding of the float32 modes is the identity), plus the one term a single step cannot see: reward_k depends
- * on x_{k-1} through prev_shaping.  The perturbation force and the vehicle are constants.
+ * on x_{k-1} through prev_shaping.  The perturbation force and the vehicle are constants here; cs_rollout_vjp_ex
+ * (below) differentiates with respect to them as well.
  *
  * Asynchronous on `stream`.  io->struct_size must be sizeof(cs_rollout_io) (else CS_ERR_ABI); the argument block is
  * checked before the context. */
@@ -603,6 +606,40 @@ typedef struct cs_rollout_io {
 } cs_rollout_io;
 int cs_rollout_states(cs_ctx* ctx, const cs_rollout_io* io, void* stream);
 int cs_rollout_vjp(cs_ctx* ctx, const cs_rollout_io* io, void* stream);
+
+/* Rollouts as functions of the vehicle and of the start's pending force: system identification,
+ * disturbance estimation, sensitivity to the vehicle.  cs_rollout_states_ex / cs_rollout_vjp_ex take cs_rollout_io as
+ * cs_rollout_states / cs_rollout_vjp do, plus
+ *   vehicle_dev    [12,N] float64, cs_set_vehicle_params' rows (B, D, M, L, Ix, Iy, Iz, Jr, maxrpm, G, rho, C_L), or
+ *                  NULL = the env's own vehicle (its per-env table, else cs_config's).  A table given here is folded on
+ *                  the device into a scratch table of the context, bit for bit as cs_set_vehicle_params folds it, and is
+ *                  used by THIS call only: the env's installed vehicle is untouched and the rollout stays a pure
+ *                  function.  It cannot be checked synchronously: the caller guarantees M, Ix, Iy, Iz > 0 and every
+ *                  value finite (cs_set_vehicle_params' contract; gym_copter_amd checks it with a device reduction).  A
+ *                  cs_rollout_vjp_ex must be given the same vehicle as the cs_rollout_states_ex that made its tape.
+ *   g_vehicle_dev  [12,N] dL / d vehicle, per env (callers sum over envs for a shared vehicle); rows that do not enter
+ *                  the configuration are 0: B under CS_THRUST_LIFT, rho and C_L under CS_THRUST_B, Jr without
+ *                  rotor_gyro.  Written by cs_rollout_vjp_ex; NULL = not wanted.
+ *   g_force_dev    [3,N] dL / d the start's pending force, newtons (an explicit start's start_force_dev, or the stored
+ *                  start's pending perturbation).  Exactly 0 where no perturbation is pending (the stored start's was
+ *                  consumed, or an explicit start has no start_force_dev: pass a zero start_force_dev for the
+ *                  sensitivity at F = 0), where it never integrates (kept pending by a ground-contact freeze), and for
+ *                  a lane with a NEXT_STEP reset pending: the new episode's draw is a constant (the steps after that
+ *                  reset still contribute to g_vehicle).  Written by cs_rollout_vjp_ex; NULL = not wanted.
+ * g_vehicle_dev and g_force_dev are in out_dtype (CS_JAC_F64 or CS_JAC_F32); cs_rollout_states_ex reads vehicle_dev
+ * only.  The storage rounding is the identity, as in cs_rollout_vjp.  With pio == NULL both calls are exactly
+ * cs_rollout_states / cs_rollout_vjp.  Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32.  The first call with a
+ * vehicle_dev or a gradient allocates the context's scratch tables (call it outside graph capture); calls on one context
+ * that use them must be ordered on one stream. */
+typedef struct cs_rollout_param_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_param_io) */
+  uint32_t out_dtype;          /* CS_JAC_F64 / CS_JAC_F32: g_vehicle_dev, g_force_dev */
+  const double* vehicle_dev;   /* [12,N] float64 raw vehicle for this call, or NULL */
+  void* g_vehicle_dev;         /* [12,N] */
+  void* g_force_dev;           /* [3,N] newtons */
+} cs_rollout_param_io;
+int cs_rollout_states_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_param_io* pio, void* stream);
+int cs_rollout_vjp_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_param_io* pio, void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in
