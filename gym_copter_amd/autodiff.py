@@ -1,11 +1,13 @@
 """torch.autograd over K-step rollouts: differentiable_rollout(env, actions, state) is CopterVecEnv.rollout_states
 as a differentiable function of the actions (and of an explicit start's x, and optionally of the vehicle and the start's
-pending force), its backward CopterVecEnv.rollout_vjp (rollout_vjp_params).  See DESIGN.md sections 10 and 11 and
-INTEGRATION.md."""
-from .vecenv import Rollout, _torch
+pending force), its backward CopterVecEnv.rollout_vjp (rollout_vjp_params); differentiable_mlp_rollout(env, params, K,
+hidden) is the closed-loop CopterVecEnv.rollout_mlp_states under an MLP policy, its backward rollout_mlp_vjp.  See
+DESIGN.md sections 10 to 12 and INTEGRATION.md."""
+from .vecenv import MlpRollout, Rollout, _torch
 
 _FN = None
 _FN_PARAMS = None
+_FN_MLP = None
 
 
 def _function():
@@ -113,3 +115,68 @@ def differentiable_rollout(env, actions, state=None, vehicle=None):
     else:
         out = _function_params().apply(actions, x0, vehicle, force, env, state)
     return Rollout(*out)
+
+
+def _function_mlp():
+    global _FN_MLP
+    if _FN_MLP is not None:
+        return _FN_MLP
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class MlpRolloutFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, params, offsets, x0, env, num_steps, hidden, state):
+            r = env.rollout_mlp_states(params, num_steps, hidden, offsets=offsets, state=state)
+            out = tuple(t.clone() for t in r)                   # (the env's buffers are overwritten by its next call)
+            x, reward, term, trunc, status, obs, actions = out
+            ctx.mark_non_differentiable(term, trunc, status, obs, actions)
+            # (params is saved, not kept as an attribute: autograd refuses a backward after an in-place change of it)
+            ctx.save_for_backward(params, x, status, obs, actions)
+            ctx.env, ctx.state, ctx.hidden = env, state, hidden
+            ctx.want = (offsets is not None, x0 is not None)
+            return out
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, gx, gr, *_):
+            params, x, status, obs, actions = ctx.saved_tensors
+            gp, ga, g0 = ctx.env.rollout_mlp_vjp(params, MlpRollout(x, None, None, None, status, obs, actions), gx=gx,
+                                                 gr=gr, state=ctx.state, hidden=ctx.hidden, dtype=torch.float64)
+            want_u, want_x0 = ctx.want
+            return (gp.to(params.dtype), ga.to(torch.float32) if want_u else None,
+                    g0.clone() if (want_x0 and g0 is not None) else None, None, None, None, None)
+
+    _FN_MLP = MlpRolloutFunction
+    return _FN_MLP
+
+
+def differentiable_mlp_rollout(env, params, num_steps, hidden, offsets=None, state=None):
+    """K = num_steps closed-loop steps of `env` under the MLP policy `params` (CopterVecEnv.rollout_mlp_states: step k
+    takes a_k = float32(pi(o_{k-1}) + offsets[k-1]), auto-reset disabled), differentiable: returns an MlpRollout whose
+    x [K,N,12] float64 and reward [K,N] float64 carry gradients, and whose terminated / truncated / status and the obs /
+    actions tapes do not.  `params` ([P] float32 device tensor, gym_copter_amd.mlp's layout) receives dL / d params,
+    `offsets` ([K,N,A] float32, optional) dL / d offsets, an explicit start's state["x"] ([12,N] float64, when it
+    requires grad) dL / d x0 -- all through one backward kernel (CopterVecEnv.rollout_mlp_vjp) and one torch reduction
+    for the parameters.  The outputs are copies; an in-place change of params between the forward and the backward is
+    refused, and a double backward raises (once differentiable).  With the stored start the env must not step between
+    the forward and the backward.  A loss on the action tape is not differentiated (it is an output without gradient):
+    penalise the motors through x."""
+    torch = _torch()
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.dim() != 1:
+        raise ValueError("params must be a 1-D float32 torch tensor (gym_copter_amd.mlp)")
+    if params.device != env.device:
+        raise ValueError("params must be on %s, got %s" % (env.device, params.device))
+    if offsets is not None:
+        if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.float32:
+            raise ValueError("offsets must be a float32 torch tensor of shape (%d, %d, %d)"
+                             % (num_steps, env.num_envs, env.action_dim))
+        if offsets.device != env.device:
+            raise ValueError("offsets must be on %s, got %s" % (env.device, offsets.device))
+    x0 = None
+    if state is not None and isinstance(state.get("x"), torch.Tensor) and state["x"].requires_grad:
+        if state["x"].dtype != torch.float64:
+            raise ValueError("state['x'] must be float64 to receive a gradient, got %s" % state["x"].dtype)
+        x0 = state["x"]
+    out = _function_mlp().apply(params, offsets, x0, env, num_steps, hidden, state)
+    return MlpRollout(*out)

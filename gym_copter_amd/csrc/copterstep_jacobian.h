@@ -18,6 +18,10 @@ int enter_context(cs_ctx* ctx, const char* who, void* stream, ContextView* out);
 int report_error(int code, const char* message);
 int report_hip(hipError_t e, const char* what);
 
+// (copterstep_rollout_grad.hip) the cs_rollout_io checks of cs_rollout_states / cs_rollout_vjp (vjp: the backward's),
+// made before the context; also those of cs_rollout_mlp_* (copterstep_rollout_mlp.hip)
+int check_rollout_io(const cs_rollout_io* io, const char* who, bool vjp);
+
 constexpr int kVehicleRows = 12;  // cs_set_vehicle_params' raw rows: B, D, M, L, Ix, Iy, Iz, Jr, maxrpm, G, rho, C_L
 
 // what cs_rollout_states_ex / cs_rollout_vjp_ex need beyond ContextView: the configuration's motor

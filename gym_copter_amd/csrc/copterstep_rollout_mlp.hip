@@ -1,0 +1,468 @@
+// copterstep_rollout_mlp.hip -- differentiable CLOSED-LOOP rollouts under a fused MLP policy on gfx950
+// (cs_rollout_mlp_states / cs_rollout_mlp_vjp, include/copterstep.h): K steps with auto-reset disabled in which step k
+// takes a_k = fl32(pi_theta(o_{k-1}) + u_k), and the reverse-mode gradient of a loss on them with respect to u, the
+// explicit start and (through the action tape, host side) theta.  Nothing of the env state is written.
+//
+// The loop replaced: lander.py:40-65 with a policy in place of the random action -- observe, act, step -- run K times
+// and differentiated (analytic policy gradients).  Upstream lines differentiated: those of copterstep_rollout_grad.hip.
+//
+// One lane per env on the tile layout of the step kernels, as copterstep_rollout_grad.hip.  The policy's weights are
+// wave-uniform: they are read through the scalar unit (constant address space), streamed one hidden unit at a time, so a
+// lane holds O(OBS + A) policy values whatever the width.  The forward is rollout_states_kernel with the policy in front
+// of each rollout_step; the backward is rollout_vjp_kernel's sweep with the policy's vector-Jacobian product after each
+// step_adjoint: lambda_o += J_o pi^T g_a, recomputed in float64 from the tape row already in registers.  DESIGN.md
+// section 12.
+#include <string>
+
+#include "copterstep_jacobian.h"
+
+// the primal must round as the step kernels do (copterstep_kernels.hip), and the policy's float32 arithmetic is the
+// explicit fmaf chain below, whatever the compiler would contract
+#pragma clang fp contract(off)
+
+#include "dev_tile.h"
+#include "dev_codec.h"
+#include "dev_math.h"
+#include "dev_physics.h"
+#include "dev_task.h"
+#include "jacobian_tangents.h"
+#include "rollout_adjoint.h"
+#include "rollout_step.h"
+
+namespace cs {
+namespace {
+
+// what the kernels take of cs_rollout_mlp_io
+struct MlpArgs {
+  const float* params;   // [P] float32, the layout of include/copterstep.h
+  const float* offsets;  // [K,N,A] u, or nullptr
+  float* actions;        // [K,N,A] the action tape
+  float* obs;            // [K,N,OBS] the observation tape, or nullptr
+  int hidden;            // 0 .. CS_MLP_MAX_HIDDEN
+};
+
+// A weight: the address is wave-uniform, and the constant address space lets the compiler fetch it with a scalar load
+// (the params are never written by these kernels).
+typedef __attribute__((address_space(4))) const float ConstF32;
+__device__ __forceinline__ float weight(const float* p, int idx) { return ((ConstF32*)p)[idx]; }
+
+// pi_theta(o) in float32, the arithmetic include/copterstep.h documents: every sum an fmaf chain that starts from the
+// bias and adds the terms in index order; tanhf the device library's.  Streams over the hidden units (pre_j -> h_j ->
+// a[0..A) += W2[., j] h_j).
+template <int OBS, int A>
+__device__ __forceinline__ void mlp_forward(const float* P, int H, const float (&o)[OBS], float (&a)[A]) {
+  if (H == 0) {  // [W (A x OBS), b (A)]
+#pragma unroll
+    for (int c = 0; c < A; ++c) {
+      float s = weight(P, A * OBS + c);
+#pragma unroll
+      for (int j = 0; j < OBS; ++j) s = fmaf(weight(P, c * OBS + j), o[j], s);
+      a[c] = s;
+    }
+    return;
+  }
+  const int b1 = H * OBS, w2 = b1 + H, b2 = w2 + A * H;  // [W1 (H x OBS), b1 (H), W2 (A x H), b2 (A)]
+#pragma unroll
+  for (int c = 0; c < A; ++c) a[c] = weight(P, b2 + c);
+#pragma clang loop unroll(disable)
+  for (int h = 0; h < H; ++h) {
+    float pre = weight(P, b1 + h);
+#pragma unroll
+    for (int j = 0; j < OBS; ++j) pre = fmaf(weight(P, h * OBS + j), o[j], pre);
+    const float t = tanhf(pre);
+#pragma unroll
+    for (int c = 0; c < A; ++c) a[c] = fmaf(weight(P, w2 + c * H + h), t, a[c]);
+  }
+}
+
+// lam[FIRST + j] += (J_o pi(o)^T ga)_j in float64: o = the float32 observation of x (its rounding straight-through), the
+// hidden units recomputed in float64 (tanh' = 1 - h^2).  Streams over the hidden units as mlp_forward does.
+template <int TASK>
+__device__ __forceinline__ void mlp_vjp(const float* P, int H, const double (&x)[12], const double (&ga)[4],
+                                        double (&lam)[12]) {
+  constexpr int OBS = task_obs_dim(TASK), FIRST = task_obs_first(TASK), A = task_act_dim(TASK);
+  double o[OBS];
+#pragma unroll
+  for (int j = 0; j < OBS; ++j) o[j] = (double)(float)x[FIRST + j];
+  if (H == 0) {
+#pragma unroll
+    for (int c = 0; c < A; ++c) {
+#pragma unroll
+      for (int j = 0; j < OBS; ++j) lam[FIRST + j] = fma((double)weight(P, c * OBS + j), ga[c], lam[FIRST + j]);
+    }
+    return;
+  }
+  const int b1 = H * OBS, w2 = b1 + H;
+#pragma clang loop unroll(disable)
+  for (int h = 0; h < H; ++h) {
+    double pre = (double)weight(P, b1 + h);
+#pragma unroll
+    for (int j = 0; j < OBS; ++j) pre = fma((double)weight(P, h * OBS + j), o[j], pre);
+    const double t = tanh(pre);
+    double gh = 0.0;
+#pragma unroll
+    for (int c = 0; c < A; ++c) gh = fma((double)weight(P, w2 + c * H + h), ga[c], gh);
+    const double gp = gh * (1.0 - t * t);
+#pragma unroll
+    for (int j = 0; j < OBS; ++j) lam[FIRST + j] = fma(gp, (double)weight(P, h * OBS + j), lam[FIRST + j]);
+  }
+}
+
+// One float32 row of W values per lane, [.., N, W] at row `row` (64-bit): a whole wavefront's 64 rows are contiguous
+// and go out through the LDS as 16 B stores (64 W floats = 16 W float4), a partial one lane by lane.
+template <int W>
+__device__ __forceinline__ void store_row_f32(float* lds, float* base, size_t row, uint32_t env0, uint32_t i, int lane,
+                                              bool whole, bool valid, const float (&v)[W]) {
+  if (whole) {
+#pragma unroll
+    for (int j = 0; j < W; ++j) lds[lane * W + j] = v[j];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float4* src = reinterpret_cast<const float4*>(lds);
+    float4* dst = reinterpret_cast<float4*>(base + (row + env0) * W);
+#pragma unroll
+    for (int v4 = 0; v4 < (16 * W + kWave - 1) / kWave; ++v4) {
+      const int e = v4 * kWave + lane;
+      if ((16 * W) % kWave == 0 || e < 16 * W) dst[e] = src[e];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  } else if (valid) {
+    float* dst = base + (row + i) * W;
+#pragma unroll
+    for (int j = 0; j < W; ++j) dst[j] = v[j];
+  }
+}
+
+// the action as rollout_step takes it (load_action_at's fan-out of the task's A columns onto the four motors)
+template <int A>
+__device__ __forceinline__ float4 motors_of(const float (&a)[A]) {
+  if constexpr (A == 4) return make_float4(a[0], a[1], a[2], a[3]);
+  else if constexpr (A == 2) return make_float4(a[0], a[1], a[1], a[0]);
+  else return make_float4(a[0], a[0], a[0], a[0]);
+}
+
+template <int TASK, int MODE>
+__global__ __launch_bounds__(kBlock) void rollout_mlp_states_kernel(const DevConst c, const DevState s,
+                                                                    const cs_rollout_io io, const MlpArgs m) {
+  constexpr int A = task_act_dim(TASK), OBS = task_obs_dim(TASK), FIRST = task_obs_first(TASK);
+  __shared__ __attribute__((aligned(16))) double xrow[kBlock * 12];  // 6 KiB: the wavefront's state rows of a step
+  __shared__ __attribute__((aligned(16))) float orow[kBlock * OBS];  // its observation rows
+  __shared__ __attribute__((aligned(16))) float arow[kBlock * A];    // its action rows
+  const int lane = threadIdx.x;
+  const uint32_t tile_index = blockIdx.x;
+  const uint32_t i = tile_index * kBlock + threadIdx.x;
+  const uint32_t n = s.n;
+  const uint32_t env0 = i - lane;
+  const bool valid = i < n;
+  const bool whole = env0 + (uint32_t)kWave <= n;
+
+  Coef q = uniform_coef(c);
+  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, valid ? i : 0u);
+  using TILE = TileIO<MODE>;
+  const TILE tile(s, tile_index, lane);
+  Env<MODE> e;
+  unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
+  resolve_episode<MODE>(c, tile, e);
+  double px, py, pz;
+  if (io.start_x_dev != nullptr) {
+    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
+    e.reset_pending = false;
+  } else {
+    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+  }
+
+  const float* u_lane = m.offsets != nullptr ? m.offsets + (size_t)(valid ? i : 0u) * A : nullptr;
+  const size_t act_step = (size_t)n * A;
+#pragma clang loop unroll(disable)
+  for (int k = 0; k < io.num_steps; ++k) {
+    const size_t row = (size_t)k * n;  // 64-bit: K x N x 12 doubles pass 4 GiB at 1 M envs
+    // ---- the policy: o_{k-1} = what step() returned for the state before this step ----
+    float o[OBS], a[A];
+#pragma unroll
+    for (int j = 0; j < OBS; ++j) o[j] = (float)e.x[FIRST + j];
+    mlp_forward<OBS, A>(m.params, m.hidden, o, a);
+    if (u_lane != nullptr) {
+      const float4 u = load_action_at<TASK>(u_lane);
+      u_lane += act_step;
+      const float uu[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+      for (int j = 0; j < A; ++j) a[j] = a[j] + uu[j];
+    }
+    if (m.obs != nullptr) store_row_f32<OBS>(orow, m.obs, row, env0, i, lane, whole, valid, o);
+    store_row_f32<A>(arow, m.actions, row, env0, i, lane, whole, valid, a);
+
+    const bool resetting = e.reset_pending;
+    double reward;
+    bool term, trunc;
+    rollout_step<TASK, MODE>(c, q, e, motors_of<A>(a), px, py, pz, reward, term, trunc);
+    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
+      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+    } else if (!e.pend) {
+      px = py = pz = -0.0;
+    }
+
+    if (io.x_dev != nullptr) {
+      if (whole) {  // 64 rows of 96 B through the LDS: six 1 KiB stores of 16 B per lane
+#pragma unroll
+        for (int j = 0; j < 12; j += 2)
+          *reinterpret_cast<double2*>(xrow + lane * 12 + j) = make_double2(e.x[j], e.x[j + 1]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const double2* src = reinterpret_cast<const double2*>(xrow);
+        double2* dst = reinterpret_cast<double2*>(io.x_dev + (row + env0) * 12);
+#pragma unroll
+        for (int v = 0; v < 6; ++v) dst[v * kWave + lane] = src[v * kWave + lane];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      } else if (valid) {
+        double* dst = io.x_dev + (row + i) * 12;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) dst[j] = e.x[j];
+      }
+    }
+    if (valid) {
+      if (io.reward_dev != nullptr) io.reward_dev[row + i] = reward;
+      if (io.terminated_dev != nullptr) io.terminated_dev[row + i] = term ? 1 : 0;
+      if (io.truncated_dev != nullptr) io.truncated_dev[row + i] = trunc ? 1 : 0;
+      if (io.status_dev != nullptr) io.status_dev[row + i] = (uint8_t)e.fs;
+    }
+  }
+}
+
+// rollout_vjp_kernel's sweep (copterstep_rollout_grad.hip) with the policy's VJP after each step's adjoint: io.actions_dev
+// is the action tape here.  g_a (stored as g_actions) is complete when step k's adjoint returns it: every later step's
+// dependence on a_k runs through x_k, whose adjoint lam already holds.
+template <int TASK, int MODE, bool GYRO>
+__device__ __forceinline__ void rollout_mlp_vjp_body(const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                                                     const MlpArgs& m) {
+  constexpr int A = task_act_dim(TASK);
+  const int lane = threadIdx.x;
+  const uint32_t tile_index = blockIdx.x;
+  const uint32_t i = tile_index * kBlock + threadIdx.x;
+  const uint32_t n = s.n;
+  const bool valid = i < n;
+  const uint32_t ii = valid ? i : 0u;  // (padding lanes recompute env 0's steps and store nothing)
+  const int K = io.num_steps;
+  const bool f32out = io.out_dtype == CS_JAC_F32;
+
+  Coef q = uniform_coef(c);
+  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
+  double lam[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) lam[k] = 0.0;
+  double ga[4];
+
+  // ---- steps K-1 .. 2: starts from the tape, the next step's inputs fetched while this one computes ----
+  StepIn cur;
+  if (K > 1) load_tape_step<TASK>(io, n, ii, K - 1, cur);
+#pragma clang loop unroll(disable)
+  for (int k = K - 1; k >= 2; --k) {
+    StepIn nxt;
+    load_tape_step<TASK>(io, n, ii, k - 1, nxt);
+    const double gr = add_cotangents(io, (size_t)k * n, ii, lam);
+    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, -0.0, -0.0, -0.0, false, true, false, nullptr, lam, ga);
+    if (valid && io.g_actions_dev != nullptr) {
+      if (f32out)
+        store_ga<float, A>(io.g_actions_dev, (size_t)k * n, i, ga);
+      else
+        store_ga<double, A>(io.g_actions_dev, (size_t)k * n, i, ga);
+    }
+    mlp_vjp<TASK>(m.params, m.hidden, cur.x, ga, lam);
+    cur = nxt;
+  }
+
+  // ---- step 1 (peeled: a stored start's NEXT_STEP reset draws the perturbation that enters it) ----
+  if (K > 1) {
+    double px = -0.0, py = -0.0, pz = -0.0;
+    if (io.start_x_dev == nullptr) {
+      using TILE = TileIO<MODE>;
+      const TILE tile(s, tile_index, lane);
+      Env<MODE> e;
+      unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
+      if (e.reset_pending) {
+        resolve_episode<MODE>(c, tile, e);
+        next_episode<MODE, true>(e);
+        pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, true, false, px, py, pz);
+      }
+    }
+    const double gr = add_cotangents(io, (size_t)n, ii, lam);
+    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, px, py, pz, false, true, false, nullptr, lam, ga);
+    if (valid && io.g_actions_dev != nullptr) {
+      if (f32out)
+        store_ga<float, A>(io.g_actions_dev, (size_t)n, i, ga);
+      else
+        store_ga<double, A>(io.g_actions_dev, (size_t)n, i, ga);
+    }
+    mlp_vjp<TASK>(m.params, m.hidden, cur.x, ga, lam);
+  }
+
+  // ---- step 0: from the start point, decoded as the forward decoded it ----
+  StepIn in;
+  double px, py, pz;
+  bool resetting = false, prev_diff = false, prev_none = false;
+  if (io.start_x_dev != nullptr) {
+    bool pend;
+    double prev_sh;
+    explicit_start<TASK, MODE>(c, q, io, i, n, valid, in.x, in.fs, pend, px, py, pz, prev_sh);
+    prev_diff = io.start_prev_shaping_dev == nullptr;
+    prev_none = prev_sh != prev_sh;
+  } else {
+    using TILE = TileIO<MODE>;
+    const TILE tile(s, tile_index, lane);
+    Env<MODE> e;
+    unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
+    resolve_episode<MODE>(c, tile, e);
+    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) in.x[k] = e.x[k];
+    in.fs = e.fs;
+    resetting = e.reset_pending;
+    prev_none = e.prev_sh != e.prev_sh;
+  }
+  in.act = load_action_at<TASK>(io.actions_dev + (size_t)ii * A);
+  const double gr0 = add_cotangents(io, 0, ii, lam);
+  step_adjoint<TASK, MODE, GYRO>(c, q, in, gr0, px, py, pz, resetting, prev_diff, prev_none, nullptr, lam, ga);
+  // (a resetting lane: ga = lam = 0, so the policy adds nothing -- and its pre-reset state need not be finite)
+  if (!resetting) mlp_vjp<TASK>(m.params, m.hidden, in.x, ga, lam);
+  if (valid) {
+    if (io.g_actions_dev != nullptr) {
+      if (f32out)
+        store_ga<float, A>(io.g_actions_dev, 0, i, ga);
+      else
+        store_ga<double, A>(io.g_actions_dev, 0, i, ga);
+    }
+    if (io.g_x0_dev != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        if (f32out)
+          reinterpret_cast<float*>(io.g_x0_dev)[(size_t)k * n + i] = (float)lam[k];
+        else
+          reinterpret_cast<double*>(io.g_x0_dev)[(size_t)k * n + i] = lam[k];
+      }
+    }
+  }
+}
+
+// The backward without the rotor-gyro term is held to 2 wavefronts per SIMD: it fits 256 VGPRs without AGPRs or scratch
+// there, where the allocator left to itself takes 8-16 AGPRs and 1 wavefront.  With the term the same bound spills to
+// scratch, so that form keeps the default (profiles/rollout_mlp_resources.txt).
+template <int TASK, int MODE>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void rollout_mlp_vjp_kernel(
+    const DevConst c, const DevState s, const cs_rollout_io io, const MlpArgs m) {
+  rollout_mlp_vjp_body<TASK, MODE, false>(c, s, io, m);
+}
+template <int TASK, int MODE>
+__global__ __launch_bounds__(kBlock) void rollout_mlp_vjp_gyro_kernel(const DevConst c, const DevState s,
+                                                                      const cs_rollout_io io, const MlpArgs m) {
+  rollout_mlp_vjp_body<TASK, MODE, true>(c, s, io, m);
+}
+
+#define CS_RM_TASKS(M)                                 \
+  switch (task) {                                      \
+    case CS_TASK_LANDER3D: M(CS_TASK_LANDER3D); break; \
+    case CS_TASK_HOVER3D: M(CS_TASK_HOVER3D); break;   \
+    case CS_TASK_LANDER2D: M(CS_TASK_LANDER2D); break; \
+    case CS_TASK_LANDER1D: M(CS_TASK_LANDER1D); break; \
+    case CS_TASK_HOVER2D: M(CS_TASK_HOVER2D); break;   \
+    case CS_TASK_HOVER1D: M(CS_TASK_HOVER1D); break;   \
+    default: return hipErrorInvalidValue;              \
+  }
+
+hipError_t launch_rollout_mlp_states(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                                     const MlpArgs& m, hipStream_t stream) {
+  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
+#define CS_MS_MODE(TASK)                                                                                          \
+  do {                                                                                                            \
+    if (mode == CS_STATE_F32G)                                                                                    \
+      hipLaunchKernelGGL((rollout_mlp_states_kernel<TASK, CS_STATE_F32G>), grid, block, 0, stream, c, s, io, m);   \
+    else if (mode == CS_STATE_F32_RN)                                                                             \
+      hipLaunchKernelGGL((rollout_mlp_states_kernel<TASK, CS_STATE_F32_RN>), grid, block, 0, stream, c, s, io, m); \
+    else                                                                                                          \
+      hipLaunchKernelGGL((rollout_mlp_states_kernel<TASK, CS_STATE_F64>), grid, block, 0, stream, c, s, io, m);    \
+  } while (0)
+  CS_RM_TASKS(CS_MS_MODE)
+#undef CS_MS_MODE
+  return hipGetLastError();
+}
+
+hipError_t launch_rollout_mlp_vjp(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                                  const MlpArgs& m, hipStream_t stream) {
+  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
+#define CS_MV_GYRO(TASK, MODE)                                                                                    \
+  do {                                                                                                            \
+    if (c.gyro)                                                                                                   \
+      hipLaunchKernelGGL((rollout_mlp_vjp_gyro_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);         \
+    else                                                                                                          \
+      hipLaunchKernelGGL((rollout_mlp_vjp_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);              \
+  } while (0)
+#define CS_MV_MODE(TASK)                                                                                          \
+  do {                                                                                                            \
+    if (mode == CS_STATE_F32G)                                                                                    \
+      CS_MV_GYRO(TASK, CS_STATE_F32G);                                                                            \
+    else if (mode == CS_STATE_F32_RN)                                                                             \
+      CS_MV_GYRO(TASK, CS_STATE_F32_RN);                                                                          \
+    else                                                                                                          \
+      CS_MV_GYRO(TASK, CS_STATE_F64);                                                                             \
+  } while (0)
+  CS_RM_TASKS(CS_MV_MODE)
+#undef CS_MV_MODE
+#undef CS_MV_GYRO
+  return hipGetLastError();
+}
+#undef CS_RM_TASKS
+
+// the argument blocks, checked before the context: the MLP block's own checks, then check_rollout_io on a copy of io
+// whose actions_dev is the action tape (returned in `out`)
+int check_rollout_io_mlp(const cs_rollout_io* io, const cs_rollout_mlp_io* mio, const char* who, bool vjp,
+                         cs_rollout_io* out) {
+  const std::string w(who);
+  if (io == nullptr) return report_error(CS_ERR_ARG, (w + ": null io").c_str());
+  if (mio == nullptr) return report_error(CS_ERR_ARG, (w + ": null mio").c_str());
+  if (mio->struct_size != sizeof(cs_rollout_mlp_io))
+    return report_error(CS_ERR_ABI, (w + ": mio->struct_size " + std::to_string(mio->struct_size) + " != " +
+                                     std::to_string(sizeof(cs_rollout_mlp_io)) + " (sizeof(cs_rollout_mlp_io))").c_str());
+  if (mio->hidden < 0 || mio->hidden > CS_MLP_MAX_HIDDEN)
+    return report_error(CS_ERR_ARG, (w + ": hidden " + std::to_string(mio->hidden) + " is not in [0, " +
+                                     std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
+  if (mio->params_dev == nullptr) return report_error(CS_ERR_ARG, (w + ": params_dev is required").c_str());
+  if (mio->actions_out_dev == nullptr)
+    return report_error(CS_ERR_ARG, (w + ": actions_out_dev (the action tape) is required").c_str());
+  if (io->actions_dev != nullptr)
+    return report_error(CS_ERR_ARG, (w + ": io->actions_dev must be NULL (the policy makes the actions; open-loop "
+                                         "offsets go in mio->offsets_dev)").c_str());
+  // the rest is cs_rollout_io's contract, with the action tape where the actions go
+  *out = *io;
+  out->actions_dev = mio->actions_out_dev;
+  return check_rollout_io(out, who, vjp);
+}
+
+}  // namespace
+}  // namespace cs
+
+extern "C" int cs_rollout_mlp_states(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio,
+                                     void* stream) {
+  cs_rollout_io io2;
+  if (int rc_ = cs::check_rollout_io_mlp(io, mio, "cs_rollout_mlp_states", false, &io2)) return rc_;
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, "cs_rollout_mlp_states", stream, &v)) return rc_;
+  const cs::MlpArgs m{mio->params_dev, mio->offsets_dev, mio->actions_out_dev, mio->obs_out_dev, mio->hidden};
+  const hipError_t e = cs::launch_rollout_mlp_states(v.task, v.mode, *v.c, *v.s, io2, m, (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mlp_states: kernel launch");
+  return CS_OK;
+}
+
+extern "C" int cs_rollout_mlp_vjp(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio, void* stream) {
+  cs_rollout_io io2;
+  if (int rc_ = cs::check_rollout_io_mlp(io, mio, "cs_rollout_mlp_vjp", true, &io2)) return rc_;
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, "cs_rollout_mlp_vjp", stream, &v)) return rc_;
+  const cs::MlpArgs m{mio->params_dev, nullptr, nullptr, nullptr, mio->hidden};
+  const hipError_t e = cs::launch_rollout_mlp_vjp(v.task, v.mode, *v.c, *v.s, io2, m, (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mlp_vjp: kernel launch");
+  return CS_OK;
+}

@@ -211,6 +211,18 @@ class ShardedCopterVecEnv:
         return self.local.rollout_vjp_params(self._local_rollout_actions(actions), rollout, gx=gx, gr=gr, state=state,
                                              vehicle=vehicle, dtype=dtype)
 
+    def rollout_mlp_states(self, params, num_steps, hidden, offsets=None, state=None):
+        """CopterVecEnv.rollout_mlp_states of this rank's envs: shard-local, no gather (params: the policy every rank
+        shares; offsets: [K, n_local, A] or the global [K, N, A]; an explicit `state` covers the local envs)."""
+        if offsets is not None:
+            offsets = self._local_rollout_actions(offsets)
+        return self.local.rollout_mlp_states(params, num_steps, hidden, offsets=offsets, state=state)
+
+    def rollout_mlp_vjp(self, params, rollout, gx=None, gr=None, state=None, hidden=None, offsets=None, dtype=None):
+        """CopterVecEnv.rollout_mlp_vjp of this rank's envs: shard-local (rollout, gx, gr: the local envs').  g_params
+        is THIS rank's sum over its envs: a data-parallel caller all-reduces it (sum) across the ranks."""
+        return self.local.rollout_mlp_vjp(params, rollout, gx=gx, gr=gr, state=state, hidden=hidden, dtype=dtype)
+
     def close(self):
         self.local.close()
 

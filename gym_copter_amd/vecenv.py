@@ -26,6 +26,7 @@ import weakref
 import numpy as np
 
 from . import _lib
+from . import mlp as _mlp
 from .spaces import gymnasium_api
 
 # Envs that hold a device context.  Whatever is still open when the interpreter exits is closed by an exit handler,
@@ -91,6 +92,8 @@ STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dThe
 StepJacobian = collections.namedtuple("StepJacobian", "dx du reward_dx reward_du branch")
 # CopterVecEnv.rollout_states' result (device tensors, [K, N, ...])
 Rollout = collections.namedtuple("Rollout", "x reward terminated truncated status")
+# a closed-loop rollout (rollout_mlp_states): Rollout's fields plus the observation and action tapes
+MlpRollout = collections.namedtuple("MlpRollout", "x reward terminated truncated status obs actions")
 
 
 def _torch():
@@ -924,21 +927,25 @@ class CopterVecEnv(_VectorEnvBase):
         self._keep = keep
         return out
 
-    def _rollout_io(self, actions, state):
+    def _rollout_io(self, actions, state, num_steps=None):
         """The cs_rollout_io of rollout_states / rollout_vjp: actions [K,N,A] and the start point; returns (io, K, the
-        tensors the call reads)."""
+        tensors the call reads).  actions=None (the closed-loop calls): no actions, K = num_steps."""
         torch = _torch()
         n, ad = self.num_envs, self.action_dim
-        shape = tuple(actions.shape) if hasattr(actions, "shape") else np.shape(actions)
-        if len(shape) != 3 or shape[0] < 1:
-            raise ValueError("actions must have shape (K, %d, %d) with K >= 1, got %s" % (n, ad, tuple(shape)))
-        K = int(shape[0])
-        a, _ = self._dev_f32(actions, (K, n, ad), "actions")
         io = _lib.RolloutIO()
         io.struct_size = C.sizeof(_lib.RolloutIO)
+        keep = []
+        if actions is None:
+            K = num_steps
+        else:
+            shape = tuple(actions.shape) if hasattr(actions, "shape") else np.shape(actions)
+            if len(shape) != 3 or shape[0] < 1:
+                raise ValueError("actions must have shape (K, %d, %d) with K >= 1, got %s" % (n, ad, tuple(shape)))
+            K = int(shape[0])
+            a, _ = self._dev_f32(actions, (K, n, ad), "actions")
+            io.actions_dev = a.data_ptr()
+            keep.append(a)
         io.num_steps = K
-        io.actions_dev = a.data_ptr()
-        keep = [a]
         if state is not None:
             unknown = set(state) - {"x", "status", "force", "prev_shaping"}
             if unknown or "x" not in state or "status" not in state:
@@ -1117,6 +1124,135 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_rollout_vjp_ex(self._ctx, C.byref(io), C.byref(pio), self._stream()))
         self._keep = keep
         return ga, g0, gv, gf
+
+    def _mlp_io(self, params, hidden, num_steps, offsets, keep):
+        """The cs_rollout_mlp_io of rollout_mlp_states / rollout_mlp_vjp (its tapes not yet set) and the device params."""
+        torch = _torch()
+        if not isinstance(num_steps, int) or isinstance(num_steps, bool) or num_steps < 1:
+            raise ValueError("num_steps must be an int >= 1, got %r" % (num_steps,))
+        P = _mlp.num_params(self.obs_dim, self.action_dim, hidden)    # (checks hidden)
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.dim() != 1:
+            raise ValueError("params must be a 1-D float32 torch tensor of %d values (gym_copter_amd.mlp), got %s"
+                             % (P, getattr(params, "dtype", type(params).__name__)))
+        if params.shape[0] != P:
+            raise ValueError("params must have %d values for obs_dim %d, action_dim %d, hidden %d, got %d"
+                             % (P, self.obs_dim, self.action_dim, hidden, params.shape[0]))
+        p = params.detach().to(self.device).contiguous()
+        keep.append(p)
+        mio = _lib.RolloutMlpIO()
+        mio.struct_size = C.sizeof(_lib.RolloutMlpIO)
+        mio.hidden = hidden
+        mio.params_dev = p.data_ptr()
+        if offsets is not None:
+            u, _ = self._dev_f32(offsets, (num_steps, self.num_envs, self.action_dim), "offsets")
+            keep.append(u)
+            mio.offsets_dev = u.data_ptr()
+        return mio, p
+
+    def rollout_mlp_states(self, params, num_steps, hidden, offsets=None, state=None):
+        """K = num_steps calls of step() with auto-reset DISABLED under a fused MLP policy, as a pure function (DESIGN
+        section 12): step k takes a_k = float32(pi(o_{k-1}) + offsets[k-1]), where o_{k-1} is the float32 observation
+        step() returns for the state before step k (the start's for k = 1) and pi the MLP of `params` ([P] float32, the
+        layout of gym_copter_amd.mlp; hidden = 0 is linear, 1..64 one tanh layer).  offsets [K,N,A] (None = 0) is an
+        open-loop term added to the policy's action.  The start point, the pending perturbation, a pending NEXT_STEP
+        reset, prev_shaping and the step counter are rollout_states'; no env state changes.
+
+        Returns MlpRollout(x, reward, terminated, truncated, status -- rollout_states' fields, bit-identical to a twin
+        env stepped with `actions` --, obs [K,N,OBS] float32 (o_{k-1}), actions [K,N,A] float32 (a_k)).  Asynchronous on
+        the current stream; the tensors are buffers of this env, overwritten by its next call with the same K."""
+        self._check_open()
+        torch = _torch()
+        keep = []
+        mio, _ = self._mlp_io(params, hidden, num_steps, offsets, keep)
+        io, K, k2 = self._rollout_io(None, state, num_steps)
+        keep += k2
+        n, dev = self.num_envs, self.device
+        out = self._rollout_cache(("mlp_states", K), lambda: MlpRollout(
+            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
+            torch.empty((K, n), dtype=torch.float64, device=dev),
+            torch.empty((K, n), dtype=torch.bool, device=dev),
+            torch.empty((K, n), dtype=torch.bool, device=dev),
+            torch.empty((K, n), dtype=torch.uint8, device=dev),
+            torch.empty((K, n, self.obs_dim), dtype=torch.float32, device=dev),
+            torch.empty((K, n, self.action_dim), dtype=torch.float32, device=dev)))
+        io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in out[:5])
+        mio.obs_out_dev, mio.actions_out_dev = out.obs.data_ptr(), out.actions.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_mlp_states(self._ctx, C.byref(io), C.byref(mio), self._stream()))
+        self._keep = keep
+        return out
+
+    def rollout_mlp_vjp(self, params, rollout, gx=None, gr=None, state=None, hidden=None, offsets=None, dtype=None,
+                        param_grad=True):
+        """Reverse-mode gradient of a closed-loop rollout: given the cotangents gx [K,N,12] (on rollout.x) and gr [K,N]
+        (on rollout.reward), either None (zero), returns (g_params [P] float64, g_actions [K,N,A], g_x0 [12,N] or None).
+
+        g_actions = dL / d a_k including every later step's dependence on a_k through the policy -- which is also
+        dL / d offsets; g_x0 = dL / d state["x"] of an explicit start (including the path through o_0), None for the
+        stored one; g_params = sum over envs and steps of J_params pi^T g_actions, reduced by torch from rollout.obs
+        (gym_copter_amd.mlp.param_grad; param_grad=False skips it and returns None).  `rollout` is what
+        rollout_mlp_states(params, K, hidden, offsets, state) returned (its x, status, obs and actions are the tape;
+        with the stored start the env must not have been stepped since); `hidden` must be that call's.  The float32
+        rounding of o and a is straight-through.  dtype: torch.float64 (default) or torch.float32 for g_actions and
+        g_x0.  Asynchronous on the current stream; g_actions and g_x0 are buffers of this env, overwritten by its next
+        call with the same K and dtype.  (`offsets` is accepted for symmetry with the forward; the backward reads the
+        action tape, not the offsets.)"""
+        self._check_open()
+        torch = _torch()
+        if hidden is None:
+            raise ValueError("hidden is required (the forward's)")
+        dtype = torch.float64 if dtype is None else dtype
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("dtype must be torch.float64 or torch.float32")
+        n, ad, od = self.num_envs, self.action_dim, self.obs_dim
+        acts = getattr(rollout, "actions", None)
+        if not isinstance(acts, torch.Tensor) or acts.dim() != 3:
+            raise ValueError("rollout.actions must be the [K,N,A] action tape of rollout_mlp_states")
+        K = int(acts.shape[0])
+        keep = []
+        mio, p = self._mlp_io(params, hidden, K, None, keep)
+        io, _, k2 = self._rollout_io(None, state, K)
+        keep += k2
+        io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+        obs = getattr(rollout, "obs", None)
+        for t, name, shape, dt in ((rollout.x, "rollout.x", (K, n, 12), torch.float64),
+                                   (rollout.status, "rollout.status", (K, n), torch.uint8),
+                                   (acts, "rollout.actions", (K, n, ad), torch.float32),
+                                   (obs, "rollout.obs", (K, n, od), torch.float32)):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a device tensor of shape %s (rollout_mlp_states' result)" % (name, shape))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, self.device))
+        io.x_dev, io.status_dev = rollout.x.data_ptr(), rollout.status.data_ptr()
+        mio.actions_out_dev = acts.data_ptr()
+
+        def cot(v, shape, name):
+            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if not t.dtype.is_floating_point:
+                raise ValueError("%s must be a floating-point array" % name)
+            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+        if gx is not None:
+            io.gx_dev = cot(gx, (K, n, 12), "gx")
+        if gr is not None:
+            io.gr_dev = cot(gr, (K, n), "gr")
+        dev = self.device
+        ga = self._rollout_cache(("mlp_g_actions", K, dtype), lambda: torch.empty((K, n, ad), dtype=dtype, device=dev))
+        io.g_actions_dev = ga.data_ptr()
+        g0 = None
+        if state is not None:
+            g0 = self._rollout_cache(("mlp_g_x0", dtype), lambda: torch.empty((12, n), dtype=dtype, device=dev))
+            io.g_x0_dev = g0.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_mlp_vjp(self._ctx, C.byref(io), C.byref(mio), self._stream()))
+            gp = _mlp.param_grad(p, hidden, obs, ga) if param_grad else None
+        self._keep = keep
+        return gp, ga, g0
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

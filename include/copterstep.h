@@ -27,6 +27,9 @@
  *                            rollout (vector-Jacobian product)
  *   cs_rollout_*_ex          the same with a vehicle override    + the vehicle_params dict (vehicles/dji_phantom.py:9-26)
  *                            and gradients w.r.t. vehicle, force
+ *   cs_rollout_mlp_states    the same rollout closed-loop       lander.py:40-65 with a policy in place of the random
+ *   cs_rollout_mlp_vjp       under a fused MLP policy, and      action; the rollout lines above, differentiated
+ *                            its gradient
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -640,6 +643,56 @@ typedef struct cs_rollout_param_io {
 } cs_rollout_param_io;
 int cs_rollout_states_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_param_io* pio, void* stream);
 int cs_rollout_vjp_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_param_io* pio, void* stream);
+
+/* Differentiable CLOSED-LOOP rollouts under a fused MLP policy: analytic policy gradients
+ * (backpropagation through the simulator) without a Python loop.  The loop replaced is lander.py:40-65 with a policy in
+ * place of the random action -- observe, act, step -- K times.  A closed-loop rollout is K calls of cs_step with auto-reset
+ * disabled in which step k = 1..K takes
+ *     a_k = fl32( pi_theta(o_{k-1}) + u_k )
+ * o_{k-1} is the float32 observation cs_step returns for the state before step k (the task's obs_dim state slots from
+ * its first observed slot: what a copterstep_rollout.h policy receives; for k = 1 that of the start point, stored or
+ * explicit); u_k = offsets_dev[k-1] (NULL = 0).  Everything else -- the start point, the pending perturbation, a
+ * NEXT_STEP reset pending at the start, prev_shaping, the step counter, no env state written -- is cs_rollout_states'.
+ *
+ * The policy is an MLP shared by every env, one flat float32 parameter vector theta = params_dev:
+ *   hidden = 0:        a = W o + b                          [W (A x OBS, row-major), b (A)]            P = A (OBS + 1)
+ *   1 <= hidden <= 64: h = tanh(W1 o + b1), a = W2 h + b2   [W1 (H x OBS), b1 (H), W2 (A x H), b2 (A)]
+ *                                                           P = H (OBS + 1) + A (H + 1)
+ * Its float32 arithmetic is fixed (no dependence on the compiler's contraction): every sum is an fmaf chain that starts
+ * from its bias and adds the terms in index order -- pre_j = fmaf(W1[j][OBS-1], o[OBS-1], ... fmaf(W1[j][0], o[0], b1[j])),
+ * h_j = tanhf(pre_j) (the device library's tanhf), a_c = fmaf(W2[c][H-1], h_{H-1}, ... fmaf(W2[c][0], h_0, b2[c])) --
+ * and a_k = a + u_k is one float32 addition (skipped when offsets_dev is NULL).
+ *
+ * cs_rollout_mlp_states (forward) writes cs_rollout_io's x, reward, flag and status outputs as cs_rollout_states does
+ * (bit-identical to an env with auto-reset disabled stepped with actions_out_dev), plus
+ *   actions_out_dev  [K,N,A] float32  a_k (required: it is the backward's tape)
+ *   obs_out_dev      [K,N,OBS] float32 o_{k-1}, or NULL (not written)
+ * cs_rollout_mlp_vjp (backward) reads the tape (io x_dev, status_dev and actions_out_dev, the forward's own, with the
+ * same params, hidden and start; offsets_dev and obs_out_dev are not read) and writes, in io->out_dtype,
+ *   g_actions_dev    [K,N,A]  dL / d a_k INCLUDING every later step's dependence on a_k through the policy; = dL / d u_k
+ *   g_x0_dev         [12,N]   dL / d x0 (an explicit start), including the path through o_0
+ * The derivative rules are cs_rollout_vjp's plus the policy's: the float32 rounding of o and of a is straight-through
+ * (as the storage rounding is), tanh' = 1 - h^2 with h recomputed in float64, lambda_o += J_o pi^T g_a accumulated in
+ * float64.  A lane that resets in step 1 has g_a_1 = 0, so the policy adds nothing through a_1.  The gradient with
+ * respect to theta is a reduction over every env and step that the caller makes from the obs tape and g_actions:
+ *     g_theta = sum_{k,n} J_theta pi(o_{k-1,n})^T g_a_{k,n}
+ * (gym_copter_amd.mlp.param_grad: h recomputed in float64, as the kernel does).
+ *
+ * io->actions_dev must be NULL in both calls (the policy makes the actions).  params_dev is read by the scalar unit:
+ * 4-B aligned, never written while a call runs; actions_out_dev and obs_out_dev 16-B aligned.  The vehicle override and
+ * parameter gradients of cs_rollout_param_io are not part of these calls.  Asynchronous on `stream`;
+ * mio->struct_size must be sizeof(cs_rollout_mlp_io) (else CS_ERR_ABI); both blocks are checked before the context. */
+#define CS_MLP_MAX_HIDDEN 64
+typedef struct cs_rollout_mlp_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_mlp_io) */
+  int32_t hidden;              /* 0 .. CS_MLP_MAX_HIDDEN */
+  const float* params_dev;     /* [P] float32, required */
+  const float* offsets_dev;    /* [K,N,A] u, or NULL */
+  float* actions_out_dev;      /* [K,N,A] a_k: written by _states, read by _vjp as the tape (required) */
+  float* obs_out_dev;          /* [K,N,OBS] o_{k-1}: written by _states, NULL = not written */
+} cs_rollout_mlp_io;
+int cs_rollout_mlp_states(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio, void* stream);
+int cs_rollout_mlp_vjp(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio, void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in

@@ -1,0 +1,546 @@
+"""Closed-loop differentiable rollouts under a fused MLP policy on the device (cs_rollout_mlp_states /
+cs_rollout_mlp_vjp, CopterVecEnv.rollout_mlp_states / rollout_mlp_vjp, gym_copter_amd.differentiable_mlp_rollout): the
+primal bit-identical to a twin env stepped with the forward's own action tape, the tapes against the float32 observation
+and a float64 NumPy MLP, theta = 0 against the open-loop calls, the gradient against chained step_jacobian + a float64
+policy Jacobian and against central differences of the float64 closed-loop oracle (tests/mlp_rollout_fd.py), no side
+effects, autograd, policy training on Hover3D, the sharded passthrough, float32 outputs, errors and 64-bit offsets."""
+import numpy as np
+import pytest
+
+from gpu_util import have_gpu, to_np
+from jacobian_fd import hover_action
+from mlp_rollout_fd import OBS_SHAPE, fd_mlp_rollout_vjp
+from oracle.refcpu import AIRBORNE, LANDED
+from rollout_fd import shaping_grad
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not have_gpu(), reason="needs a HIP device")]
+
+TASKS = ["lander3d", "hover3d", "lander2d", "lander1d", "hover2d", "hover1d"]
+TASK_A = {"lander3d": 4, "hover3d": 4, "lander2d": 2, "hover1d": 1, "lander1d": 1, "hover2d": 2}
+U32 = 2.0 ** -24
+
+
+def _env(task, n, mode="float64", autoreset="disabled", **kw):
+    import gym_copter_amd
+    kw.setdefault("max_steps", 100000)
+    return gym_copter_amd.CopterVecEnv(task=task, num_envs=n, state_dtype=mode, autoreset_mode=autoreset, **kw)
+
+
+def _theta(task, hidden, seed, scale=0.1, env=None):
+    """A policy near hover: the output bias is the hover motor value, the output weights small."""
+    import torch
+    from gym_copter_amd import mlp
+    p = mlp.init(OBS_SHAPE[task][1], TASK_A[task], hidden, generator=torch.Generator().manual_seed(seed),
+                 out_bias=hover_action(), out_scale=scale)
+    return p if env is None else p.to(env.device)
+
+
+def _dev(a, env, dtype=None):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(env.device, dtype=dtype)
+
+
+def _scaled(got, want):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    return float(np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want))))
+
+
+def _point(n, rng):
+    x = np.empty((12, n))
+    x[0], x[2] = rng.uniform(-3, 3, (2, n))
+    x[1], x[3], x[5] = rng.uniform(-1, 1, (3, n))
+    x[4] = rng.uniform(-15, -8, n)
+    x[6], x[8] = rng.uniform(-0.2, 0.2, (2, n))
+    x[10] = rng.uniform(-0.5, 0.5, n)
+    x[7], x[9], x[11] = rng.uniform(-0.5, 0.5, (3, n))
+    return x, np.full(n, AIRBORNE, np.uint8)
+
+
+def _compare_with_twin(twin, r, lanes=None):
+    """twin (auto-reset disabled, or the env itself) stepped with the rollout's action tape == the rollout"""
+    import torch
+    sel = slice(None) if lanes is None else lanes
+    tsel = slice(None) if lanes is None else torch.from_numpy(lanes).to(twin.device)
+    for k in range(r.actions.shape[0]):
+        _, rew, term, trunc, _ = twin.step(r.actions[k].clone())
+        s = twin.get_state(only=("x", "status"))
+        assert np.array_equal(to_np(r.x[k]).T[:, sel], s["x"][:, sel]), k
+        assert np.array_equal(to_np(r.status[k])[sel], s["status"][sel]), k
+        assert torch.equal(r.reward[k].float()[tsel], rew[tsel]), k
+        assert torch.equal(r.terminated[k][tsel], term[tsel]) and torch.equal(r.truncated[k][tsel], trunc[tsel]), k
+
+
+def _obs_of(task, x12):
+    first, od = OBS_SHAPE[task]
+    return np.asarray(x12[..., first:first + od], np.float64).astype(np.float32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. the primal is K calls of step() with the forward's own actions, bit for bit
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["float32", "float32_rn", "float64"])
+@pytest.mark.parametrize("task", TASKS)
+def test_primal_is_bit_identical_to_a_twin(task, mode):
+    """From reset (a perturbation pending: the stored start), K = 30, with open-loop offsets; the width cycles through
+    0, 1, 32, 64 over the cases."""
+    import torch
+    n, K = 1000, 30
+    hidden = [0, 1, 32, 64][(TASKS.index(task) * 3 + ["float32", "float32_rn", "float64"].index(mode)) % 4]
+    env, twin = _env(task, n, mode, seed=5), _env(task, n, mode, seed=5)
+    try:
+        env.reset()
+        twin.reset()
+        s0 = env.get_state(only=("x",))["x"].T.copy()
+        rng = np.random.default_rng(TASKS.index(task) * 7 + len(mode))
+        u = _dev(rng.uniform(-0.3, 0.3, (K, n, TASK_A[task])).astype(np.float32), env)
+        p = _theta(task, hidden, 1, env=env)
+        r = env.rollout_mlp_states(p, K, hidden, offsets=u)
+        r = type(r)(*(t.clone() for t in r))
+        assert r.obs.shape == (K, n, OBS_SHAPE[task][1]) and r.actions.shape == (K, n, TASK_A[task])
+        assert torch.isfinite(r.actions).all()
+        assert np.array_equal(to_np(r.obs[0]), _obs_of(task, s0))
+        _compare_with_twin(twin, r)
+    finally:
+        env.close()
+        twin.close()
+
+
+@pytest.mark.parametrize("case", ["substeps10_h32", "explicit_h64", "explicit_force_h1", "substeps10_f32_h0"])
+def test_primal_bit_identity_configurations(case):
+    n, K = 1024, 30
+    substeps = 10 if case.startswith("substeps10") else 1
+    mode = "float32" if "f32" in case or case.startswith("explicit_force") else "float64"
+    hidden = int(case.rsplit("_h", 1)[1])
+    env, twin = _env("lander3d", n, mode, seed=2, substeps=substeps), _env("lander3d", n, mode, seed=2,
+                                                                           substeps=substeps)
+    try:
+        env.reset()
+        twin.reset()
+        rng = np.random.default_rng(9)
+        state = None
+        if case.startswith("explicit"):
+            x, st = _point(n, rng)
+            if mode != "float64":
+                x = x.astype(np.float32).astype(np.float64)
+            # (a force the float32 storage holds exactly: the twin keeps its explicit force in a float32 word)
+            f = rng.uniform(-20, 20, (3, n)).astype(np.float32).astype(np.float64) if "force" in case else None
+            state = {"x": x, "status": st}
+            s = twin.get_state()
+            twin.set_state(x=x, status=st, steps=s["steps"], prev_shaping=np.full(n, np.nan), force=f,
+                           flags=np.full(n, 5 if f is not None else 0, np.uint8))    # (bit 0 pending, bit 2 explicit)
+            state["prev_shaping"] = np.full(n, np.nan)
+            if f is not None:
+                state["force"] = f
+        p = _theta("lander3d", hidden, 2, env=env)
+        r = env.rollout_mlp_states(p, K, hidden, state=state)
+        r = type(r)(*(t.clone() for t in r))
+        if state is not None:
+            assert np.array_equal(to_np(r.obs[0]), _obs_of("lander3d", state["x"].T))
+        _compare_with_twin(twin, r)
+    finally:
+        env.close()
+        twin.close()
+
+
+def test_primal_from_pending_next_step_resets():
+    """A next_step env with resets pending at the start: the rollout resets them in step 1 (the policy's first action
+    is ignored there) with the draw step() makes; stepping the same env with the action tape afterwards reproduces it on
+    every env that does not terminate inside the horizon."""
+    n, K = 2048, 20
+    env = _env("lander3d", n, "float32", autoreset="next_step", seed=11)
+    try:
+        env.reset()
+        rng = np.random.default_rng(12)
+        pend = np.zeros(n, bool)
+        for _ in range(200):
+            _, _, term, trunc, _ = env.step(_dev(rng.uniform(0, 1, (n, 4)).astype(np.float32), env))
+            pend = to_np(term | trunc).astype(bool)
+            if pend.sum() >= 32:
+                break
+        assert pend.sum() >= 32
+        r = env.rollout_mlp_states(_theta("lander3d", 32, 3, env=env), K, 32)
+        r = type(r)(*(t.clone() for t in r))
+        quiet = ~to_np(r.terminated | r.truncated).any(axis=0)
+        assert (quiet & pend).sum() >= 16
+        _compare_with_twin(env, r, lanes=np.flatnonzero(quiet))
+    finally:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. the tapes
+# ---------------------------------------------------------------------------------------------------------------------
+def _action_bound(theta, hidden, obs, A):
+    """|a32 - a64| for the documented float32 arithmetic: fmaf chains of m terms (bias first) err by at most m u times
+    the sum of their terms' magnitudes; tanhf by a few ulp (4 u |h| + 1e-30 taken), and tanh' <= 1 carries the
+    pre-activation's error into h; the offset's addition rounds once.  Returned x 2."""
+    import torch
+    from gym_copter_amd import mlp
+    p = {k: v.double().abs().numpy() for k, v in mlp.unpack(torch.as_tensor(theta).cpu(), obs.shape[-1], A,
+                                                             hidden).items()}
+    o = np.abs(obs.astype(np.float64))
+    OBS = o.shape[-1]
+    if hidden == 0:
+        mag = o @ p["W"].T + p["b"]
+        return 2 * ((OBS + 1) * U32 * mag)
+    pre_mag = o @ p["W1"].T + p["b1"]
+    dh = (OBS + 1) * U32 * pre_mag + 4 * U32 + 1e-30
+    out_mag = p["b2"] + np.ones_like(pre_mag) @ p["W2"].T     # |h| <= 1
+    return 2 * ((hidden + 1) * U32 * out_mag + dh @ p["W2"].T)
+
+
+@pytest.mark.parametrize("hidden", [0, 1, 32, 64])
+@pytest.mark.parametrize("task", ["lander3d", "hover2d"])
+def test_tapes_are_the_observations_and_the_float32_policy(task, hidden):
+    n, K = 777, 12
+    A = TASK_A[task]
+    env = _env(task, n, "float32", seed=4)
+    try:
+        env.reset()
+        s0 = env.get_state(only=("x",))["x"].T.copy()
+        rng = np.random.default_rng(hidden)
+        u = rng.uniform(-0.2, 0.2, (K, n, A)).astype(np.float32)
+        p = _theta(task, hidden, 7, scale=1.0, env=env)
+        r = env.rollout_mlp_states(p, K, hidden, offsets=_dev(u, env))
+        obs, acts, x = to_np(r.obs).copy(), to_np(r.actions).copy(), to_np(r.x).copy()
+        assert np.array_equal(obs[0], _obs_of(task, s0))
+        assert np.array_equal(obs[1:], _obs_of(task, x[:-1]))
+        from mlp_rollout_fd import policy64
+        pc = p.cpu().numpy()
+        want = policy64(pc, obs.reshape(-1, obs.shape[-1]), hidden, A).reshape(K, n, A) + u
+        bound = _action_bound(pc, hidden, obs, A) + U32 * np.abs(want)
+        err = np.abs(acts.astype(np.float64) - want)
+        assert np.all(err <= bound), float(np.max(err - bound))
+    finally:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. theta = 0 is the open-loop rollout of the offsets
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("hidden", [0, 32])
+def test_zero_policy_is_the_open_loop_rollout(hidden):
+    import torch
+    n, K = 2000, 16
+    env = _env("lander3d", n, "float32", seed=3)
+    try:
+        env.reset()
+        rng = np.random.default_rng(1)
+        u = _dev((hover_action() * rng.uniform(0.5, 1.5, (K, n, 4))).astype(np.float32), env)
+        x, st = _point(n, rng)
+        x = x.astype(np.float32).astype(np.float64)
+        gx = _dev(rng.standard_normal((K, n, 12)), env)
+        gr = _dev(rng.standard_normal((K, n)), env)
+        from gym_copter_amd import mlp
+        p0 = torch.zeros(mlp.num_params(10, 4, hidden), dtype=torch.float32, device=env.device)
+        for state in (None, {"x": x, "status": st}):
+            r = env.rollout_mlp_states(p0, K, hidden, offsets=u, state=state)
+            r = type(r)(*(t.clone() for t in r))
+            q = env.rollout_states(u, state=state)
+            for a, b in zip(r[:5], q):
+                assert torch.equal(a, b)
+            assert torch.equal(r.actions, u)
+            gp, ga, g0 = env.rollout_mlp_vjp(p0, r, gx=gx, gr=gr, state=state, hidden=hidden)
+            ga, g0 = ga.clone(), None if g0 is None else g0.clone()
+            wa, w0 = env.rollout_vjp(u, q, gx=gx, gr=gr, state=state)
+            assert torch.equal(ga, wa)
+            assert (g0 is None) == (w0 is None) and (g0 is None or torch.equal(g0, w0))
+            assert gp.shape == p0.shape and gp.dtype == torch.float64 and torch.isfinite(gp).all()
+    finally:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. the gradient against chained step_jacobian + a float64 policy Jacobian on the kernel's own tape
+# ---------------------------------------------------------------------------------------------------------------------
+def _policy_jac(theta, hidden, obs, A):
+    """J_o pi at obs [n, OBS] in float64: [n, A, OBS]"""
+    import torch
+    from gym_copter_amd import mlp
+    p = {k: v.double().numpy() for k, v in mlp.unpack(torch.as_tensor(theta).cpu(), obs.shape[-1], A, hidden).items()}
+    o = obs.astype(np.float64)
+    if hidden == 0:
+        return np.broadcast_to(p["W"], (o.shape[0],) + p["W"].shape)
+    h = np.tanh(o @ p["W1"].T + p["b1"])
+    return np.einsum("ch,nh,hj->ncj", p["W2"], 1 - h * h, p["W1"])
+
+
+@pytest.mark.parametrize("task,hidden", [("lander3d", 0), ("lander3d", 32), ("hover3d", 16)])
+def test_gradient_equals_chained_step_jacobians_and_policy_jacobian(task, hidden):
+    """2 048 envs, K = 24, float32 storage, an explicit start (g_x0), LANDED envs, offsets that clip some actions: g_u,
+    g_x0 and g_theta equal the reverse product of step_jacobian at the tape plus J_o pi at the obs tape (and
+    -grad shaping(x_{k-1}) where a Lander step's reward has a gradient), within 1e-9 scaled."""
+    import torch
+    from gym_copter_amd import mlp
+    n, K, A = 2048, 24, 4
+    first, od = OBS_SHAPE[task]
+    rng = np.random.default_rng(31 + hidden)
+    env = _env(task, n, "float32", seed=4)
+    try:
+        env.reset()
+        x, st = _point(n, rng)
+        x = x.astype(np.float32).astype(np.float64)
+        q = n // 8
+        x[4, :q], x[5, :q], st[:q] = 0.0, 0.0, LANDED
+        u = np.zeros((K, n, A), np.float32)
+        u[:, q:2 * q] = rng.uniform(-0.8, 0.8, (K, q, A))                     # some clipped
+        state = {"x": x, "status": st}
+        p = _theta(task, hidden, 5, scale=0.3, env=env)
+        gx, gr = rng.standard_normal((K, n, 12)), rng.standard_normal((K, n))
+        r = env.rollout_mlp_states(p, K, hidden, offsets=_dev(u, env), state=state)
+        r = type(r)(*(t.clone() for t in r))
+        gp, ga, g0 = env.rollout_mlp_vjp(p, r, gx=_dev(gx, env), gr=_dev(gr, env), state=state, hidden=hidden)
+        gp, ga, g0 = to_np(gp).copy(), to_np(ga).copy(), to_np(g0).copy()
+        tape_x, tape_s, obs = to_np(r.x).copy(), to_np(r.status).copy(), to_np(r.obs).copy()
+        acts = r.actions
+        assert (tape_s == LANDED).any() and (to_np(acts) < 0).any()
+        lam = np.zeros((n, 12))
+        want = np.zeros((K, n, A))
+        max_angle = np.radians(45)
+        for k in range(K - 1, -1, -1):
+            lam += gx[k]
+            if k == 0:
+                jac = env.step_jacobian(acts[0], state={"x": x, "status": st})
+            else:
+                jac = env.step_jacobian(acts[k], state={"x": tape_x[k - 1].T.copy(), "status": tape_s[k - 1]})
+            dx, du, rdx, rdu = (to_np(t).astype(np.float64) for t in jac[:4])
+            want[k] = np.einsum("nij,ni->nj", du, lam) + gr[k][:, None] * rdu
+            new = np.einsum("nij,ni->nj", dx, lam) + gr[k][:, None] * rdx
+            xprev = x.T if k == 0 else tape_x[k - 1]
+            xk = tape_x[k]
+            tilt = ~((np.abs(xk[:, 0]) >= 10) | (np.abs(xk[:, 2]) >= 10)) & \
+                ((np.abs(xk[:, 6]) >= max_angle) | (np.abs(xk[:, 8]) >= max_angle))
+            if task.startswith("lander"):                                        # (the explicit start's shaping(x0))
+                new -= (gr[k] * ~tilt)[:, None] * shaping_grad(xprev.T).T
+            new[:, first:first + od] += np.einsum("ncj,nc->nj", _policy_jac(p.cpu(), hidden, obs[k], A), want[k])
+            lam = new
+        assert _scaled(ga, want) <= 1e-9, _scaled(ga, want)
+        assert _scaled(g0, lam.T) <= 1e-9, _scaled(g0, lam.T)
+        wp = mlp.param_grad(p.cpu(), hidden, torch.from_numpy(obs), torch.from_numpy(want)).numpy()
+        assert np.max(np.abs(gp - wp) / np.maximum(1.0, np.abs(wp))) <= 1e-9
+    finally:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. the gradient against central differences of the float64 closed-loop oracle
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("task,hidden,substeps", [("lander3d", 8, 1), ("hover3d", 0, 1), ("lander2d", 4, 10),
+                                                  ("hover1d", 3, 1)])
+def test_gradient_matches_central_differences(task, hidden, substeps):
+    """float64 storage, K = 8, explicit starts away from every branch, a policy whose feedback moves the motors by ~10 %
+    of hover: g_theta, g_u and g_x0 within 1e-5 scaled (the device's float32 observation and action roundings move the
+    trajectory by ~1e-7 relative; the bar covers that)."""
+    n, K, A = 48, 8, TASK_A[task]
+    rng = np.random.default_rng(7)
+    env = _env(task, n, "float64", substeps=substeps)
+    try:
+        x, st = _point(n, rng)
+        u = (hover_action() * rng.uniform(-0.2, 0.2, (K, n, A))).astype(np.float32)
+        p = _theta(task, hidden, 9, scale=0.001 if hidden else 0.0005, env=env)   # feedback of ~10 % of hover
+        gx, gr = rng.standard_normal((K, n, 12)), rng.standard_normal((K, n))
+        state = {"x": x, "status": st}
+        r = env.rollout_mlp_states(p, K, hidden, offsets=_dev(u, env), state=state)
+        gp, ga, g0 = env.rollout_mlp_vjp(p, r, gx=_dev(gx, env), gr=_dev(gr, env), state=state, hidden=hidden)
+        wp, wu, w0 = fd_mlp_rollout_vjp(task, x, st, p.cpu().double().numpy(), hidden, K, offsets=u.astype(np.float64),
+                                        gx=gx, gr=gr, substeps=substeps)
+        errs = (_scaled(to_np(gp), wp), _scaled(to_np(ga), wu), _scaled(to_np(g0), w0))
+        print("central differences %s H=%d substeps=%d: g_theta %.2e g_u %.2e g_x0 %.2e" % ((task, hidden, substeps)
+                                                                                              + errs))
+        assert max(errs) <= 1e-5, errs
+    finally:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. no side effects
+# ---------------------------------------------------------------------------------------------------------------------
+def test_rollout_changes_no_env_state():
+    import torch
+    n, K = 1000, 16
+    env = _env("lander3d", n, "float32", autoreset="next_step", seed=8, episode_stats=True)
+    twin = _env("lander3d", n, "float32", autoreset="next_step", seed=8, episode_stats=True)
+    try:
+        rng = np.random.default_rng(0)
+        env.reset()
+        twin.reset()
+        for _ in range(30):
+            a = _dev(rng.uniform(0, 1, (n, 4)).astype(np.float32), env)
+            env.step(a)
+            twin.step(a)
+        p = _theta("lander3d", 16, 1, env=env)
+        r = env.rollout_mlp_states(p, K, 16)
+        env.rollout_mlp_vjp(p, r, gx=torch.ones((K, n, 12), dtype=torch.float64, device=env.device),
+                            gr=torch.ones((K, n), dtype=torch.float64, device=env.device), hidden=16)
+        s1, s2 = env.get_state(), twin.get_state()
+        assert sorted(s1) == sorted(s2)
+        for k in s1:
+            assert np.array_equal(s1[k], s2[k], equal_nan=True), k
+        for _ in range(3):            # the RNG position too: resets after this draw what the twin's draw
+            a = _dev(rng.uniform(0, 1, (n, 4)).astype(np.float32), env)
+            o1, o2 = env.step(a), twin.step(a)
+            for u, v in zip(o1[:4], o2[:4]):
+                assert torch.equal(u, v)
+    finally:
+        env.close()
+        twin.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. autograd
+# ---------------------------------------------------------------------------------------------------------------------
+def test_differentiable_mlp_rollout_autograd():
+    import torch
+    import gym_copter_amd
+    n, K, hidden = 512, 10, 16
+    rng = np.random.default_rng(5)
+    env = _env("lander3d", n, "float64")
+    try:
+        x, st = _point(n, rng)
+        p = _theta("lander3d", hidden, 4, env=env).requires_grad_(True)
+        u = _dev(rng.uniform(-0.1, 0.1, (K, n, 4)).astype(np.float32), env).requires_grad_(True)
+        x0 = _dev(x, env).requires_grad_(True)
+        state = {"x": x0, "status": st}
+        gx, gr = _dev(rng.standard_normal((K, n, 12)), env), _dev(rng.standard_normal((K, n)), env)
+        r = gym_copter_amd.differentiable_mlp_rollout(env, p, K, hidden, offsets=u, state=state)
+        assert not r.obs.requires_grad and not r.actions.requires_grad and not r.status.requires_grad
+        loss = (r.x * gx).sum() + (r.reward * gr).sum()
+        loss.backward()
+        r2 = env.rollout_mlp_states(p.detach(), K, hidden, offsets=u.detach(), state={"x": x, "status": st})
+        gp, ga, g0 = env.rollout_mlp_vjp(p.detach(), r2, gx=gx, gr=gr, state={"x": x, "status": st}, hidden=hidden)
+        assert torch.equal(p.grad, gp.float()) and torch.equal(u.grad, ga.float()) and torch.equal(x0.grad, g0)
+        # once differentiable: a double backward raises
+        r = gym_copter_amd.differentiable_mlp_rollout(env, p, K, hidden, offsets=u, state=state)
+        g, = torch.autograd.grad(r.reward.sum(), p, create_graph=True)
+        with pytest.raises(RuntimeError):
+            g.sum().backward()
+        # an in-place change of params between the forward and the backward is refused
+        r = gym_copter_amd.differentiable_mlp_rollout(env, p, K, hidden, state=state)
+        with torch.no_grad():
+            p.add_(0.0)
+        with pytest.raises(RuntimeError):
+            r.reward.sum().backward()
+        with pytest.raises(ValueError):
+            gym_copter_amd.differentiable_mlp_rollout(env, p.detach().double(), K, hidden)
+    finally:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. application: analytic policy gradients on Hover3D
+# ---------------------------------------------------------------------------------------------------------------------
+def test_policy_training_holds_hover3d():
+    """4 096 Hover3D envs started around hover with random altitude offsets and climb rates, K = 64 (0.64 s), a tanh
+    MLP (H = 32) trained by Adam through differentiable_mlp_rollout for 60 iterations on the mean squared altitude error
+    plus 0.1 x the squared climb rate over the horizon: the horizon loss falls by the margin of DESIGN section 12.  The
+    step size is ~1 % of the hover motor value (0.0166): the motors act on thrust through a_k^2."""
+    import torch
+    import gym_copter_amd
+    n, K, hidden = 4096, 64, 32
+    rng = np.random.default_rng(61)
+    env = _env("hover3d", n, "float32", seed=1)
+    try:
+        x = np.zeros((12, n))
+        x[0], x[2] = rng.uniform(-0.5, 0.5, (2, n))
+        x[4] = -5.0 + rng.uniform(-0.5, 0.5, n)
+        x[5] = rng.uniform(-1.0, 1.0, n)
+        x = x.astype(np.float32).astype(np.float64)
+        state = {"x": _dev(x, env), "status": np.full(n, AIRBORNE, np.uint8)}
+        p = _theta("hover3d", hidden, 0, scale=0.01, env=env).requires_grad_(True)
+        opt = torch.optim.Adam([p], lr=2e-4)
+        losses = []
+        for _ in range(60):
+            opt.zero_grad()
+            r = gym_copter_amd.differentiable_mlp_rollout(env, p, K, hidden, state=state)
+            loss = ((r.x[..., 4] + 5.0) ** 2 + 0.1 * r.x[..., 5] ** 2).mean()
+            loss.backward()
+            opt.step()
+            losses.append(float(loss.detach()))
+        print("hover3d APG: loss %.4f -> %.4f (min %.4f)" % (losses[0], losses[-1], min(losses)))
+        assert np.isfinite(losses).all()
+        assert losses[-1] < 0.7 * losses[0], (losses[0], losses[-1])   # measured: 0.179 -> 0.090
+    finally:
+        env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 9. sharded passthrough, float32 outputs, errors, 64-bit offsets
+# ---------------------------------------------------------------------------------------------------------------------
+def test_sharded_single_rank_matches_plain_env():
+    import torch
+    from gym_copter_amd.sharded import ShardedCopterVecEnv
+    n, K = 4097, 10
+    sh = ShardedCopterVecEnv("lander3d", n, device=0, seed=6, autoreset_mode="next_step")
+    plain = _env("lander3d", n, "float32", autoreset="next_step", seed=6, max_steps=1000)
+    try:
+        sh.reset()
+        plain.reset()
+        p = _theta("lander3d", 8, 2, env=plain)
+        gr = torch.ones((K, n), dtype=torch.float64, device=plain.device)
+        r1, r2 = sh.rollout_mlp_states(p, K, 8), plain.rollout_mlp_states(p, K, 8)
+        for u, v in zip(r1, r2):
+            assert torch.equal(u, v)
+        g1 = sh.rollout_mlp_vjp(p, r1, gr=gr, hidden=8)
+        g2 = plain.rollout_mlp_vjp(p, r2, gr=gr, hidden=8)
+        assert torch.equal(g1[0], g2[0]) and torch.equal(g1[1], g2[1])
+    finally:
+        sh.close()
+        plain.close()
+
+
+def test_float32_outputs_shapes_dtypes_and_errors():
+    import torch
+    n, K = 300, 6
+    rng = np.random.default_rng(2)
+    env = _env("lander2d", n, "float64")
+    try:
+        x, st = _point(n, rng)
+        state = {"x": x, "status": st}
+        p = _theta("lander2d", 4, 1, env=env)
+        r = env.rollout_mlp_states(p, K, 4, state=state)
+        gr = _dev(rng.standard_normal((K, n)), env)
+        gp64, ga64, g064 = (t.clone() for t in env.rollout_mlp_vjp(p, r, gr=gr, state=state, hidden=4))
+        gp32, ga32, g032 = env.rollout_mlp_vjp(p, r, gr=gr, state=state, hidden=4, dtype=torch.float32)
+        assert ga32.dtype == torch.float32 and g032.dtype == torch.float32 and gp32.dtype == torch.float64
+        assert torch.equal(ga32, ga64.float()) and torch.equal(g032, g064.float())
+        with pytest.raises(ValueError):
+            env.rollout_mlp_states(p.double(), K, 4)
+        with pytest.raises(ValueError):
+            env.rollout_mlp_states(p[:-1], K, 4)
+        with pytest.raises(ValueError):
+            env.rollout_mlp_states(p, K, 65)
+        with pytest.raises(ValueError):
+            env.rollout_mlp_states(p, 0, 4)
+        with pytest.raises(ValueError):
+            env.rollout_mlp_states(p, K, 4, offsets=torch.zeros((K, n, 4), device=env.device))
+        with pytest.raises(ValueError):
+            env.rollout_mlp_vjp(p, r, gr=gr, state=state)                      # hidden missing
+        with pytest.raises(ValueError):
+            env.rollout_mlp_vjp(p, r._replace(obs=r.obs[:, :-1]), gr=gr, state=state, hidden=4)
+        with pytest.raises(ValueError):
+            env.rollout_mlp_vjp(p, r, gr=gr[:-1], state=state, hidden=4)
+    finally:
+        env.close()
+
+
+def test_large_offsets_past_4_gib():
+    import torch
+    n, K = 1 << 20, 48
+    assert K * n * 12 * 8 > 4 << 30
+    env, twin = _env("lander3d", n, "float32", seed=9), _env("lander3d", n, "float32", seed=9)
+    try:
+        env.reset()
+        twin.reset()
+        p = _theta("lander3d", 8, 3, env=env)
+        r = env.rollout_mlp_states(p, K, 8)
+        for k in range(K):
+            twin.step(r.actions[k].clone())
+        s = twin.get_state(only=("x", "status"))
+        assert np.array_equal(to_np(r.x[K - 1, n - 1]), s["x"][:, n - 1])
+        assert np.array_equal(to_np(r.obs[K - 1, n - 1]), _obs_of("lander3d", to_np(r.x[K - 2, n - 1])))
+        gp, ga, _ = env.rollout_mlp_vjp(p, r, gr=torch.ones((K, n), dtype=torch.float64, device=env.device), hidden=8)
+        assert bool(torch.isfinite(ga[K - 1, n - 1]).all()) and bool(torch.isfinite(ga[0, n - 1]).all())
+        assert bool(torch.isfinite(gp).all())
+    finally:
+        env.close()
+        twin.close()

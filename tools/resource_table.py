@@ -1,0 +1,41 @@
+"""One line per kernel from hipcc's -Rpass-analysis=kernel-resource-usage remarks (make report): name | SGPRs | VGPRs |
+AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_resources.txt.
+
+    python3 tools/resource_table.py remarks.txt > profiles/rollout_mlp_resources.txt"""
+import re
+import sys
+
+FIELDS = (("TotalSGPRs", "SGPRs"), ("VGPRs", "VGPRs"), ("AGPRs", "AGPRs"), ("ScratchSize [bytes/lane]", "scratch"),
+          ("Occupancy [waves/SIMD]", "waves"), ("LDS Size [bytes/block]", "LDS"))
+
+
+def table(lines):
+    rows, cur = [], None
+    for line in lines:
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = {"name": re.sub(r"^_ZN2cs12_GLOBAL__N_1\d+", "", m.group(1)).split("EvNS_")[0]}
+            rows.append(cur)
+            continue
+        for key, short in FIELDS:
+            m = re.search(r"remark:\s+%s: (\d+)" % re.escape(key), line)
+            if m and cur is not None:
+                cur[short] = int(m.group(1))
+    return rows
+
+
+def main(path):
+    rows = table(open(path).read().splitlines())
+    print("# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_mlp.hip: the closed-loop forward")
+    print("# rollout_mlp_states_kernel<TASK, MODE> and the backward: rollout_mlp_vjp_kernel<TASK, MODE> (no rotor-gyro term,")
+    print("# held to 2 wavefronts per SIMD) and rollout_mlp_vjp_gyro_kernel<TASK, MODE> (DESIGN.md section 12).")
+    print("# Name | SGPRs | VGPRs | AGPRs | scratch B/lane | waves/SIMD | LDS B/block")
+    for r in rows:
+        print("|".join([r["name"]] + [str(r.get(s, "?")) for _, s in FIELDS]))
+    spill = [r["name"] for r in rows if r.get("scratch", 0) != 0]
+    print("# %d kernels; scratch in %d of them" % (len(rows), len(spill)))
+    return 1 if spill else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1]))
