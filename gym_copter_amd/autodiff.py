@@ -6,7 +6,6 @@ DESIGN.md sections 10 to 12 and INTEGRATION.md."""
 from .vecenv import MlpRollout, Rollout, _torch
 
 _FN = None
-_FN_PARAMS = None
 _FN_MLP = None
 
 
@@ -19,48 +18,16 @@ def _function():
 
     class RolloutFunction(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, actions, x0, env, state):
-            r = env.rollout_states(actions, state)
-            x, reward = r.x.clone(), r.reward.clone()           # (the env's buffers are overwritten by its next call)
-            term, trunc, status = r.terminated.clone(), r.truncated.clone(), r.status.clone()
-            ctx.mark_non_differentiable(term, trunc, status)
-            ctx.save_for_backward(actions, x, status)
-            ctx.env, ctx.state, ctx.want_x0 = env, state, x0 is not None
-            return x, reward, term, trunc, status
-
-        @staticmethod
-        @once_differentiable
-        def backward(ctx, gx, gr, *_):
-            actions, x, status = ctx.saved_tensors
-            env = ctx.env
-            ga, g0 = env.rollout_vjp(actions, Rollout(x, None, None, None, status), gx=gx, gr=gr, state=ctx.state,
-                                     dtype=torch.float64)
-            ga = ga.to(actions.dtype)                           # (a copy: the env's buffer is overwritten next call)
-            g0 = g0.clone() if (ctx.want_x0 and g0 is not None) else None
-            return ga, g0, None, None
-
-    _FN = RolloutFunction
-    return _FN
-
-
-def _function_params():
-    global _FN_PARAMS
-    if _FN_PARAMS is not None:
-        return _FN_PARAMS
-    torch = _torch()
-    from torch.autograd.function import once_differentiable
-
-    class RolloutParamsFunction(torch.autograd.Function):
-        @staticmethod
         def forward(ctx, actions, x0, vehicle, force, env, state):
             r = env.rollout_states(actions, state, vehicle=vehicle)
-            x, reward = r.x.clone(), r.reward.clone()
+            x, reward = r.x.clone(), r.reward.clone()           # (the env's buffers are overwritten by its next call)
             term, trunc, status = r.terminated.clone(), r.truncated.clone(), r.status.clone()
             ctx.mark_non_differentiable(term, trunc, status)
             # (the vehicle is saved, not kept as an attribute: autograd then refuses a backward after an in-place change
             # of it, so the backward may skip re-checking the table the forward's rollout_states checked)
             ctx.save_for_backward(actions, x, status, vehicle)
             ctx.env, ctx.state = env, state
+            ctx.params = vehicle is not None or force is not None
             ctx.want = (x0 is not None, vehicle is not None and vehicle.requires_grad, force is not None)
             return x, reward, term, trunc, status
 
@@ -68,14 +35,20 @@ def _function_params():
         @once_differentiable
         def backward(ctx, gx, gr, *_):
             actions, x, status, vehicle = ctx.saved_tensors
-            ga, g0, gv, gf = ctx.env._vjp(actions, Rollout(x, None, None, None, status), gx, gr, ctx.state,
-                                          torch.float64, params=True, vehicle=vehicle, check_vehicle=False)
+            tape = Rollout(x, None, None, None, status)
+            if ctx.params:                                      # the parameter VJP: g_vehicle and g_force as well
+                ga, g0, gv, gf = ctx.env._vjp(actions, tape, gx, gr, ctx.state, torch.float64, params=True,
+                                              vehicle=vehicle, check_vehicle=False)
+            else:
+                ga, g0 = ctx.env.rollout_vjp(actions, tape, gx=gx, gr=gr, state=ctx.state, dtype=torch.float64)
+                gv = gf = None
             want_x0, want_v, want_f = ctx.want
+            # (copies: the env's buffers are overwritten by its next call)
             return (ga.to(actions.dtype), g0.clone() if (want_x0 and g0 is not None) else None,
                     gv.clone() if want_v else None, gf.clone() if want_f else None, None, None)
 
-    _FN_PARAMS = RolloutParamsFunction
-    return _FN_PARAMS
+    _FN = RolloutFunction
+    return _FN
 
 
 def differentiable_rollout(env, actions, state=None, vehicle=None):
@@ -110,11 +83,7 @@ def differentiable_rollout(env, actions, state=None, vehicle=None):
         if not isinstance(vehicle, torch.Tensor) or vehicle.dtype != torch.float64:
             raise ValueError("vehicle must be a float64 torch tensor of shape (%d, %d)"
                              % (len(env.VEHICLE_ROWS), env.num_envs))
-    if vehicle is None and force is None:
-        out = _function().apply(actions, x0, env, state)
-    else:
-        out = _function_params().apply(actions, x0, vehicle, force, env, state)
-    return Rollout(*out)
+    return Rollout(*_function().apply(actions, x0, vehicle, force, env, state))
 
 
 def _function_mlp():

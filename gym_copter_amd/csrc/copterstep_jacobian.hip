@@ -24,6 +24,7 @@
 #include "dev_physics.h"
 #include "dev_task.h"
 #include "jacobian_tangents.h"
+#include "dev_launch.h"
 
 namespace cs {
 namespace {
@@ -184,29 +185,15 @@ __global__ __launch_bounds__(kBlock) void step_jacobian_kernel(const DevConst c,
   if (valid && io.branch_dev != nullptr) io.branch_dev[i] = (uint8_t)bits;
 }
 
+template <int TASK, int MODE>
+hipError_t jacobian_t(const DevConst& c, const DevState& s, const cs_jacobian_io& io, hipStream_t stream) {
+  hipLaunchKernelGGL((step_jacobian_kernel<TASK, MODE>), dim3(grid_for(s.n)), dim3(kBlock), 0, stream, c, s, io);
+  return hipGetLastError();
+}
+
 hipError_t launch_step_jacobian(int task, int mode, const DevConst& c, const DevState& s, const cs_jacobian_io& io,
                                 hipStream_t stream) {
-  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
-#define CS_JAC_MODE(TASK)                                                                                         \
-  do {                                                                                                            \
-    if (mode == CS_STATE_F32G)                                                                                    \
-      hipLaunchKernelGGL((step_jacobian_kernel<TASK, CS_STATE_F32G>), grid, block, 0, stream, c, s, io);           \
-    else if (mode == CS_STATE_F32_RN)                                                                             \
-      hipLaunchKernelGGL((step_jacobian_kernel<TASK, CS_STATE_F32_RN>), grid, block, 0, stream, c, s, io);         \
-    else                                                                                                          \
-      hipLaunchKernelGGL((step_jacobian_kernel<TASK, CS_STATE_F64>), grid, block, 0, stream, c, s, io);            \
-  } while (0)
-  switch (task) {
-    case CS_TASK_LANDER3D: CS_JAC_MODE(CS_TASK_LANDER3D); break;
-    case CS_TASK_HOVER3D: CS_JAC_MODE(CS_TASK_HOVER3D); break;
-    case CS_TASK_LANDER2D: CS_JAC_MODE(CS_TASK_LANDER2D); break;
-    case CS_TASK_LANDER1D: CS_JAC_MODE(CS_TASK_LANDER1D); break;
-    case CS_TASK_HOVER2D: CS_JAC_MODE(CS_TASK_HOVER2D); break;
-    case CS_TASK_HOVER1D: CS_JAC_MODE(CS_TASK_HOVER1D); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef CS_JAC_MODE
-  return hipGetLastError();
+  CS_DISPATCH(jacobian_t, c, s, io, stream)
 }
 
 }  // namespace

@@ -11,8 +11,8 @@
 // registers for K steps (the pieces of advance(): physics_substeps, the stored-word rounding, judge_step) and writes
 // each step's state row through the LDS.  The backward kernel sweeps k = K .. 1 with the adjoint in registers; each
 // step's primal is recomputed from the caller's tape (the forward's x and status rows), the substep start states from
-// the step's start (O(substeps^2) calls).  The pieces the closed-loop rollouts share are in rollout_step.h.  DESIGN.md
-// section 10.
+// the step's start (O(substeps^2) calls).  Both loops are rollout_sweep.h's, shared with the closed-loop rollouts;
+// the kernels here are wrappers that pick the open-loop actions and the sweep's extension.  DESIGN.md sections 10, 11.
 #include <string>
 
 #include "copterstep_jacobian.h"
@@ -29,6 +29,8 @@
 #include "jacobian_tangents.h"
 #include "rollout_adjoint.h"
 #include "rollout_step.h"
+#include "rollout_sweep.h"
+#include "dev_launch.h"
 
 namespace cs {
 namespace {
@@ -36,498 +38,70 @@ namespace {
 template <int TASK, int MODE>
 __global__ __launch_bounds__(kBlock) void rollout_states_kernel(const DevConst c, const DevState s,
                                                                 const cs_rollout_io io) {
-  constexpr int A = task_act_dim(TASK);
   __shared__ __attribute__((aligned(16))) double xrow[kBlock * 12];  // 6 KiB: the wavefront's state rows of a step
-  const int lane = threadIdx.x;
-  const uint32_t tile_index = blockIdx.x;
-  const uint32_t i = tile_index * kBlock + threadIdx.x;
-  const uint32_t n = s.n;
-  const uint32_t env0 = i - lane;
-  const bool valid = i < n;
-  const bool whole = env0 + (uint32_t)kWave <= n;
-
-  Coef q = uniform_coef(c);
-  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, valid ? i : 0u);
-  // the stored env, decoded as step_many_kernel decodes it (its counters are the rollout's in both start forms)
-  using TILE = TileIO<MODE>;
-  const TILE tile(s, tile_index, lane);
-  Env<MODE> e;
-  unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
-  resolve_episode<MODE>(c, tile, e);
-  double px, py, pz;
-  if (io.start_x_dev != nullptr) {
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
-    e.reset_pending = false;
-  } else {
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-  }
-
-  const float* act_lane = io.actions_dev + (size_t)(valid ? i : 0u) * A;
-  const size_t act_step = (size_t)n * A;
-#pragma clang loop unroll(disable)
-  for (int k = 0; k < io.num_steps; ++k) {
-    const float4 act = load_action_at<TASK>(act_lane);
-    act_lane += act_step;
-    const bool resetting = e.reset_pending;
-    double reward;
-    bool term, trunc;
-    rollout_step<TASK, MODE>(c, q, e, act, px, py, pz, reward, term, trunc);
-    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
-      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-    } else if (!e.pend) {
-      px = py = pz = -0.0;
-    }
-
-    const size_t row = (size_t)k * n;  // 64-bit: K x N x 12 doubles pass 4 GiB at 1 M envs
-    if (io.x_dev != nullptr) {
-      if (whole) {  // 64 rows of 96 B through the LDS: six 1 KiB stores of 16 B per lane
-#pragma unroll
-        for (int j = 0; j < 12; j += 2)
-          *reinterpret_cast<double2*>(xrow + lane * 12 + j) = make_double2(e.x[j], e.x[j + 1]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const double2* src = reinterpret_cast<const double2*>(xrow);
-        double2* dst = reinterpret_cast<double2*>(io.x_dev + (row + env0) * 12);
-#pragma unroll
-        for (int v = 0; v < 6; ++v) dst[v * kWave + lane] = src[v * kWave + lane];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      } else if (valid) {
-        double* dst = io.x_dev + (row + i) * 12;
-#pragma unroll
-        for (int j = 0; j < 12; ++j) dst[j] = e.x[j];
-      }
-    }
-    if (valid) {
-      if (io.reward_dev != nullptr) io.reward_dev[row + i] = reward;
-      if (io.terminated_dev != nullptr) io.terminated_dev[row + i] = term ? 1 : 0;
-      if (io.truncated_dev != nullptr) io.truncated_dev[row + i] = trunc ? 1 : 0;
-      if (io.status_dev != nullptr) io.status_dev[row + i] = (uint8_t)e.fs;
-    }
-  }
+  rollout_forward<TASK, MODE>(c, s, io, xrow, OpenLoop<TASK>{io.actions_dev, 0});
 }
 
 template <int TASK, int MODE, bool GYRO>
 __global__ __launch_bounds__(kBlock) void rollout_vjp_kernel(const DevConst c, const DevState s,
                                                              const cs_rollout_io io) {
-  constexpr int A = task_act_dim(TASK);
-  const int lane = threadIdx.x;
-  const uint32_t tile_index = blockIdx.x;
-  const uint32_t i = tile_index * kBlock + threadIdx.x;
-  const uint32_t n = s.n;
-  const bool valid = i < n;
-  const uint32_t ii = valid ? i : 0u;  // (padding lanes recompute env 0's steps and store nothing)
-  const int K = io.num_steps;
-  const bool f32out = io.out_dtype == CS_JAC_F32;
-
-  Coef q = uniform_coef(c);
-  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
-  double lam[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) lam[k] = 0.0;
-  double ga[4];
-
-  // ---- steps K-1 .. 2: starts from the tape, the next step's inputs fetched while this one computes ----
-  StepIn cur;
-  if (K > 1) load_tape_step<TASK>(io, n, ii, K - 1, cur);
-#pragma clang loop unroll(disable)
-  for (int k = K - 1; k >= 2; --k) {
-    StepIn nxt;  // (the earlier step's tape row and action, in flight while this step computes)
-    load_tape_step<TASK>(io, n, ii, k - 1, nxt);
-    const double gr = add_cotangents(io, (size_t)k * n, ii, lam);
-    const double* tape_next = nullptr;
-#ifdef CS_DEBUG_ROLLOUT
-    tape_next = io.x_dev + ((size_t)k * n + ii) * 12;
-#endif
-    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, -0.0, -0.0, -0.0, false, true, false, tape_next, lam, ga);
-    if (valid && io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, (size_t)k * n, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, (size_t)k * n, i, ga);
-    }
-    cur = nxt;
-  }
-
-  // ---- step 1 (peeled: the loop's steps have no perturbation) ----
-  // A stored-start lane with a NEXT_STEP reset pending resets in step 0, and the new episode's perturbation (the draw
-  // step() makes) enters the first call of step 1: its recompute needs it, or its x' is not the tape's.  Every other
-  // perturbation is consumed in step 0 or only ever meets calls that do not integrate.
-  if (K > 1) {
-    double px = -0.0, py = -0.0, pz = -0.0;
-    if (io.start_x_dev == nullptr) {
-      using TILE = TileIO<MODE>;
-      const TILE tile(s, tile_index, lane);
-      Env<MODE> e;
-      unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
-      if (e.reset_pending) {  // (rollout_step's masked reset, then the forward's draw for the new episode)
-        resolve_episode<MODE>(c, tile, e);
-        next_episode<MODE, true>(e);
-        pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, true, false, px, py, pz);
-      }
-    }
-    const double gr = add_cotangents(io, (size_t)n, ii, lam);
-    const double* tape_next = nullptr;
-#ifdef CS_DEBUG_ROLLOUT
-    tape_next = io.x_dev + ((size_t)n + ii) * 12;
-#endif
-    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, px, py, pz, false, true, false, tape_next, lam, ga);
-    if (valid && io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, (size_t)n, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, (size_t)n, i, ga);
-    }
-  }
-
-  // ---- step 0: from the start point, decoded as the forward decoded it ----
-  StepIn in;
-  double px, py, pz;
-  bool resetting = false, prev_diff = false, prev_none = false;
-  if (io.start_x_dev != nullptr) {
-    bool pend;
-    double prev_sh;
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, in.x, in.fs, pend, px, py, pz, prev_sh);
-    prev_diff = io.start_prev_shaping_dev == nullptr;
-    prev_none = prev_sh != prev_sh;
-  } else {
-    using TILE = TileIO<MODE>;
-    const TILE tile(s, tile_index, lane);
-    Env<MODE> e;
-    unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
-    resolve_episode<MODE>(c, tile, e);
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) in.x[k] = e.x[k];
-    in.fs = e.fs;
-    resetting = e.reset_pending;
-    prev_none = e.prev_sh != e.prev_sh;
-  }
-  in.act = load_action_at<TASK>(io.actions_dev + (size_t)ii * A);
-  const double gr0 = add_cotangents(io, 0, ii, lam);
-  const double* tape_next = nullptr;
-#ifdef CS_DEBUG_ROLLOUT
-  if (!resetting) tape_next = io.x_dev + (size_t)ii * 12;  // (a resetting step is not recomputed: its gradient is 0)
-#endif
-  step_adjoint<TASK, MODE, GYRO>(c, q, in, gr0, px, py, pz, resetting, prev_diff, prev_none, tape_next, lam, ga);
-  if (valid) {
-    if (io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, 0, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, 0, i, ga);
-    }
-    if (io.g_x0_dev != nullptr) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        if (f32out)
-          reinterpret_cast<float*>(io.g_x0_dev)[(size_t)k * n + i] = (float)lam[k];
-        else
-          reinterpret_cast<double*>(io.g_x0_dev)[(size_t)k * n + i] = lam[k];
-      }
-    }
-  }
-}
-
-// Where the parameter-gradient backward writes (cs_rollout_vjp_ex): g_coef [kCoefRows, N] float64 (the adjoints of
-// Coef's rows, for unfold_vehicle_kernel), g_force [3, N] (newtons; float32 when f32) or nullptr.
-struct ParamGradOut {
-  double* g_coef;
-  void* g_force;
-  uint32_t f32;
-};
-
-// pending_perturbation() with the force kept: f = the pending force in newtons (0 when none), (px, py, pz) = f two_inv_M
-// with the same bits as pending_perturbation's (f x 1.0 is f, and -0.0 x 1.0 is -0.0)
-template <int MODE, class TILE>
-__device__ __forceinline__ void pending_force(const DevConst& c, const Coef& q, const TILE& tile, uint32_t i,
-                                              uint32_t episode, uint32_t ep_far, bool pend, bool expl, double (&f)[3],
-                                              double& px, double& py, double& pz) {
-  Coef unit = q;
-  unit.two_inv_M = 1.0;
-  pending_perturbation<MODE, true>(c, unit, tile, i, episode, ep_far, pend, expl, f[0], f[1], f[2]);
-  px = f[0] * q.two_inv_M;
-  py = f[1] * q.two_inv_M;
-  pz = f[2] * q.two_inv_M;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) f[j] = pend ? f[j] : 0.0;
-}
-
-// rollout_vjp_kernel's sweep with the coefficient adjoints (acc = this lane's LDS columns, po = where the coefficient
-// and force adjoints go); instantiated with PARAM = true only.  With PARAM = false it is that kernel's sweep, which
-// keeps its own text because calling this function from it, though equivalent, changed its instruction schedule
-// (profiles/rollout_param_grad_isa.txt).  The two copies must change together: ANY fix to the plain sweep in
-// rollout_vjp_kernel must be mirrored here, and the other way round (the bit-identity of g_actions / g_x0 between the
-// two, tests/test_gpu_rollout_param_grad.py, catches a copy that drifts).
-template <int TASK, int MODE, bool GYRO, bool PARAM>
-__device__ __forceinline__ void rollout_vjp_body(const DevConst& c, const DevState& s, const cs_rollout_io& io,
-                                                 const ParamGradOut& po, double* acc) {
-  constexpr int A = task_act_dim(TASK);
-  const int lane = threadIdx.x;
-  const uint32_t tile_index = blockIdx.x;
-  const uint32_t i = tile_index * kBlock + threadIdx.x;
-  const uint32_t n = s.n;
-  const bool valid = i < n;
-  const uint32_t ii = valid ? i : 0u;  // (padding lanes recompute env 0's steps and store nothing)
-  const int K = io.num_steps;
-  const bool f32out = io.out_dtype == CS_JAC_F32;
-
-  Coef q = uniform_coef(c);
-  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
-  double lam[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) lam[k] = 0.0;
-  double ga[4];
-  if constexpr (PARAM) {
-#pragma unroll
-    for (int j = 0; j < 2 * kAccRows; ++j) acc[j * kBlock] = 0.0;
-  }
-
-  // ---- steps K-1 .. 2: starts from the tape, the next step's inputs fetched while this one computes ----
-  StepIn cur;
-  if (K > 1) load_tape_step<TASK>(io, n, ii, K - 1, cur);
-#pragma clang loop unroll(disable)
-  for (int k = K - 1; k >= 2; --k) {
-    StepIn nxt;  // (the earlier step's tape row and action, in flight while this step computes)
-    load_tape_step<TASK>(io, n, ii, k - 1, nxt);
-    const double gr = add_cotangents(io, (size_t)k * n, ii, lam);
-    const double* tape_next = nullptr;
-#ifdef CS_DEBUG_ROLLOUT
-    tape_next = io.x_dev + ((size_t)k * n + ii) * 12;
-#endif
-    step_adjoint<TASK, MODE, GYRO, PARAM>(c, q, cur, gr, -0.0, -0.0, -0.0, false, true, false, tape_next, lam, ga,
-                                          acc);
-    if (valid && io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, (size_t)k * n, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, (size_t)k * n, i, ga);
-    }
-    cur = nxt;
-  }
-
-  // ---- step 1 (peeled: the loop's steps have no perturbation) ----
-  // A stored-start lane with a NEXT_STEP reset pending resets in step 0, and the new episode's perturbation (the draw
-  // step() makes) enters the first call of step 1: its recompute needs it, or its x' is not the tape's.  Every other
-  // perturbation is consumed in step 0 or only ever meets calls that do not integrate.
-  if (K > 1) {
-    double px = -0.0, py = -0.0, pz = -0.0;
-    double f1[3] = {0.0, 0.0, 0.0};  // (PARAM) that draw in newtons: px = f1[0] two_inv_M
-    if (io.start_x_dev == nullptr) {
-      using TILE = TileIO<MODE>;
-      const TILE tile(s, tile_index, lane);
-      Env<MODE> e;
-      unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
-      if (e.reset_pending) {  // (rollout_step's masked reset, then the forward's draw for the new episode)
-        resolve_episode<MODE>(c, tile, e);
-        next_episode<MODE, true>(e);
-        if constexpr (PARAM) {
-          pending_force<MODE>(c, q, tile, i, e.episode, e.ep_far, true, false, f1, px, py, pz);
-        } else {
-          pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, true, false, px, py, pz);
-        }
-      }
-    }
-    const double gr = add_cotangents(io, (size_t)n, ii, lam);
-    const double* tape_next = nullptr;
-#ifdef CS_DEBUG_ROLLOUT
-    tape_next = io.x_dev + ((size_t)n + ii) * 12;
-#endif
-    step_adjoint<TASK, MODE, GYRO, PARAM>(c, q, cur, gr, px, py, pz, false, true, false, tape_next, lam, ga, acc);
-    if constexpr (PARAM) {  // the new episode's draw is a constant, 2 / M multiplies it: only two_inv_M's adjoint
-      acc[8 * kBlock] += (acc[(kAccPe + 0) * kBlock] * f1[0] + acc[(kAccPe + 1) * kBlock] * f1[1]) +
-                         acc[(kAccPe + 2) * kBlock] * f1[2];
-    }
-    if (valid && io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, (size_t)n, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, (size_t)n, i, ga);
-    }
-  }
-
-  // ---- step 0: from the start point, decoded as the forward decoded it ----
-  StepIn in;
-  double px, py, pz;
-  double f0[3] = {0.0, 0.0, 0.0};  // (PARAM) the start's pending force in newtons: px = f0[0] two_inv_M
-  bool fpend = false;              // (PARAM) a force is pending at the start: only then has it a gradient
-  bool resetting = false, prev_diff = false, prev_none = false;
-  if (io.start_x_dev != nullptr) {
-    bool pend;
-    double prev_sh;
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, in.x, in.fs, pend, px, py, pz, prev_sh);
-    prev_diff = io.start_prev_shaping_dev == nullptr;
-    prev_none = prev_sh != prev_sh;
-    if constexpr (PARAM) {
-      fpend = pend && valid;
-      if (fpend) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) f0[j] = io.start_force_dev[(size_t)j * n + i];
-      }
-    }
-  } else {
-    using TILE = TileIO<MODE>;
-    const TILE tile(s, tile_index, lane);
-    Env<MODE> e;
-    unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
-    resolve_episode<MODE>(c, tile, e);
-    if constexpr (PARAM) {
-      pending_force<MODE>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, f0, px, py, pz);
-      fpend = e.pend;
-    } else {
-      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-    }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) in.x[k] = e.x[k];
-    in.fs = e.fs;
-    resetting = e.reset_pending;
-    prev_none = e.prev_sh != e.prev_sh;
-  }
-  in.act = load_action_at<TASK>(io.actions_dev + (size_t)ii * A);
-  const double gr0 = add_cotangents(io, 0, ii, lam);
-  const double* tape_next = nullptr;
-#ifdef CS_DEBUG_ROLLOUT
-  if (!resetting) tape_next = io.x_dev + (size_t)ii * 12;  // (a resetting step is not recomputed: its gradient is 0)
-#endif
-  // (PARAM) step 0 accumulates into the second set of rows, added unless the step is a NEXT_STEP reset: that step
-  // computes nothing (dt = 0), but its pre-reset state need not be finite
-  step_adjoint<TASK, MODE, GYRO, PARAM>(c, q, in, gr0, px, py, pz, resetting, prev_diff, prev_none, tape_next, lam,
-                                        ga, PARAM ? acc + kAccRows * kBlock : nullptr);
-  if constexpr (PARAM) {
-    double* acc0 = acc + kAccRows * kBlock;
-    // the perturbation's adjoint, where there is a perturbation: none pending (consumed, or an explicit start without
-    // start_force_dev) and a NEXT_STEP reset (its new draw is a constant) give a force gradient of exactly 0
-    const bool live = fpend && !resetting;
-    const double pe[3] = {live ? acc0[(kAccPe + 0) * kBlock] : 0.0, live ? acc0[(kAccPe + 1) * kBlock] : 0.0,
-                          live ? acc0[(kAccPe + 2) * kBlock] : 0.0};
-    acc[8 * kBlock] += (pe[0] * f0[0] + pe[1] * f0[1]) + pe[2] * f0[2];
-    if (valid) {  // the coefficient adjoints [11, N] for the unfold kernel, the force's [3, N] in the caller's dtype
-#pragma unroll
-      for (int j = 0; j < kCoefRows; ++j)
-        po.g_coef[(size_t)j * n + i] = resetting ? acc[j * kBlock] : acc[j * kBlock] + acc0[j * kBlock];
-      if (po.g_force != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          const double g = q.two_inv_M * pe[j];
-          if (po.f32)
-            reinterpret_cast<float*>(po.g_force)[(size_t)j * n + i] = (float)g;
-          else
-            reinterpret_cast<double*>(po.g_force)[(size_t)j * n + i] = g;
-        }
-      }
-    }
-  }
-  if (valid) {
-    if (io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, 0, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, 0, i, ga);
-    }
-    if (io.g_x0_dev != nullptr) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        if (f32out)
-          reinterpret_cast<float*>(io.g_x0_dev)[(size_t)k * n + i] = (float)lam[k];
-        else
-          reinterpret_cast<double*>(io.g_x0_dev)[(size_t)k * n + i] = lam[k];
-      }
-    }
-  }
+  rollout_vjp_sweep<TASK, MODE, GYRO>(c, s, io, SweepPlain{});
 }
 
 // The parameter-gradient backward (cs_rollout_vjp_ex): the plain sweep plus the coefficient adjoints, accumulated over
 // the steps in lane-private LDS columns, read-modify-written where each term arises, not in registers: the plain sweep
-// already holds 231-255 VGPRs (profiles/rollout_param_grad_resources.txt).  Two sets of kAccRows rows (step 0 has its
+// already holds 229-255 VGPRs (profiles/rollout_grad_resources.txt).  Two sets of kAccRows rows (step 0 has its
 // own), 2 x 14 x 8 B x 64 lanes = 14 KiB per workgroup.  The sweep still needs 243-255 VGPRs + up to 44 AGPRs: 1
 // wavefront per SIMD in 35 of 36 instantiations, where the plain kernel has 2.
 template <int TASK, int MODE, bool GYRO>
 __global__ __launch_bounds__(kBlock) void rollout_vjp_param_kernel(const DevConst c, const DevState s,
                                                                    const cs_rollout_io io, const ParamGradOut po) {
   __shared__ double acc[2 * kAccRows * kBlock];
-  rollout_vjp_body<TASK, MODE, GYRO, true>(c, s, io, po, acc + threadIdx.x);
+  rollout_vjp_sweep<TASK, MODE, GYRO>(c, s, io, SweepParam{po, acc + threadIdx.x});
 }
 
-#define CS_RG_TASKS(M)                           \
-  switch (task) {                                \
-    case CS_TASK_LANDER3D: M(CS_TASK_LANDER3D); break; \
-    case CS_TASK_HOVER3D: M(CS_TASK_HOVER3D); break;   \
-    case CS_TASK_LANDER2D: M(CS_TASK_LANDER2D); break; \
-    case CS_TASK_LANDER1D: M(CS_TASK_LANDER1D); break; \
-    case CS_TASK_HOVER2D: M(CS_TASK_HOVER2D); break;   \
-    case CS_TASK_HOVER1D: M(CS_TASK_HOVER1D); break;   \
-    default: return hipErrorInvalidValue;        \
-  }
+// the launchers of one (task, mode) instantiation (CS_DISPATCH picks it), the backward's split on the rotor-gyro term
+template <int TASK, int MODE>
+hipError_t states_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, hipStream_t stream) {
+  hipLaunchKernelGGL((rollout_states_kernel<TASK, MODE>), dim3(grid_for(s.n)), dim3(kBlock), 0, stream, c, s, io);
+  return hipGetLastError();
+}
+
+template <int TASK, int MODE>
+hipError_t vjp_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, hipStream_t stream) {
+  const dim3 grid(grid_for(s.n)), block(kBlock);
+  if (c.gyro)
+    hipLaunchKernelGGL((rollout_vjp_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io);
+  else
+    hipLaunchKernelGGL((rollout_vjp_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io);
+  return hipGetLastError();
+}
+
+template <int TASK, int MODE>
+hipError_t vjp_param_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const ParamGradOut& po,
+                       hipStream_t stream) {
+  const dim3 grid(grid_for(s.n)), block(kBlock);
+  if (c.gyro)
+    hipLaunchKernelGGL((rollout_vjp_param_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, po);
+  else
+    hipLaunchKernelGGL((rollout_vjp_param_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, po);
+  return hipGetLastError();
+}
 
 hipError_t launch_rollout_states(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
                                  hipStream_t stream) {
-  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
-#define CS_RS_MODE(TASK)                                                                                          \
-  do {                                                                                                            \
-    if (mode == CS_STATE_F32G)                                                                                    \
-      hipLaunchKernelGGL((rollout_states_kernel<TASK, CS_STATE_F32G>), grid, block, 0, stream, c, s, io);          \
-    else if (mode == CS_STATE_F32_RN)                                                                             \
-      hipLaunchKernelGGL((rollout_states_kernel<TASK, CS_STATE_F32_RN>), grid, block, 0, stream, c, s, io);        \
-    else                                                                                                          \
-      hipLaunchKernelGGL((rollout_states_kernel<TASK, CS_STATE_F64>), grid, block, 0, stream, c, s, io);           \
-  } while (0)
-  CS_RG_TASKS(CS_RS_MODE)
-#undef CS_RS_MODE
-  return hipGetLastError();
+  CS_DISPATCH(states_t, c, s, io, stream)
 }
 
 hipError_t launch_rollout_vjp(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
                               hipStream_t stream) {
-  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
-#define CS_RV_GYRO(TASK, MODE)                                                                                    \
-  do {                                                                                                            \
-    if (c.gyro)                                                                                                   \
-      hipLaunchKernelGGL((rollout_vjp_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io);               \
-    else                                                                                                          \
-      hipLaunchKernelGGL((rollout_vjp_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io);              \
-  } while (0)
-#define CS_RV_MODE(TASK)                                                                                          \
-  do {                                                                                                            \
-    if (mode == CS_STATE_F32G)                                                                                    \
-      CS_RV_GYRO(TASK, CS_STATE_F32G);                                                                            \
-    else if (mode == CS_STATE_F32_RN)                                                                             \
-      CS_RV_GYRO(TASK, CS_STATE_F32_RN);                                                                          \
-    else                                                                                                          \
-      CS_RV_GYRO(TASK, CS_STATE_F64);                                                                             \
-  } while (0)
-  CS_RG_TASKS(CS_RV_MODE)
-#undef CS_RV_MODE
-#undef CS_RV_GYRO
-  return hipGetLastError();
+  CS_DISPATCH(vjp_t, c, s, io, stream)
 }
 
 hipError_t launch_rollout_vjp_param(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
                                     const ParamGradOut& po, hipStream_t stream) {
-  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
-#define CS_RP_GYRO(TASK, MODE)                                                                                    \
-  do {                                                                                                            \
-    if (c.gyro)                                                                                                   \
-      hipLaunchKernelGGL((rollout_vjp_param_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, po);     \
-    else                                                                                                          \
-      hipLaunchKernelGGL((rollout_vjp_param_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, po);    \
-  } while (0)
-#define CS_RP_MODE(TASK)                                                                                          \
-  do {                                                                                                            \
-    if (mode == CS_STATE_F32G)                                                                                    \
-      CS_RP_GYRO(TASK, CS_STATE_F32G);                                                                            \
-    else if (mode == CS_STATE_F32_RN)                                                                             \
-      CS_RP_GYRO(TASK, CS_STATE_F32_RN);                                                                          \
-    else                                                                                                          \
-      CS_RP_GYRO(TASK, CS_STATE_F64);                                                                             \
-  } while (0)
-  CS_RG_TASKS(CS_RP_MODE)
-#undef CS_RP_MODE
-#undef CS_RP_GYRO
-  return hipGetLastError();
+  CS_DISPATCH(vjp_param_t, c, s, io, po, stream)
 }
-#undef CS_RG_TASKS
 
 // ---------------------------------------------------------------------------------------------------------------------
 // vehicle tables on the device

@@ -8,8 +8,8 @@
 //
 // One lane per env on the tile layout of the step kernels, as copterstep_rollout_grad.hip.  The policy's weights are
 // wave-uniform: they are read through the scalar unit (constant address space), streamed one hidden unit at a time, so a
-// lane holds O(OBS + A) policy values whatever the width.  The forward is rollout_states_kernel with the policy in front
-// of each rollout_step; the backward is rollout_vjp_kernel's sweep with the policy's vector-Jacobian product after each
+// lane holds O(OBS + A) policy values whatever the width.  The forward is rollout_states_kernel's loop with the policy
+// in front of each rollout_step; the backward is rollout_sweep.h's reverse sweep with the policy's vector-Jacobian product after each
 // step_adjoint: lambda_o += J_o pi^T g_a, recomputed in float64 from the tape row already in registers.  DESIGN.md
 // section 12.
 #include <string>
@@ -28,6 +28,8 @@
 #include "jacobian_tangents.h"
 #include "rollout_adjoint.h"
 #include "rollout_step.h"
+#include "rollout_sweep.h"
+#include "dev_launch.h"
 
 namespace cs {
 namespace {
@@ -144,6 +146,8 @@ __device__ __forceinline__ float4 motors_of(const float (&a)[A]) {
   else return make_float4(a[0], a[0], a[0], a[0]);
 }
 
+// The closed-loop forward keeps its own loop: rollout_forward (rollout_sweep.h) with the policy as its action source
+// computed the same outputs but ran 1-3 % slower at H = 32 and 64 (profiles/rollout_sweep_refactor_ab.txt).
 template <int TASK, int MODE>
 __global__ __launch_bounds__(kBlock) void rollout_mlp_states_kernel(const DevConst c, const DevState s,
                                                                     const cs_rollout_io io, const MlpArgs m) {
@@ -234,119 +238,16 @@ __global__ __launch_bounds__(kBlock) void rollout_mlp_states_kernel(const DevCon
   }
 }
 
-// rollout_vjp_kernel's sweep (copterstep_rollout_grad.hip) with the policy's VJP after each step's adjoint: io.actions_dev
-// is the action tape here.  g_a (stored as g_actions) is complete when step k's adjoint returns it: every later step's
-// dependence on a_k runs through x_k, whose adjoint lam already holds.
-template <int TASK, int MODE, bool GYRO>
-__device__ __forceinline__ void rollout_mlp_vjp_body(const DevConst& c, const DevState& s, const cs_rollout_io& io,
-                                                     const MlpArgs& m) {
-  constexpr int A = task_act_dim(TASK);
-  const int lane = threadIdx.x;
-  const uint32_t tile_index = blockIdx.x;
-  const uint32_t i = tile_index * kBlock + threadIdx.x;
-  const uint32_t n = s.n;
-  const bool valid = i < n;
-  const uint32_t ii = valid ? i : 0u;  // (padding lanes recompute env 0's steps and store nothing)
-  const int K = io.num_steps;
-  const bool f32out = io.out_dtype == CS_JAC_F32;
-
-  Coef q = uniform_coef(c);
-  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
-  double lam[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) lam[k] = 0.0;
-  double ga[4];
-
-  // ---- steps K-1 .. 2: starts from the tape, the next step's inputs fetched while this one computes ----
-  StepIn cur;
-  if (K > 1) load_tape_step<TASK>(io, n, ii, K - 1, cur);
-#pragma clang loop unroll(disable)
-  for (int k = K - 1; k >= 2; --k) {
-    StepIn nxt;
-    load_tape_step<TASK>(io, n, ii, k - 1, nxt);
-    const double gr = add_cotangents(io, (size_t)k * n, ii, lam);
-    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, -0.0, -0.0, -0.0, false, true, false, nullptr, lam, ga);
-    if (valid && io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, (size_t)k * n, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, (size_t)k * n, i, ga);
-    }
-    mlp_vjp<TASK>(m.params, m.hidden, cur.x, ga, lam);
-    cur = nxt;
+// The closed-loop sweep's extension (rollout_vjp_sweep's EXT): the policy's VJP after each step's adjoint; io.actions_dev
+// is the action tape
+template <int TASK>
+struct SweepPolicy {
+  static constexpr bool kParam = false, kPolicy = true;
+  const MlpArgs& m;
+  __device__ __forceinline__ void vjp(const double (&x)[12], const double (&ga)[4], double (&lam)[12]) const {
+    mlp_vjp<TASK>(m.params, m.hidden, x, ga, lam);
   }
-
-  // ---- step 1 (peeled: a stored start's NEXT_STEP reset draws the perturbation that enters it) ----
-  if (K > 1) {
-    double px = -0.0, py = -0.0, pz = -0.0;
-    if (io.start_x_dev == nullptr) {
-      using TILE = TileIO<MODE>;
-      const TILE tile(s, tile_index, lane);
-      Env<MODE> e;
-      unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
-      if (e.reset_pending) {
-        resolve_episode<MODE>(c, tile, e);
-        next_episode<MODE, true>(e);
-        pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, true, false, px, py, pz);
-      }
-    }
-    const double gr = add_cotangents(io, (size_t)n, ii, lam);
-    step_adjoint<TASK, MODE, GYRO>(c, q, cur, gr, px, py, pz, false, true, false, nullptr, lam, ga);
-    if (valid && io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, (size_t)n, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, (size_t)n, i, ga);
-    }
-    mlp_vjp<TASK>(m.params, m.hidden, cur.x, ga, lam);
-  }
-
-  // ---- step 0: from the start point, decoded as the forward decoded it ----
-  StepIn in;
-  double px, py, pz;
-  bool resetting = false, prev_diff = false, prev_none = false;
-  if (io.start_x_dev != nullptr) {
-    bool pend;
-    double prev_sh;
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, in.x, in.fs, pend, px, py, pz, prev_sh);
-    prev_diff = io.start_prev_shaping_dev == nullptr;
-    prev_none = prev_sh != prev_sh;
-  } else {
-    using TILE = TileIO<MODE>;
-    const TILE tile(s, tile_index, lane);
-    Env<MODE> e;
-    unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
-    resolve_episode<MODE>(c, tile, e);
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) in.x[k] = e.x[k];
-    in.fs = e.fs;
-    resetting = e.reset_pending;
-    prev_none = e.prev_sh != e.prev_sh;
-  }
-  in.act = load_action_at<TASK>(io.actions_dev + (size_t)ii * A);
-  const double gr0 = add_cotangents(io, 0, ii, lam);
-  step_adjoint<TASK, MODE, GYRO>(c, q, in, gr0, px, py, pz, resetting, prev_diff, prev_none, nullptr, lam, ga);
-  // (a resetting lane: ga = lam = 0, so the policy adds nothing -- and its pre-reset state need not be finite)
-  if (!resetting) mlp_vjp<TASK>(m.params, m.hidden, in.x, ga, lam);
-  if (valid) {
-    if (io.g_actions_dev != nullptr) {
-      if (f32out)
-        store_ga<float, A>(io.g_actions_dev, 0, i, ga);
-      else
-        store_ga<double, A>(io.g_actions_dev, 0, i, ga);
-    }
-    if (io.g_x0_dev != nullptr) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        if (f32out)
-          reinterpret_cast<float*>(io.g_x0_dev)[(size_t)k * n + i] = (float)lam[k];
-        else
-          reinterpret_cast<double*>(io.g_x0_dev)[(size_t)k * n + i] = lam[k];
-      }
-    }
-  }
-}
+};
 
 // The backward without the rotor-gyro term is held to 2 wavefronts per SIMD: it fits 256 VGPRs without AGPRs or scratch
 // there, where the allocator left to itself takes 8-16 AGPRs and 1 wavefront.  With the term the same bound spills to
@@ -354,67 +255,43 @@ __device__ __forceinline__ void rollout_mlp_vjp_body(const DevConst& c, const De
 template <int TASK, int MODE>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void rollout_mlp_vjp_kernel(
     const DevConst c, const DevState s, const cs_rollout_io io, const MlpArgs m) {
-  rollout_mlp_vjp_body<TASK, MODE, false>(c, s, io, m);
+  rollout_vjp_sweep<TASK, MODE, false>(c, s, io, SweepPolicy<TASK>{m});
 }
 template <int TASK, int MODE>
 __global__ __launch_bounds__(kBlock) void rollout_mlp_vjp_gyro_kernel(const DevConst c, const DevState s,
                                                                       const cs_rollout_io io, const MlpArgs m) {
-  rollout_mlp_vjp_body<TASK, MODE, true>(c, s, io, m);
+  rollout_vjp_sweep<TASK, MODE, true>(c, s, io, SweepPolicy<TASK>{m});
 }
 
-#define CS_RM_TASKS(M)                                 \
-  switch (task) {                                      \
-    case CS_TASK_LANDER3D: M(CS_TASK_LANDER3D); break; \
-    case CS_TASK_HOVER3D: M(CS_TASK_HOVER3D); break;   \
-    case CS_TASK_LANDER2D: M(CS_TASK_LANDER2D); break; \
-    case CS_TASK_LANDER1D: M(CS_TASK_LANDER1D); break; \
-    case CS_TASK_HOVER2D: M(CS_TASK_HOVER2D); break;   \
-    case CS_TASK_HOVER1D: M(CS_TASK_HOVER1D); break;   \
-    default: return hipErrorInvalidValue;              \
-  }
+// the launchers of one (task, mode) instantiation (CS_DISPATCH picks it), the backward's split on the rotor-gyro term
+template <int TASK, int MODE>
+hipError_t mlp_states_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const MlpArgs& m,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL((rollout_mlp_states_kernel<TASK, MODE>), dim3(grid_for(s.n)), dim3(kBlock), 0, stream, c, s, io,
+                     m);
+  return hipGetLastError();
+}
+
+template <int TASK, int MODE>
+hipError_t mlp_vjp_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const MlpArgs& m,
+                     hipStream_t stream) {
+  const dim3 grid(grid_for(s.n)), block(kBlock);
+  if (c.gyro)
+    hipLaunchKernelGGL((rollout_mlp_vjp_gyro_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);
+  else
+    hipLaunchKernelGGL((rollout_mlp_vjp_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);
+  return hipGetLastError();
+}
 
 hipError_t launch_rollout_mlp_states(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
                                      const MlpArgs& m, hipStream_t stream) {
-  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
-#define CS_MS_MODE(TASK)                                                                                          \
-  do {                                                                                                            \
-    if (mode == CS_STATE_F32G)                                                                                    \
-      hipLaunchKernelGGL((rollout_mlp_states_kernel<TASK, CS_STATE_F32G>), grid, block, 0, stream, c, s, io, m);   \
-    else if (mode == CS_STATE_F32_RN)                                                                             \
-      hipLaunchKernelGGL((rollout_mlp_states_kernel<TASK, CS_STATE_F32_RN>), grid, block, 0, stream, c, s, io, m); \
-    else                                                                                                          \
-      hipLaunchKernelGGL((rollout_mlp_states_kernel<TASK, CS_STATE_F64>), grid, block, 0, stream, c, s, io, m);    \
-  } while (0)
-  CS_RM_TASKS(CS_MS_MODE)
-#undef CS_MS_MODE
-  return hipGetLastError();
+  CS_DISPATCH(mlp_states_t, c, s, io, m, stream)
 }
 
 hipError_t launch_rollout_mlp_vjp(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
                                   const MlpArgs& m, hipStream_t stream) {
-  const dim3 grid((s.n + kBlock - 1) / kBlock), block(kBlock);
-#define CS_MV_GYRO(TASK, MODE)                                                                                    \
-  do {                                                                                                            \
-    if (c.gyro)                                                                                                   \
-      hipLaunchKernelGGL((rollout_mlp_vjp_gyro_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);         \
-    else                                                                                                          \
-      hipLaunchKernelGGL((rollout_mlp_vjp_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);              \
-  } while (0)
-#define CS_MV_MODE(TASK)                                                                                          \
-  do {                                                                                                            \
-    if (mode == CS_STATE_F32G)                                                                                    \
-      CS_MV_GYRO(TASK, CS_STATE_F32G);                                                                            \
-    else if (mode == CS_STATE_F32_RN)                                                                             \
-      CS_MV_GYRO(TASK, CS_STATE_F32_RN);                                                                          \
-    else                                                                                                          \
-      CS_MV_GYRO(TASK, CS_STATE_F64);                                                                             \
-  } while (0)
-  CS_RM_TASKS(CS_MV_MODE)
-#undef CS_MV_MODE
-#undef CS_MV_GYRO
-  return hipGetLastError();
+  CS_DISPATCH(mlp_vjp_t, c, s, io, m, stream)
 }
-#undef CS_RM_TASKS
 
 // the argument blocks, checked before the context: the MLP block's own checks, then check_rollout_io on a copy of io
 // whose actions_dev is the action tape (returned in `out`)

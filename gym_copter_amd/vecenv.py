@@ -883,9 +883,7 @@ class CopterVecEnv(_VectorEnvBase):
         call with the same dtype."""
         self._check_open()
         torch = _torch()
-        dtype = torch.float64 if dtype is None else dtype
-        if dtype not in (torch.float64, torch.float32):
-            raise ValueError("dtype must be torch.float64 or torch.float32")
+        dtype = self._out_dtype(dtype)
         n, ad = self.num_envs, self.action_dim
         a, _ = self._dev_f32(actions, (n, ad), "actions")
         io = _lib.JacobianIO()
@@ -898,18 +896,10 @@ class CopterVecEnv(_VectorEnvBase):
             if unknown or "x" not in state or "status" not in state:
                 raise ValueError("state needs the keys 'x' and 'status' (and optionally 'force'), got %s"
                                  % sorted(state))
-
-            def dev(v, shape, dt, name):
-                t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-                if tuple(t.shape) != shape:
-                    raise ValueError("state[%r] must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-                t = t.to(device=self.device, dtype=dt, non_blocking=True).contiguous()
-                keep.append(t)
-                return t.data_ptr()
-            io.x_dev = dev(state["x"], (12, n), torch.float64, "x")
-            io.status_dev = dev(state["status"], (n,), torch.uint8, "status")
+            io.x_dev = self._state_dev(state["x"], (12, n), torch.float64, "x", keep)
+            io.status_dev = self._state_dev(state["status"], (n,), torch.uint8, "status", keep)
             if state.get("force") is not None:
-                io.force_dev = dev(state["force"], (3, n), torch.float64, "force")
+                io.force_dev = self._state_dev(state["force"], (3, n), torch.float64, "force", keep)
         cache = getattr(self, "_jac_out", None)
         if cache is None:
             cache = self._jac_out = {}
@@ -951,21 +941,79 @@ class CopterVecEnv(_VectorEnvBase):
             if unknown or "x" not in state or "status" not in state:
                 raise ValueError("state needs the keys 'x' and 'status' (and optionally 'force', 'prev_shaping'), got %s"
                                  % sorted(state))
-
-            def dev(v, shape, dt, name):
-                t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-                if tuple(t.shape) != shape:
-                    raise ValueError("state[%r] must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-                t = t.detach().to(device=self.device, dtype=dt, non_blocking=True).contiguous()
-                keep.append(t)
-                return t.data_ptr()
-            io.start_x_dev = dev(state["x"], (12, n), torch.float64, "x")
-            io.start_status_dev = dev(state["status"], (n,), torch.uint8, "status")
+            io.start_x_dev = self._state_dev(state["x"], (12, n), torch.float64, "x", keep)
+            io.start_status_dev = self._state_dev(state["status"], (n,), torch.uint8, "status", keep)
             if state.get("force") is not None:
-                io.start_force_dev = dev(state["force"], (3, n), torch.float64, "force")
+                io.start_force_dev = self._state_dev(state["force"], (3, n), torch.float64, "force", keep)
             if state.get("prev_shaping") is not None:
-                io.start_prev_shaping_dev = dev(state["prev_shaping"], (n,), torch.float64, "prev_shaping")
+                io.start_prev_shaping_dev = self._state_dev(state["prev_shaping"], (n,), torch.float64, "prev_shaping",
+                                                            keep)
         return io, K, keep
+
+    def _state_dev(self, v, shape, dt, name, keep):
+        """state[name] of step_jacobian or a rollout as a contiguous device tensor of dtype dt, kept alive in `keep`;
+        returns its data pointer."""
+        torch = _torch()
+        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+        if tuple(t.shape) != shape:
+            raise ValueError("state[%r] must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+        t = t.detach().to(device=self.device, dtype=dt, non_blocking=True).contiguous()
+        keep.append(t)
+        return t.data_ptr()
+
+    @staticmethod
+    def _out_dtype(dtype):
+        """The dtype of a derivative's outputs: torch.float64 (None) or torch.float32."""
+        torch = _torch()
+        dtype = torch.float64 if dtype is None else dtype
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("dtype must be torch.float64 or torch.float32")
+        return dtype
+
+    def _check_tape(self, source, *tapes):
+        """A backward's tape, (tensor, name, shape, dtype) each: contiguous device tensors as `source` returned them."""
+        torch = _torch()
+        for t, name, shape, dt in tapes:
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("%s must be a device tensor of shape %s (%s' result)" % (name, shape, source))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, self.device))
+
+    def _cotangents(self, io, gx, gr, K, keep):
+        """io.gx_dev and io.gr_dev of a backward: gx [K,N,12] and gr [K,N] (None: zero) as float64 device tensors, kept
+        alive in `keep`."""
+        torch = _torch()
+        n = self.num_envs
+
+        def cot(v, shape, name):
+            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
+            if not t.dtype.is_floating_point:
+                raise ValueError("%s must be a floating-point array" % name)
+            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+        if gx is not None:
+            io.gx_dev = cot(gx, (K, n, 12), "gx")
+        if gr is not None:
+            io.gr_dev = cot(gr, (K, n), "gr")
+
+    def _grad_out(self, io, prefix, K, dtype, explicit):
+        """A backward's outputs, set in io: g_actions [K,N,A] and, for an explicit start, g_x0 [12,N] (else None) -- buffers
+        of this env cached under `prefix` (the plain and the closed-loop calls keep their own)."""
+        torch = _torch()
+        n, dev = self.num_envs, self.device
+        ga = self._rollout_cache((prefix + "g_actions", K, dtype),
+                                 lambda: torch.empty((K, n, self.action_dim), dtype=dtype, device=dev))
+        io.g_actions_dev = ga.data_ptr()
+        g0 = None
+        if explicit:
+            g0 = self._rollout_cache((prefix + "g_x0", dtype), lambda: torch.empty((12, n), dtype=dtype, device=dev))
+            io.g_x0_dev = g0.data_ptr()
+        return ga, g0
 
     def _rollout_cache(self, key, make):
         cache = getattr(self, "_rollout_out", None)
@@ -1073,49 +1121,23 @@ class CopterVecEnv(_VectorEnvBase):
     def _vjp(self, actions, rollout, gx, gr, state, dtype, params=False, vehicle=None, check_vehicle=True):
         self._check_open()
         torch = _torch()
-        dtype = torch.float64 if dtype is None else dtype
-        if dtype not in (torch.float64, torch.float32):
-            raise ValueError("dtype must be torch.float64 or torch.float32")
+        dtype = self._out_dtype(dtype)
         io, K, keep = self._rollout_io(actions, state)
-        n, ad = self.num_envs, self.action_dim
+        n = self.num_envs
         io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
         x, status = getattr(rollout, "x", None), getattr(rollout, "status", None)
-        for t, name, shape, dt in ((x, "rollout.x", (K, n, 12), torch.float64),
-                                   (status, "rollout.status", (K, n), torch.uint8)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("%s must be a device tensor of shape %s (rollout_states' result)" % (name, shape))
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, self.device))
+        self._check_tape("rollout_states", (x, "rollout.x", (K, n, 12), torch.float64),
+                         (status, "rollout.status", (K, n), torch.uint8))
         io.x_dev, io.status_dev = x.data_ptr(), status.data_ptr()
-
-        def cot(v, shape, name):
-            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-            if not (t.dtype.is_floating_point):
-                raise ValueError("%s must be a floating-point array" % name)
-            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        if gx is not None:
-            io.gx_dev = cot(gx, (K, n, 12), "gx")
-        if gr is not None:
-            io.gr_dev = cot(gr, (K, n), "gr")
-        dev = self.device
-        ga = self._rollout_cache(("g_actions", K, dtype), lambda: torch.empty((K, n, ad), dtype=dtype, device=dev))
-        io.g_actions_dev = ga.data_ptr()
-        g0 = None
-        if state is not None:
-            g0 = self._rollout_cache(("g_x0", dtype), lambda: torch.empty((12, n), dtype=dtype, device=dev))
-            io.g_x0_dev = g0.data_ptr()
+        self._cotangents(io, gx, gr, K, keep)
+        ga, g0 = self._grad_out(io, "", K, dtype, state is not None)
         if not params:
             with torch.cuda.device(self.device):
                 _lib.check(self._lib.cs_rollout_vjp(self._ctx, C.byref(io), self._stream()))
             self._keep = keep
             return ga, g0
         pio = self._param_io(vehicle, keep, dtype, check=check_vehicle)
+        dev = self.device
         gv = self._rollout_cache(("g_vehicle", dtype), lambda: torch.empty((len(self.VEHICLE_ROWS), n), dtype=dtype,
                                                                            device=dev))
         gf = self._rollout_cache(("g_force", dtype), lambda: torch.empty((3, n), dtype=dtype, device=dev))
@@ -1201,9 +1223,7 @@ class CopterVecEnv(_VectorEnvBase):
         torch = _torch()
         if hidden is None:
             raise ValueError("hidden is required (the forward's)")
-        dtype = torch.float64 if dtype is None else dtype
-        if dtype not in (torch.float64, torch.float32):
-            raise ValueError("dtype must be torch.float64 or torch.float32")
+        dtype = self._out_dtype(dtype)
         n, ad, od = self.num_envs, self.action_dim, self.obs_dim
         acts = getattr(rollout, "actions", None)
         if not isinstance(acts, torch.Tensor) or acts.dim() != 3:
@@ -1215,39 +1235,14 @@ class CopterVecEnv(_VectorEnvBase):
         keep += k2
         io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
         obs = getattr(rollout, "obs", None)
-        for t, name, shape, dt in ((rollout.x, "rollout.x", (K, n, 12), torch.float64),
-                                   (rollout.status, "rollout.status", (K, n), torch.uint8),
-                                   (acts, "rollout.actions", (K, n, ad), torch.float32),
-                                   (obs, "rollout.obs", (K, n, od), torch.float32)):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("%s must be a device tensor of shape %s (rollout_mlp_states' result)" % (name, shape))
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, self.device))
+        self._check_tape("rollout_mlp_states", (rollout.x, "rollout.x", (K, n, 12), torch.float64),
+                         (rollout.status, "rollout.status", (K, n), torch.uint8),
+                         (acts, "rollout.actions", (K, n, ad), torch.float32),
+                         (obs, "rollout.obs", (K, n, od), torch.float32))
         io.x_dev, io.status_dev = rollout.x.data_ptr(), rollout.status.data_ptr()
         mio.actions_out_dev = acts.data_ptr()
-
-        def cot(v, shape, name):
-            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-            if not t.dtype.is_floating_point:
-                raise ValueError("%s must be a floating-point array" % name)
-            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        if gx is not None:
-            io.gx_dev = cot(gx, (K, n, 12), "gx")
-        if gr is not None:
-            io.gr_dev = cot(gr, (K, n), "gr")
-        dev = self.device
-        ga = self._rollout_cache(("mlp_g_actions", K, dtype), lambda: torch.empty((K, n, ad), dtype=dtype, device=dev))
-        io.g_actions_dev = ga.data_ptr()
-        g0 = None
-        if state is not None:
-            g0 = self._rollout_cache(("mlp_g_x0", dtype), lambda: torch.empty((12, n), dtype=dtype, device=dev))
-            io.g_x0_dev = g0.data_ptr()
+        self._cotangents(io, gx, gr, K, keep)
+        ga, g0 = self._grad_out(io, "mlp_", K, dtype, state is not None)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.cs_rollout_mlp_vjp(self._ctx, C.byref(io), C.byref(mio), self._stream()))
             gp = _mlp.param_grad(p, hidden, obs, ga) if param_grad else None
