@@ -100,6 +100,18 @@ class RolloutMlpIO(C.Structure):
                 ("offsets_dev", C.c_void_p), ("actions_out_dev", C.c_void_p), ("obs_out_dev", C.c_void_p)]
 
 
+class RolloutMlpExIO(C.Structure):
+    """Mirror of `struct cs_rollout_mlp_ex_io` (cs_rollout_mlp_vjp_ex)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved_", C.c_uint32), ("g_actions_in_dev", C.c_void_p)]
+
+
+class MlpGradIO(C.Structure):
+    """Mirror of `struct cs_mlp_grad_io` (cs_mlp_param_grad)."""
+    _fields_ = [("struct_size", C.c_uint32), ("ga_dtype", C.c_uint32), ("hidden", C.c_int32),
+                ("num_steps", C.c_int32), ("params_dev", C.c_void_p), ("obs_dev", C.c_void_p),
+                ("g_actions_dev", C.c_void_p), ("g_params_dev", C.c_void_p)]
+
+
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
 JAC_INTEGRATED, JAC_LANDED, JAC_CONTACT, JAC_LEVELING, JAC_CRASHED, JAC_RESET, JAC_CLIPPED = 1, 2, 4, 8, 16, 32, 64
@@ -164,6 +176,9 @@ SYMBOLS = {
     "cs_rollout_vjp_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutParamIO), _P]),
     "cs_rollout_mlp_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMlpIO), _P]),
     "cs_rollout_mlp_vjp": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMlpIO), _P]),
+    "cs_rollout_mlp_vjp_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMlpIO), C.POINTER(RolloutMlpExIO),
+                                        _P]),
+    "cs_mlp_param_grad": (C.c_int, [_P, C.POINTER(MlpGradIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

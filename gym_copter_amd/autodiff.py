@@ -95,11 +95,15 @@ def _function_mlp():
 
     class MlpRolloutFunction(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, params, offsets, x0, env, num_steps, hidden, state):
+        def forward(ctx, params, offsets, x0, env, num_steps, hidden, state, action_grad, reduce):
             r = env.rollout_mlp_states(params, num_steps, hidden, offsets=offsets, state=state)
             out = tuple(t.clone() for t in r)                   # (the env's buffers are overwritten by its next call)
             x, reward, term, trunc, status, obs, actions = out
-            ctx.mark_non_differentiable(term, trunc, status, obs, actions)
+            if action_grad:                                     # (the action tape carries a gradient: its cotangent is
+                ctx.mark_non_differentiable(term, trunc, status, obs)       # the backward's g_actions_in)
+            else:
+                ctx.mark_non_differentiable(term, trunc, status, obs, actions)
+            ctx.action_grad, ctx.reduce = action_grad, reduce
             # (params is saved, not kept as an attribute: autograd refuses a backward after an in-place change of it)
             ctx.save_for_backward(params, x, status, obs, actions)
             ctx.env, ctx.state, ctx.hidden = env, state, hidden
@@ -108,29 +112,35 @@ def _function_mlp():
 
         @staticmethod
         @once_differentiable
-        def backward(ctx, gx, gr, *_):
+        def backward(ctx, gx, gr, *rest):
             params, x, status, obs, actions = ctx.saved_tensors
+            gact = rest[4] if ctx.action_grad else None         # (the cotangent of the action tape, the seventh output)
             gp, ga, g0 = ctx.env.rollout_mlp_vjp(params, MlpRollout(x, None, None, None, status, obs, actions), gx=gx,
-                                                 gr=gr, state=ctx.state, hidden=ctx.hidden, dtype=torch.float64)
+                                                 gr=gr, state=ctx.state, hidden=ctx.hidden, dtype=torch.float64,
+                                                 g_actions_in=gact, reduce=ctx.reduce)
             want_u, want_x0 = ctx.want
             return (gp.to(params.dtype), ga.to(torch.float32) if want_u else None,
-                    g0.clone() if (want_x0 and g0 is not None) else None, None, None, None, None)
+                    g0.clone() if (want_x0 and g0 is not None) else None, None, None, None, None, None, None)
 
     _FN_MLP = MlpRolloutFunction
     return _FN_MLP
 
 
-def differentiable_mlp_rollout(env, params, num_steps, hidden, offsets=None, state=None):
+def differentiable_mlp_rollout(env, params, num_steps, hidden, offsets=None, state=None, action_grad=False,
+                               reduce="torch"):
     """K = num_steps closed-loop steps of `env` under the MLP policy `params` (CopterVecEnv.rollout_mlp_states: step k
     takes a_k = float32(pi(o_{k-1}) + offsets[k-1]), auto-reset disabled), differentiable: returns an MlpRollout whose
     x [K,N,12] float64 and reward [K,N] float64 carry gradients, and whose terminated / truncated / status and the obs /
     actions tapes do not.  `params` ([P] float32 device tensor, gym_copter_amd.mlp's layout) receives dL / d params,
     `offsets` ([K,N,A] float32, optional) dL / d offsets, an explicit start's state["x"] ([12,N] float64, when it
-    requires grad) dL / d x0 -- all through one backward kernel (CopterVecEnv.rollout_mlp_vjp) and one torch reduction
-    for the parameters.  The outputs are copies; an in-place change of params between the forward and the backward is
-    refused, and a double backward raises (once differentiable).  With the stored start the env must not step between
-    the forward and the backward.  A loss on the action tape is not differentiated (it is an output without gradient):
-    penalise the motors through x."""
+    requires grad) dL / d x0 -- all through one backward kernel (CopterVecEnv.rollout_mlp_vjp) and one reduction for the
+    parameters: torch matrix products (reduce="torch", the default) or one HIP kernel (reduce="device",
+    CopterVecEnv.mlp_param_grad).  The outputs are copies; an in-place change of params between the forward and the
+    backward is refused, and a double backward raises (once differentiable).  With the stored start the env must not
+    step between the forward and the backward.  With action_grad=True the returned `actions` tape ([K,N,A] float32)
+    carries a gradient too: a loss on the actions themselves (control effort, action rate) is differentiated, its
+    cotangent entering the backward as rollout_mlp_vjp's g_actions_in.  With the default the action tape is an output
+    without gradient, and a loss on it is not differentiated."""
     torch = _torch()
     if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.dim() != 1:
         raise ValueError("params must be a 1-D float32 torch tensor (gym_copter_amd.mlp)")
@@ -147,5 +157,7 @@ def differentiable_mlp_rollout(env, params, num_steps, hidden, offsets=None, sta
         if state["x"].dtype != torch.float64:
             raise ValueError("state['x'] must be float64 to receive a gradient, got %s" % state["x"].dtype)
         x0 = state["x"]
-    out = _function_mlp().apply(params, offsets, x0, env, num_steps, hidden, state)
+    if reduce not in ("torch", "device"):
+        raise ValueError("reduce must be 'torch' or 'device', got %r" % (reduce,))
+    out = _function_mlp().apply(params, offsets, x0, env, num_steps, hidden, state, bool(action_grad), reduce)
     return MlpRollout(*out)

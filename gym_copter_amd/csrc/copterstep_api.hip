@@ -30,6 +30,7 @@ struct cs_ctx {
   double* veh_raw = nullptr;  // ... and the raw [12][N] table they were folded from (the parameter gradients' unfold)
   double* veh_ovr = nullptr;  // scratch of cs_rollout_*_ex: an override's folded columns [11][stride]
   double* veh_gcoef = nullptr;  // ... and the coefficient adjoints [11][N]
+  double* mlp_partials = nullptr;  // scratch of cs_mlp_param_grad: its workgroups' partial sums
   cs::Tuning tune{};
   // the per-launch constants, derived from cfg once and again after cs_seed / cs_set_altitude
   cs::DevConst dc;
@@ -350,6 +351,18 @@ int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, Pa
   return CS_OK;
 }
 
+int mlp_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out) {
+  if (ctx->mlp_partials == nullptr) {
+    if (capturing((hipStream_t)stream))
+      return fail(CS_ERR_ARG, std::string(who) + ": the first call on a context allocates its scratch: make it outside "
+                                                 "graph capture");
+    DeviceGuard guard(ctx->cfg.device);
+    CS_HIP(hipMalloc((void**)&ctx->mlp_partials, bytes));
+  }
+  *out = ctx->mlp_partials;
+  return CS_OK;
+}
+
 int enter_context(cs_ctx* ctx, const char* who, void* stream, ContextView* out) {
   if (int rc_ = check_idle(ctx, who, stream, true)) return rc_;
   out->task = ctx->cfg.task;
@@ -547,6 +560,7 @@ int cs_destroy(cs_ctx* ctx) {
   if (ctx->veh_raw) (void)hipFree(ctx->veh_raw);
   if (ctx->veh_ovr) (void)hipFree(ctx->veh_ovr);
   if (ctx->veh_gcoef) (void)hipFree(ctx->veh_gcoef);
+  if (ctx->mlp_partials) (void)hipFree(ctx->mlp_partials);
   if (ctx->serve_fork) (void)hipEventDestroy(ctx->serve_fork);
   if (ctx->serve_join) (void)hipEventDestroy(ctx->serve_join);
   if (ctx->serve_mem) (void)hipFree(ctx->serve_mem);

@@ -38,4 +38,8 @@ struct ParamView {
 // (outside stream order: the first call with an override or a parameter gradient allocates)
 int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, ParamView* out);
 
+// (copterstep_api.hip) the context's scratch of cs_mlp_param_grad (copterstep_mlp_grad.hip): `bytes` of workgroup
+// partials, allocated by the first call (refused while `stream` is being captured) and released by cs_destroy
+int mlp_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
+
 }  // namespace cs

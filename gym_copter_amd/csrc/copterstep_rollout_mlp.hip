@@ -239,11 +239,21 @@ __global__ __launch_bounds__(kBlock) void rollout_mlp_states_kernel(const DevCon
 }
 
 // The closed-loop sweep's extension (rollout_vjp_sweep's EXT): the policy's VJP after each step's adjoint; io.actions_dev
-// is the action tape
-template <int TASK>
+// is the action tape.  COT (cs_rollout_mlp_vjp_ex): the caller's cotangent on the action tape, g_in [K,N,A] float64, is
+// added to each step's g_a first -- a template flag, so that the kernels without it are the ones they were.
+template <int TASK, bool COT = false>
 struct SweepPolicy {
   static constexpr bool kParam = false, kPolicy = true;
   const MlpArgs& m;
+  const double* g_in = nullptr;
+  __device__ __forceinline__ void add_action_cotangent(size_t row, uint32_t env, double (&ga)[4]) const {
+    if constexpr (COT) {
+      constexpr int A = task_act_dim(TASK);
+      const double* g = g_in + (row + env) * A;
+#pragma unroll
+      for (int c = 0; c < A; ++c) ga[c] += g[c];
+    }
+  }
   __device__ __forceinline__ void vjp(const double (&x)[12], const double (&ga)[4], double (&lam)[12]) const {
     mlp_vjp<TASK>(m.params, m.hidden, x, ga, lam);
   }
@@ -262,6 +272,18 @@ __global__ __launch_bounds__(kBlock) void rollout_mlp_vjp_gyro_kernel(const DevC
                                                                       const cs_rollout_io io, const MlpArgs m) {
   rollout_vjp_sweep<TASK, MODE, true>(c, s, io, SweepPolicy<TASK>{m});
 }
+// the same two with the cotangent on the action tape
+template <int TASK, int MODE>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void rollout_mlp_vjp_cot_kernel(
+    const DevConst c, const DevState s, const cs_rollout_io io, const MlpArgs m, const double* const g_in) {
+  rollout_vjp_sweep<TASK, MODE, false>(c, s, io, SweepPolicy<TASK, true>{m, g_in});
+}
+template <int TASK, int MODE>
+__global__ __launch_bounds__(kBlock) void rollout_mlp_vjp_gyro_cot_kernel(const DevConst c, const DevState s,
+                                                                          const cs_rollout_io io, const MlpArgs m,
+                                                                          const double* const g_in) {
+  rollout_vjp_sweep<TASK, MODE, true>(c, s, io, SweepPolicy<TASK, true>{m, g_in});
+}
 
 // the launchers of one (task, mode) instantiation (CS_DISPATCH picks it), the backward's split on the rotor-gyro term
 template <int TASK, int MODE>
@@ -274,9 +296,13 @@ hipError_t mlp_states_t(const DevConst& c, const DevState& s, const cs_rollout_i
 
 template <int TASK, int MODE>
 hipError_t mlp_vjp_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const MlpArgs& m,
-                     hipStream_t stream) {
+                     const double* g_in, hipStream_t stream) {
   const dim3 grid(grid_for(s.n)), block(kBlock);
-  if (c.gyro)
+  if (g_in != nullptr && c.gyro)
+    hipLaunchKernelGGL((rollout_mlp_vjp_gyro_cot_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m, g_in);
+  else if (g_in != nullptr)
+    hipLaunchKernelGGL((rollout_mlp_vjp_cot_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m, g_in);
+  else if (c.gyro)
     hipLaunchKernelGGL((rollout_mlp_vjp_gyro_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);
   else
     hipLaunchKernelGGL((rollout_mlp_vjp_kernel<TASK, MODE>), grid, block, 0, stream, c, s, io, m);
@@ -289,8 +315,8 @@ hipError_t launch_rollout_mlp_states(int task, int mode, const DevConst& c, cons
 }
 
 hipError_t launch_rollout_mlp_vjp(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
-                                  const MlpArgs& m, hipStream_t stream) {
-  CS_DISPATCH(mlp_vjp_t, c, s, io, m, stream)
+                                  const MlpArgs& m, const double* g_in, hipStream_t stream) {
+  CS_DISPATCH(mlp_vjp_t, c, s, io, m, g_in, stream)
 }
 
 // the argument blocks, checked before the context: the MLP block's own checks, then check_rollout_io on a copy of io
@@ -339,7 +365,26 @@ extern "C" int cs_rollout_mlp_vjp(cs_ctx* ctx, const cs_rollout_io* io, const cs
   cs::ContextView v;
   if (int rc_ = cs::enter_context(ctx, "cs_rollout_mlp_vjp", stream, &v)) return rc_;
   const cs::MlpArgs m{mio->params_dev, nullptr, nullptr, nullptr, mio->hidden};
-  const hipError_t e = cs::launch_rollout_mlp_vjp(v.task, v.mode, *v.c, *v.s, io2, m, (hipStream_t)stream);
+  const hipError_t e = cs::launch_rollout_mlp_vjp(v.task, v.mode, *v.c, *v.s, io2, m, nullptr, (hipStream_t)stream);
   if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mlp_vjp: kernel launch");
+  return CS_OK;
+}
+
+extern "C" int cs_rollout_mlp_vjp_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio,
+                                     const cs_rollout_mlp_ex_io* xio, void* stream) {
+  if (xio == nullptr) return cs_rollout_mlp_vjp(ctx, io, mio, stream);
+  cs_rollout_io io2;
+  if (int rc_ = cs::check_rollout_io_mlp(io, mio, "cs_rollout_mlp_vjp_ex", true, &io2)) return rc_;
+  if (xio->struct_size != sizeof(cs_rollout_mlp_ex_io))
+    return cs::report_error(CS_ERR_ABI, ("cs_rollout_mlp_vjp_ex: xio->struct_size " + std::to_string(xio->struct_size) +
+                                         " != " + std::to_string(sizeof(cs_rollout_mlp_ex_io)) +
+                                         " (sizeof(cs_rollout_mlp_ex_io))").c_str());
+  if (xio->reserved_ != 0) return cs::report_error(CS_ERR_ARG, "cs_rollout_mlp_vjp_ex: xio->reserved_ must be 0");
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, "cs_rollout_mlp_vjp_ex", stream, &v)) return rc_;
+  const cs::MlpArgs m{mio->params_dev, nullptr, nullptr, nullptr, mio->hidden};
+  const hipError_t e =
+      cs::launch_rollout_mlp_vjp(v.task, v.mode, *v.c, *v.s, io2, m, xio->g_actions_in_dev, (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mlp_vjp_ex: kernel launch");
   return CS_OK;
 }

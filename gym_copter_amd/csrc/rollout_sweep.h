@@ -124,8 +124,9 @@ struct ParamGradOut {
 //   kParam   the coefficient adjoints (cs_rollout_vjp_ex): step_adjoint's PARAM terms, accumulated in the lane's LDS
 //            columns `acc` (2 x kAccRows rows: step 0 has its own set), the pending force in newtons at steps 1 and 0,
 //            and the g_coef / g_force stores to `po`
-//   kPolicy  the policy's vector-Jacobian product ext.vjp(x, ga, lam) after each step's adjoint (cs_rollout_mlp_vjp:
-//            lambda_o += J_o pi^T g_a), skipped on a resetting step 0
+//   kPolicy  the caller's cotangent on the action tape, ext.add_action_cotangent(row, env, ga) (cs_rollout_mlp_vjp_ex:
+//            g_a += g_actions_in, before g_a is stored), then the policy's vector-Jacobian product ext.vjp(x, ga, lam)
+//            after each step's adjoint (cs_rollout_mlp_vjp: lambda_o += J_o pi^T g_a), skipped on a resetting step 0
 struct SweepPlain {
   static constexpr bool kParam = false, kPolicy = false;
 };
@@ -202,6 +203,7 @@ __device__ __forceinline__ void rollout_vjp_sweep(const DevConst& c, const DevSt
 #endif
     step_adjoint<TASK, MODE, GYRO, PARAM>(c, q, cur, gr, -0.0, -0.0, -0.0, false, true, false, tape_next, lam, ga,
                                           acc);
+    if constexpr (EXT::kPolicy) ext.add_action_cotangent((size_t)k * n, ii, ga);
     if (valid && io.g_actions_dev != nullptr) store_actions((size_t)k * n, ga);
     if constexpr (EXT::kPolicy) ext.vjp(cur.x, ga, lam);
     cur = nxt;
@@ -239,6 +241,7 @@ __device__ __forceinline__ void rollout_vjp_sweep(const DevConst& c, const DevSt
       acc[8 * kBlock] += (acc[(kAccPe + 0) * kBlock] * f1[0] + acc[(kAccPe + 1) * kBlock] * f1[1]) +
                          acc[(kAccPe + 2) * kBlock] * f1[2];
     }
+    if constexpr (EXT::kPolicy) ext.add_action_cotangent((size_t)n, ii, ga);
     if (valid && io.g_actions_dev != nullptr) store_actions((size_t)n, ga);
     if constexpr (EXT::kPolicy) ext.vjp(cur.x, ga, lam);
   }
@@ -314,8 +317,10 @@ __device__ __forceinline__ void rollout_vjp_sweep(const DevConst& c, const DevSt
       }
     }
   }
-  // (a resetting lane: ga = lam = 0, so the policy adds nothing -- and its pre-reset state need not be finite)
+  // (a resetting lane: the step's ga = lam = 0, so ga is the caller's cotangent alone; the policy's product is skipped
+  // -- its pre-reset state need not be finite, and a stored start returns no g_x0)
   if constexpr (EXT::kPolicy) {
+    ext.add_action_cotangent(0, ii, ga);
     if (!resetting) ext.vjp(in.x, ga, lam);
   }
   if (valid) {

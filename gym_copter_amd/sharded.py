@@ -218,10 +218,13 @@ class ShardedCopterVecEnv:
             offsets = self._local_rollout_actions(offsets)
         return self.local.rollout_mlp_states(params, num_steps, hidden, offsets=offsets, state=state)
 
-    def rollout_mlp_vjp(self, params, rollout, gx=None, gr=None, state=None, hidden=None, offsets=None, dtype=None):
-        """CopterVecEnv.rollout_mlp_vjp of this rank's envs: shard-local (rollout, gx, gr: the local envs').  g_params
-        is THIS rank's sum over its envs: a data-parallel caller all-reduces it (sum) across the ranks."""
-        return self.local.rollout_mlp_vjp(params, rollout, gx=gx, gr=gr, state=state, hidden=hidden, dtype=dtype)
+    def rollout_mlp_vjp(self, params, rollout, gx=None, gr=None, state=None, hidden=None, offsets=None, dtype=None,
+                        g_actions_in=None, reduce="torch"):
+        """CopterVecEnv.rollout_mlp_vjp of this rank's envs: shard-local (rollout, gx, gr, g_actions_in: the local
+        envs').  g_params is THIS rank's sum over its envs, by either `reduce`: a data-parallel caller all-reduces it
+        (sum) across the ranks."""
+        return self.local.rollout_mlp_vjp(params, rollout, gx=gx, gr=gr, state=state, hidden=hidden, dtype=dtype,
+                                          g_actions_in=g_actions_in, reduce=reduce)
 
     def close(self):
         self.local.close()

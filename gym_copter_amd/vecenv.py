@@ -1204,8 +1204,44 @@ class CopterVecEnv(_VectorEnvBase):
         self._keep = keep
         return out
 
+    def mlp_param_grad(self, params, hidden, obs, g_actions, out=None):
+        """g_params [P] float64 = sum_{k,n} J_params pi(obs[k,n])^T g_actions[k,n], reduced ON THE DEVICE by one HIP
+        kernel (cs_mlp_param_grad): the device counterpart of gym_copter_amd.mlp.param_grad, the
+        same sums term by term in float64 (h recomputed with the device library's tanh), in an order of its own that
+        is fixed -- the same inputs give the same bits on every call.  obs [K,N,OBS] float32 is the forward's obs tape,
+        g_actions [K,N,A] float64 or float32 what rollout_mlp_vjp returned; both contiguous tensors on this env's
+        device.  Asynchronous on the current stream; the result is written (not accumulated) into `out`, a contiguous
+        [P] float64 tensor on this env's device, or into a new tensor."""
+        self._check_open()
+        torch = _torch()
+        keep = []
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[0] < 1:
+            raise ValueError("obs must be the [K,%d,%d] obs tape of rollout_mlp_states" % (self.num_envs, self.obs_dim))
+        K = int(obs.shape[0])
+        _, p = self._mlp_io(params, hidden, K, None, keep)
+        n = self.num_envs
+        self._check_tape("rollout_mlp_states", (obs, "obs", (K, n, self.obs_dim), torch.float32))
+        if not isinstance(g_actions, torch.Tensor) or g_actions.dtype not in (torch.float64, torch.float32):
+            raise ValueError("g_actions must be a float64 or float32 device tensor of shape (%d, %d, %d)"
+                             % (K, n, self.action_dim))
+        self._check_tape("rollout_mlp_vjp", (g_actions, "g_actions", (K, n, self.action_dim), g_actions.dtype))
+        if out is None:
+            out = torch.empty(p.shape[0], dtype=torch.float64, device=self.device)
+        else:
+            self._check_tape("mlp_param_grad", (out, "out", (p.shape[0],), torch.float64))
+        gio = _lib.MlpGradIO()
+        gio.struct_size = C.sizeof(_lib.MlpGradIO)
+        gio.ga_dtype = _lib.JAC_F32 if g_actions.dtype == torch.float32 else _lib.JAC_F64
+        gio.hidden, gio.num_steps = hidden, K
+        gio.params_dev, gio.obs_dev = p.data_ptr(), obs.data_ptr()
+        gio.g_actions_dev, gio.g_params_dev = g_actions.data_ptr(), out.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_mlp_param_grad(self._ctx, C.byref(gio), self._stream()))
+        self._keep = keep + [obs, g_actions]
+        return out
+
     def rollout_mlp_vjp(self, params, rollout, gx=None, gr=None, state=None, hidden=None, offsets=None, dtype=None,
-                        param_grad=True):
+                        param_grad=True, g_actions_in=None, reduce="torch"):
         """Reverse-mode gradient of a closed-loop rollout: given the cotangents gx [K,N,12] (on rollout.x) and gr [K,N]
         (on rollout.reward), either None (zero), returns (g_params [P] float64, g_actions [K,N,A], g_x0 [12,N] or None).
 
@@ -1218,11 +1254,20 @@ class CopterVecEnv(_VectorEnvBase):
         rounding of o and a is straight-through.  dtype: torch.float64 (default) or torch.float32 for g_actions and
         g_x0.  Asynchronous on the current stream; g_actions and g_x0 are buffers of this env, overwritten by its next
         call with the same K and dtype.  (`offsets` is accepted for symmetry with the forward; the backward reads the
-        action tape, not the offsets.)"""
+        action tape, not the offsets.)
+
+        g_actions_in [K,N,A] (None = zero) is a cotangent taken directly on the action tape rollout.actions -- a loss on
+        the actions themselves, such as a control-effort penalty: a_k is the action as step() receives it, before the
+        clip, so it adds to the step's own g_a_k without a mask, and the total is what g_actions returns, what the
+        policy carries back into the state and what g_params is reduced from.  An env that resets in step 1 returns
+        g_actions[0] = g_actions_in[0].  reduce="torch" (default) makes g_params with gym_copter_amd.mlp.param_grad,
+        reduce="device" with mlp_param_grad (one HIP kernel; the same sums in another, fixed, order)."""
         self._check_open()
         torch = _torch()
         if hidden is None:
             raise ValueError("hidden is required (the forward's)")
+        if reduce not in ("torch", "device"):
+            raise ValueError("reduce must be 'torch' or 'device', got %r" % (reduce,))
         dtype = self._out_dtype(dtype)
         n, ad, od = self.num_envs, self.action_dim, self.obs_dim
         acts = getattr(rollout, "actions", None)
@@ -1242,10 +1287,28 @@ class CopterVecEnv(_VectorEnvBase):
         io.x_dev, io.status_dev = rollout.x.data_ptr(), rollout.status.data_ptr()
         mio.actions_out_dev = acts.data_ptr()
         self._cotangents(io, gx, gr, K, keep)
+        xio = None
+        if g_actions_in is not None:
+            gin = g_actions_in
+            if not isinstance(gin, torch.Tensor) or not gin.dtype.is_floating_point:
+                raise ValueError("g_actions_in must be a floating-point torch tensor of shape (%d, %d, %d)" % (K, n, ad))
+            if tuple(gin.shape) != (K, n, ad):
+                raise ValueError("g_actions_in must have shape %s, got %s" % ((K, n, ad), tuple(gin.shape)))
+            if gin.device != self.device:
+                raise ValueError("g_actions_in must be on %s, got %s" % (self.device, gin.device))
+            gin = gin.detach().to(torch.float64).contiguous()
+            keep.append(gin)
+            xio = _lib.RolloutMlpExIO()
+            xio.struct_size = C.sizeof(_lib.RolloutMlpExIO)
+            xio.g_actions_in_dev = gin.data_ptr()
         ga, g0 = self._grad_out(io, "mlp_", K, dtype, state is not None)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_mlp_vjp(self._ctx, C.byref(io), C.byref(mio), self._stream()))
-            gp = _mlp.param_grad(p, hidden, obs, ga) if param_grad else None
+            # (xio = None is a NULL block: exactly cs_rollout_mlp_vjp)
+            _lib.check(self._lib.cs_rollout_mlp_vjp_ex(self._ctx, C.byref(io), C.byref(mio),
+                                                       None if xio is None else C.byref(xio), self._stream()))
+            gp = None
+            if param_grad:
+                gp = self.mlp_param_grad(p, hidden, obs, ga) if reduce == "device" else _mlp.param_grad(p, hidden, obs, ga)
         self._keep = keep
         return gp, ga, g0
 

@@ -30,6 +30,9 @@
  *   cs_rollout_mlp_states    the same rollout closed-loop       lander.py:40-65 with a policy in place of the random
  *   cs_rollout_mlp_vjp       under a fused MLP policy, and      action; the rollout lines above, differentiated
  *                            its gradient
+ *   cs_rollout_mlp_vjp_ex    ... with a cotangent on the action  (a loss on the actions themselves)
+ *   cs_mlp_param_grad        the gradient w.r.t. the policy's   the same loop's policy, differentiated in its weights
+ *                            parameters, reduced on the device
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -674,9 +677,10 @@ int cs_rollout_vjp_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_par
  * The derivative rules are cs_rollout_vjp's plus the policy's: the float32 rounding of o and of a is straight-through
  * (as the storage rounding is), tanh' = 1 - h^2 with h recomputed in float64, lambda_o += J_o pi^T g_a accumulated in
  * float64.  A lane that resets in step 1 has g_a_1 = 0, so the policy adds nothing through a_1.  The gradient with
- * respect to theta is a reduction over every env and step that the caller makes from the obs tape and g_actions:
+ * respect to theta is a reduction over every env and step of the obs tape and g_actions:
  *     g_theta = sum_{k,n} J_theta pi(o_{k-1,n})^T g_a_{k,n}
- * (gym_copter_amd.mlp.param_grad: h recomputed in float64, as the kernel does).
+ * (cs_mlp_param_grad below, on the device; gym_copter_amd.mlp.param_grad is the same sum as torch matrix products: h
+ * recomputed in float64, as the kernel does).
  *
  * io->actions_dev must be NULL in both calls (the policy makes the actions).  params_dev is read by the scalar unit:
  * 4-B aligned, never written while a call runs; actions_out_dev and obs_out_dev 16-B aligned.  The vehicle override and
@@ -693,6 +697,47 @@ typedef struct cs_rollout_mlp_io {
 } cs_rollout_mlp_io;
 int cs_rollout_mlp_states(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio, void* stream);
 int cs_rollout_mlp_vjp(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio, void* stream);
+
+/* cs_rollout_mlp_vjp with a cotangent on the ACTION TAPE: a loss that depends on the actions themselves (control effort,
+ * action rate).  xio->g_actions_in_dev [K,N,A] float64 (NULL = zero) is the caller's dL / d a_k taken directly on
+ * actions_out_dev.  a_k is the action as cs_step receives it, before the clip, so the cotangent adds without a mask:
+ *     g_a_k = (the step's own adjoint of a_k) + g_actions_in[k]
+ * and that total is what g_actions_dev receives and what the policy's vector-Jacobian product pushes into the state's
+ * adjoint; g_actions_dev is still dL / d u_k and still the input of the theta reduction below.  A lane that resets in
+ * step 1 (a stored start with a NEXT_STEP reset pending) gets g_actions[0] = g_actions_in[0], and its policy product
+ * stays skipped (its pre-reset state need not be finite, and a stored start returns no g_x0).  With xio == NULL, or a
+ * NULL g_actions_in_dev, the call is exactly cs_rollout_mlp_vjp.  xio->struct_size must be
+ * sizeof(cs_rollout_mlp_ex_io) (else CS_ERR_ABI); the blocks are checked before the context. */
+typedef struct cs_rollout_mlp_ex_io {
+  uint32_t struct_size;            /* sizeof(cs_rollout_mlp_ex_io) */
+  uint32_t reserved_;              /* 0 */
+  const double* g_actions_in_dev;  /* [K,N,A] float64 dL / d a_k on the action tape, or NULL = zero */
+} cs_rollout_mlp_ex_io;
+int cs_rollout_mlp_vjp_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mlp_io* mio,
+                          const cs_rollout_mlp_ex_io* xio, void* stream);
+
+/* The gradient with respect to theta, on the device: g_params = sum_{k,n} J_theta pi(o_{k-1,n})^T g_a_{k,n} over the
+ * forward's obs tape and the backward's g_actions (N, OBS and A are the context's).  Per row, in float64:
+ *   o = (double)obs;  pre_j = fma chain from (double)b1[j] in index order;  h_j = tanh(pre_j) (the device library's
+ *   float64 tanh: what cs_rollout_mlp_vjp recomputes);  gh_j = sum_c W2[c][j] g_a[c];  gp_j = gh_j (1 - h_j^2);
+ *   gW1[j][i] += gp_j o_i;  gb1[j] += gp_j;  gW2[c][j] += g_a[c] h_j;  gb2[c] += g_a[c]
+ * (hidden = 0: gW[c][i] += g_a[c] o_i, gb[c] += g_a[c]) -- gym_copter_amd.mlp.param_grad term by term.  The order of
+ * summation is the kernel's own and fixed (a function of K N and the shape; no floating-point atomics): the same inputs
+ * give the same bits on every call.  g_params_dev is WRITTEN, not accumulated.  Asynchronous on `stream`; obs_dev and
+ * g_actions_dev are aligned to their element size.  The first call on a context allocates its scratch of partial sums
+ * (call it outside graph capture; released by cs_destroy), and calls on one context must be ordered on one stream.
+ * io->struct_size must be sizeof(cs_mlp_grad_io) (else CS_ERR_ABI); the block is checked before the context. */
+typedef struct cs_mlp_grad_io {
+  uint32_t struct_size;        /* sizeof(cs_mlp_grad_io) */
+  uint32_t ga_dtype;           /* CS_JAC_F64 / CS_JAC_F32: the dtype of g_actions_dev */
+  int32_t hidden;              /* 0 .. CS_MLP_MAX_HIDDEN */
+  int32_t num_steps;           /* K >= 1 */
+  const float* params_dev;     /* [P] float32, cs_rollout_mlp_io's layout */
+  const float* obs_dev;        /* [K,N,OBS] float32: the forward's obs tape */
+  const void* g_actions_dev;   /* [K,N,A]: what cs_rollout_mlp_vjp wrote */
+  double* g_params_dev;        /* [P] float64: WRITTEN, not accumulated */
+} cs_mlp_grad_io;
+int cs_mlp_param_grad(cs_ctx* ctx, const cs_mlp_grad_io* io, void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in

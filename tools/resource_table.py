@@ -1,7 +1,8 @@
 """One line per kernel from hipcc's -Rpass-analysis=kernel-resource-usage remarks (make report): name | SGPRs | VGPRs |
 AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_resources.txt.
 
-    python3 tools/resource_table.py remarks.txt > profiles/rollout_mlp_resources.txt"""
+    python3 tools/resource_table.py remarks.txt > profiles/rollout_mlp_resources.txt
+    python3 tools/resource_table.py remarks.txt mlp_grad > profiles/mlp_grad_resources.txt"""
 import re
 import sys
 
@@ -24,11 +25,19 @@ def table(lines):
     return rows
 
 
-def main(path):
+HEADS = {"rollout_mlp": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_mlp.hip: the closed-loop forward
+# rollout_mlp_states_kernel<TASK, MODE> and the backward: rollout_mlp_vjp_kernel<TASK, MODE> (no rotor-gyro term,
+# held to 2 wavefronts per SIMD) and rollout_mlp_vjp_gyro_kernel<TASK, MODE>, and the same two with the cotangent on the
+# action tape, rollout_mlp_vjp_cot_kernel and rollout_mlp_vjp_gyro_cot_kernel (DESIGN.md section 12).""", "mlp_grad": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_mlp_grad.hip: the policy-parameter gradient
+# mlp_param_grad_kernel<OBS, A, HP> (HP = 0: linear, else the hidden width rounded up to 8, 16, 32 or 64 lanes per row)
+# and mlp_grad_sum_kernel, the sum of its workgroups' partials (DESIGN.md section 12)."""}
+
+
+def main(path, which="rollout_mlp"):
     rows = table(open(path).read().splitlines())
-    print("# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_mlp.hip: the closed-loop forward")
-    print("# rollout_mlp_states_kernel<TASK, MODE> and the backward: rollout_mlp_vjp_kernel<TASK, MODE> (no rotor-gyro term,")
-    print("# held to 2 wavefronts per SIMD) and rollout_mlp_vjp_gyro_kernel<TASK, MODE> (DESIGN.md section 12).")
+    print(HEADS[which])
     print("# Name | SGPRs | VGPRs | AGPRs | scratch B/lane | waves/SIMD | LDS B/block")
     for r in rows:
         print("|".join([r["name"]] + [str(r.get(s, "?")) for _, s in FIELDS]))
@@ -38,4 +47,4 @@ def main(path):
 
 
 if __name__ == "__main__":
-    sys.exit(main(sys.argv[1]))
+    sys.exit(main(*sys.argv[1:3]))
