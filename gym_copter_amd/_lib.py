@@ -112,6 +112,21 @@ class MlpGradIO(C.Structure):
                 ("g_actions_dev", C.c_void_p), ("g_params_dev", C.c_void_p)]
 
 
+class RolloutLqrIO(C.Structure):
+    """Mirror of `struct cs_rollout_lqr_io` (cs_rollout_lqr)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("mu", C.c_double),
+                ("q_dev", C.c_void_p), ("r_dev", C.c_void_p), ("Q_dev", C.c_void_p), ("Q_final_dev", C.c_void_p),
+                ("R_dev", C.c_void_p), ("K_dev", C.c_void_p), ("d_dev", C.c_void_p), ("dV_dev", C.c_void_p),
+                ("S0_dev", C.c_void_p), ("s0_dev", C.c_void_p), ("ok_dev", C.c_void_p)]
+
+
+class RolloutFeedbackIO(C.Structure):
+    """Mirror of `struct cs_rollout_feedback_io` (cs_rollout_feedback_states)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved_", C.c_uint32), ("xbar_dev", C.c_void_p),
+                ("K_dev", C.c_void_p), ("d_dev", C.c_void_p), ("alpha_dev", C.c_void_p),
+                ("actions_out_dev", C.c_void_p)]
+
+
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
 JAC_INTEGRATED, JAC_LANDED, JAC_CONTACT, JAC_LEVELING, JAC_CRASHED, JAC_RESET, JAC_CLIPPED = 1, 2, 4, 8, 16, 32, 64
@@ -179,6 +194,8 @@ SYMBOLS = {
     "cs_rollout_mlp_vjp_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMlpIO), C.POINTER(RolloutMlpExIO),
                                         _P]),
     "cs_mlp_param_grad": (C.c_int, [_P, C.POINTER(MlpGradIO), _P]),
+    "cs_rollout_lqr": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqrIO), _P]),
+    "cs_rollout_feedback_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -211,6 +211,17 @@ class ShardedCopterVecEnv:
         return self.local.rollout_vjp_params(self._local_rollout_actions(actions), rollout, gx=gx, gr=gr, state=state,
                                              vehicle=vehicle, dtype=dtype)
 
+    def rollout_lqr(self, actions, rollout, Q, R, q=None, r=None, Q_final=None, mu=0.0, state=None, dtype=None):
+        """CopterVecEnv.rollout_lqr of this rank's envs: shard-local (rollout, q, r: the local envs')."""
+        return self.local.rollout_lqr(self._local_rollout_actions(actions), rollout, Q, R, q=q, r=r, Q_final=Q_final,
+                                      mu=mu, state=state, dtype=dtype)
+
+    def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
+        """CopterVecEnv.rollout_feedback_states of this rank's envs: shard-local (rollout, gains, alpha: the local
+        envs')."""
+        return self.local.rollout_feedback_states(self._local_rollout_actions(actions), rollout, gains, alpha,
+                                                  state=state)
+
     def rollout_mlp_states(self, params, num_steps, hidden, offsets=None, state=None):
         """CopterVecEnv.rollout_mlp_states of this rank's envs: shard-local, no gather (params: the policy every rank
         shares; offsets: [K, n_local, A] or the global [K, N, A]; an explicit `state` covers the local envs)."""

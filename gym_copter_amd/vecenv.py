@@ -94,6 +94,9 @@ StepJacobian = collections.namedtuple("StepJacobian", "dx du reward_dx reward_du
 Rollout = collections.namedtuple("Rollout", "x reward terminated truncated status")
 # a closed-loop rollout (rollout_mlp_states): Rollout's fields plus the observation and action tapes
 MlpRollout = collections.namedtuple("MlpRollout", "x reward terminated truncated status obs actions")
+# CopterVecEnv.rollout_lqr's result: the time-varying gains K [K,N,A,12] and d [K,N,A], the model's predicted cost change
+# dV [N,2], the value model at the start S0 [N,12,12], s0 [12,N], and ok [N] bool (every Cholesky pivot positive)
+LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
 
 
 def _torch():
@@ -1311,6 +1314,139 @@ class CopterVecEnv(_VectorEnvBase):
                 gp = self.mlp_param_grad(p, hidden, obs, ga) if reduce == "device" else _mlp.param_grad(p, hidden, obs, ga)
         self._keep = keep
         return gp, ga, g0
+
+    # -- the iLQR backward pass and its line-search forward --------
+    def _lqr_weights(self, Q, R, Q_final):
+        """Q [12,12], R [A,A], Q_final [12,12] or None, checked on the host (symmetric, finite; R's diagonal > 0) and
+        kept on the device: the same values are uploaded once (the iLQR driver passes them every iteration)."""
+        torch = _torch()
+        ad = self.action_dim
+
+        def host(m, shape, name):
+            a = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
+            if not np.isfinite(a).all():
+                raise ValueError("%s must be finite" % name)
+            if not np.array_equal(a, a.T):
+                raise ValueError("%s must be symmetric" % name)
+            return np.ascontiguousarray(a)
+        q = host(Q, (12, 12), "Q")
+        r = host(R, (ad, ad), "R")
+        if not (np.diag(r) > 0).all():
+            raise ValueError("R must be positive definite: its diagonal must be > 0")
+        qf = None if Q_final is None else host(Q_final, (12, 12), "Q_final")
+        key = (q.tobytes(), r.tobytes(), None if qf is None else qf.tobytes())
+        cache = getattr(self, "_lqr_w", None)
+        if cache is None or cache[0] != key:
+            dev = [None if m is None else torch.from_numpy(m).to(self.device) for m in (q, r, qf)]
+            cache = self._lqr_w = (key, dev)
+        return cache[1]
+
+    def rollout_lqr(self, actions, rollout, Q, R, q=None, r=None, Q_final=None, mu=0.0, state=None, dtype=None):
+        """The iLQR backward pass over a rollout's tape, one kernel: the Riccati recursion of the quadratic model of a
+        cost J = sum_k [l_k(x_k) + m_k(a_k)] around the rollout, with the step Jacobians of step_jacobian (every branch
+        rule of DESIGN section 9) applied on the fly and never stored.  `rollout` is what rollout_states(actions, state)
+        returned for the same actions and start (as rollout_vjp takes it).  q [K,N,12] = grad l_k at rollout.x[k-1],
+        r [K,N,A] = grad m_k at actions[k-1] (None: zero); Q [12,12] symmetric PSD, R [A,A] symmetric PD and Q_final
+        (replaces Q at the last step) are the Hessians, shared by every env and step; mu >= 0 is the Levenberg term
+        added to Quu's diagonal before it is inverted.
+
+        Returns LqrGains(K [K,N,A,12], d [K,N,A], dV [N,2], S0 [N,12,12], s0 [12,N], ok [N] bool): the action
+        a_k + alpha d_k + K_k (x_{k-1} - xbar_{k-1}) (rollout_feedback_states) changes the model's cost by
+        alpha dV[:,0] + alpha^2 dV[:,1]; S0, s0 are the value model at the start; ok is False where a Cholesky pivot was
+        not positive (raise mu).  dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).
+        Asynchronous on the current stream; the tensors are buffers of this env, overwritten by its next call with the
+        same K and dtype.  No env state changes."""
+        self._check_open()
+        torch = _torch()
+        dtype = self._out_dtype(dtype)
+        mu = float(mu)
+        if not (mu >= 0.0) or mu == float("inf"):
+            raise ValueError("mu must be finite and >= 0, got %r" % (mu,))
+        Qd, Rd, Qfd = self._lqr_weights(Q, R, Q_final)
+        io, K, keep = self._rollout_io(actions, state)
+        n, ad, dev = self.num_envs, self.action_dim, self.device
+        x, status = getattr(rollout, "x", None), getattr(rollout, "status", None)
+        self._check_tape("rollout_states", (x, "rollout.x", (K, n, 12), torch.float64),
+                         (status, "rollout.status", (K, n), torch.uint8))
+        io.x_dev, io.status_dev = x.data_ptr(), status.data_ptr()
+        lio = _lib.RolloutLqrIO()
+        lio.struct_size = C.sizeof(_lib.RolloutLqrIO)
+        lio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+        lio.mu = mu
+        for v, shape, name in ((q, (K, n, 12), "q"), (r, (K, n, ad), "r")):
+            if v is None:
+                continue
+            if not isinstance(v, torch.Tensor) or not v.dtype.is_floating_point:
+                raise ValueError("%s must be a floating-point torch tensor of shape %s" % (name, shape))
+            if tuple(v.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(v.shape)))
+            if v.device != dev:
+                raise ValueError("%s must be on %s, got %s" % (name, dev, v.device))
+            t = v.detach().to(torch.float64).contiguous()
+            keep.append(t)
+            setattr(lio, name + "_dev", t.data_ptr())
+        lio.Q_dev, lio.R_dev = Qd.data_ptr(), Rd.data_ptr()
+        lio.Q_final_dev = None if Qfd is None else Qfd.data_ptr()
+        out = self._rollout_cache(("lqr", K, dtype), lambda: (
+            torch.empty((K, n, ad, 12), dtype=dtype, device=dev), torch.empty((K, n, ad), dtype=dtype, device=dev),
+            torch.empty((n, 2), dtype=dtype, device=dev), torch.empty((n, 12, 12), dtype=dtype, device=dev),
+            torch.empty((12, n), dtype=dtype, device=dev), torch.empty(n, dtype=torch.bool, device=dev)))
+        lio.K_dev, lio.d_dev, lio.dV_dev, lio.S0_dev, lio.s0_dev, lio.ok_dev = (t.data_ptr() for t in out)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_lqr(self._ctx, C.byref(io), C.byref(lio), self._stream()))
+        self._keep = keep + [Qd, Rd, Qfd]
+        return LqrGains(*out)
+
+    def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
+        """rollout_states under the feedback of rollout_lqr, the line search's forward pass: step k takes
+        a_k = float32(actions[k-1] + alpha d_k + K_k (x_{k-1} - rollout.x[k-2])), x_{k-1} the state of THIS rollout
+        before the step (step 1 has no deviation: both rollouts share the start).  The arithmetic is float64 and fixed:
+        one multiply and one add for alpha d, then per state slot in order a subtraction, a multiply and an add, one
+        rounding to float32.  `rollout` is the nominal rollout_states(actions, state) result, `gains` rollout_lqr's
+        (float64), alpha a float or [N] float64 (per env).  Returns (Rollout, actions_out [K,N,A] float32): the Rollout
+        is bit-identical to rollout_states(actions_out, state).  Asynchronous on the current stream; the tensors are
+        buffers of this env, overwritten by its next call with the same K (they are not rollout_states' buffers).  No
+        env state changes."""
+        self._check_open()
+        torch = _torch()
+        io, K, keep = self._rollout_io(actions, state)
+        n, ad, dev = self.num_envs, self.action_dim, self.device
+        xbar = getattr(rollout, "x", None)
+        Kg, d = getattr(gains, "K", None), getattr(gains, "d", None)
+        self._check_tape("rollout_states", (xbar, "rollout.x", (K, n, 12), torch.float64))
+        self._check_tape("rollout_lqr", (Kg, "gains.K", (K, n, ad, 12), torch.float64),
+                         (d, "gains.d", (K, n, ad), torch.float64))
+        if isinstance(alpha, torch.Tensor):
+            if tuple(alpha.shape) not in ((), (n,)) or not alpha.dtype.is_floating_point:
+                raise ValueError("alpha must be a float or a floating-point tensor of shape (%d,)" % n)
+            if alpha.device != dev and alpha.dim() == 1:
+                raise ValueError("alpha must be on %s, got %s" % (dev, alpha.device))
+            al = alpha.detach().to(device=dev, dtype=torch.float64).expand(n).contiguous()
+        else:
+            a = np.asarray(alpha, dtype=np.float64)
+            if a.shape not in ((), (n,)):
+                raise ValueError("alpha must be a float or have shape (%d,), got %s" % (n, a.shape))
+            al = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (n,)))).to(dev)
+        keep.append(al)
+        out = self._rollout_cache(("feedback", K), lambda: (Rollout(
+            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
+            torch.empty((K, n), dtype=torch.float64, device=dev),
+            torch.empty((K, n), dtype=torch.bool, device=dev),
+            torch.empty((K, n), dtype=torch.bool, device=dev),
+            torch.empty((K, n), dtype=torch.uint8, device=dev)),
+            torch.empty((K, n, ad), dtype=torch.float32, device=dev)))
+        ro, acts = out
+        io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in ro)
+        fio = _lib.RolloutFeedbackIO()
+        fio.struct_size = C.sizeof(_lib.RolloutFeedbackIO)
+        fio.xbar_dev, fio.K_dev, fio.d_dev = xbar.data_ptr(), Kg.data_ptr(), d.data_ptr()
+        fio.alpha_dev, fio.actions_out_dev = al.data_ptr(), acts.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_feedback_states(self._ctx, C.byref(io), C.byref(fio), self._stream()))
+        self._keep = keep + [xbar, Kg, d]
+        return ro, acts
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

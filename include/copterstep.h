@@ -33,6 +33,10 @@
  *   cs_rollout_mlp_vjp_ex    ... with a cotangent on the action  (a loss on the actions themselves)
  *   cs_mlp_param_grad        the gradient w.r.t. the policy's   the same loop's policy, differentiated in its weights
  *                            parameters, reduced on the device
+ *   cs_rollout_lqr           the iLQR backward pass over a      the rollout lines above, differentiated (no upstream
+ *                            rollout's tape                      counterpart: a second-order trajectory optimiser)
+ *   cs_rollout_feedback_states  cs_rollout_states under the     lander.py:40-65 with a time-varying affine feedback
+ *                            feedback that pass returns          in place of the random action
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -738,6 +742,78 @@ typedef struct cs_mlp_grad_io {
   double* g_params_dev;        /* [P] float64: WRITTEN, not accumulated */
 } cs_mlp_grad_io;
 int cs_mlp_param_grad(cs_ctx* ctx, const cs_mlp_grad_io* io, void* stream);
+
+/* The iLQR backward pass over a rollout's tape, on the device: a second-order trajectory
+ * optimiser's Riccati sweep without the K dense Jacobian blocks.  The caller's cost is J = sum_{k=1..K} [l_k(x_k) +
+ * m_k(a_k)], given by its quadratic model at the tape:
+ *   q_dev       [K,N,12] float64  grad l_k at x_k (row k-1), NULL = zero
+ *   r_dev       [K,N,A]  float64  grad m_k at a_k (row k-1), NULL = zero
+ *   Q_dev       [12,12]  float64  the Hessian of l_k, symmetric PSD, shared by every env and step (required)
+ *   Q_final_dev [12,12]           replaces Q_dev at k = K, or NULL
+ *   R_dev       [A,A]    float64  the Hessian of m_k, symmetric PD, shared (required)
+ *   mu          >= 0              the Levenberg term
+ * (Gauss-Newton: no second derivatives of the dynamics enter).  With A_k = d x_k / d x_{k-1} and B_k = d x_k / d a_k --
+ * cs_step_jacobian's dx and du at (tape row k-2, its status, action k), every rule of that call included (the clip's
+ * zero columns, the identity of LANDED / contact / CRASHED, LEVELING's zero rows, A = B = 0 for a NEXT_STEP reset in
+ * step 1, straight-through storage rounding, the float64 motor law's derivative also under CS_ARITH_F32, the pending
+ * perturbation of step 1 and the redraw of step 2 after a reset as cs_rollout_vjp recomputes them); never written to
+ * memory -- the call runs, in float64, from S = 0, s = 0 beyond the horizon, for k = K .. 1:
+ *   V = S + Q_k,  v = s + q_k
+ *   Qx = A^T v,  Qu = r_k + B^T v,  Qxx = A^T V A,  Qux = B^T V A,  Quu = R + B^T V B
+ *   K_k = -(Quu + mu I)^-1 Qux,  d_k = -(Quu + mu I)^-1 Qu        (a Cholesky factorisation of the A x A matrix)
+ *   S <- Qxx + K^T Quu K + K^T Qux + Qux^T K  (its upper triangle kept),  s <- Qx + K^T Quu d + K^T Qu + Qux^T d
+ *   dV1 += d^T Qu,  dV2 += 1/2 d^T Quu d
+ * so that the model's prediction of the cost change under a_k + alpha d_k + K_k (x_{k-1} - xbar_{k-1}) is
+ * alpha dV1 + alpha^2 dV2.  Outputs, each may be NULL, in lio->out_dtype (CS_JAC_F64, or CS_JAC_F32: the float64 values
+ * rounded):
+ *   K_dev  [K,N,A,12]   d_dev  [K,N,A]   dV_dev [N,2]   S0_dev [N,12,12] and s0_dev [12,N]: S and s at the start
+ *   ok_dev [N] uint8    0 if any Cholesky pivot of the env was <= 0 or not finite (its gains are still written, finite
+ *                       or not: raise mu), else 1
+ * io is cs_rollout_vjp's block -- the tape x_dev / status_dev, actions_dev, num_steps and the start point of the
+ * cs_rollout_states call that made the tape; its cotangents and gradient outputs are not used.  Nothing of the env
+ * state is written.  Asynchronous on `stream`; lio->struct_size must be sizeof(cs_rollout_lqr_io) (else CS_ERR_ABI);
+ * both blocks are checked before the context.  The shared matrices are read by the scalar unit: 8-B aligned, never
+ * written while a call runs. */
+typedef struct cs_rollout_lqr_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_lqr_io) */
+  uint32_t out_dtype;          /* CS_JAC_F64 / CS_JAC_F32: K_dev, d_dev, dV_dev, S0_dev, s0_dev */
+  double mu;                   /* >= 0, finite */
+  const double* q_dev;         /* [K,N,12] or NULL */
+  const double* r_dev;         /* [K,N,A] or NULL */
+  const double* Q_dev;         /* [12,12], required */
+  const double* Q_final_dev;   /* [12,12] or NULL */
+  const double* R_dev;         /* [A,A], required */
+  void* K_dev;                 /* [K,N,A,12] */
+  void* d_dev;                 /* [K,N,A] */
+  void* dV_dev;                /* [N,2] */
+  void* S0_dev;                /* [N,12,12] */
+  void* s0_dev;                /* [12,N] */
+  uint8_t* ok_dev;             /* [N] */
+} cs_rollout_lqr_io;
+int cs_rollout_lqr(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_lqr_io* lio, void* stream);
+
+/* The iLQR forward pass (line search): cs_rollout_states with a time-varying affine feedback as its action source.
+ * Step k = 1..K takes
+ *     a_k = fl32( abar_k + alpha d_k + K_k (x_{k-1} - xbar_{k-1}) )
+ * x_{k-1} is the decoded stored state of THIS rollout before step k; xbar the nominal tape (xbar_dev row k-2; xbar_0 is
+ * the shared start point, so step 1 has no deviation term); abar = io->actions_dev, the nominal actions; alpha per env.
+ * The arithmetic is fixed, float64 without contraction: t = abar + alpha d (one multiply, one add); then for j = 0..11
+ * in order t += K[c][j] (x[j] - xbar[j]) (a subtraction, a multiply, an add); one rounding to float32.  Outputs are
+ * cs_rollout_states' (io's x, reward, flags, status; bit-identical to cs_rollout_states fed actions_out_dev) plus
+ *   actions_out_dev [K,N,A] float32  a_k (required)
+ * Everything else -- the start point, the pending perturbation, a pending NEXT_STEP reset, prev_shaping, the step
+ * counter, no env state written -- is cs_rollout_states'.  K_dev and d_dev are float64 (cs_rollout_lqr's with
+ * CS_JAC_F64).  fio->struct_size must be sizeof(cs_rollout_feedback_io) (else CS_ERR_ABI). */
+typedef struct cs_rollout_feedback_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_feedback_io) */
+  uint32_t reserved_;          /* 0 */
+  const double* xbar_dev;      /* [K,N,12] the nominal tape (rows 0 .. K-2 are read; may be NULL when K = 1) */
+  const double* K_dev;         /* [K,N,A,12] float64, required */
+  const double* d_dev;         /* [K,N,A] float64, required */
+  const double* alpha_dev;     /* [N] float64, required */
+  float* actions_out_dev;      /* [K,N,A] float32, required */
+} cs_rollout_feedback_io;
+int cs_rollout_feedback_states(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_feedback_io* fio, void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in

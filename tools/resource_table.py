@@ -2,7 +2,8 @@
 AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_resources.txt.
 
     python3 tools/resource_table.py remarks.txt > profiles/rollout_mlp_resources.txt
-    python3 tools/resource_table.py remarks.txt mlp_grad > profiles/mlp_grad_resources.txt"""
+    python3 tools/resource_table.py remarks.txt mlp_grad > profiles/mlp_grad_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_lqr > profiles/rollout_lqr_resources.txt"""
 import re
 import sys
 
@@ -32,7 +33,10 @@ HEADS = {"rollout_mlp": """\
 # action tape, rollout_mlp_vjp_cot_kernel and rollout_mlp_vjp_gyro_cot_kernel (DESIGN.md section 12).""", "mlp_grad": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_mlp_grad.hip: the policy-parameter gradient
 # mlp_param_grad_kernel<OBS, A, HP> (HP = 0: linear, else the hidden width rounded up to 8, 16, 32 or 64 lanes per row)
-# and mlp_grad_sum_kernel, the sum of its workgroups' partials (DESIGN.md section 12)."""}
+# and mlp_grad_sum_kernel, the sum of its workgroups' partials (DESIGN.md section 12).""", "rollout_lqr": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_lqr.hip: the iLQR backward pass
+# rollout_lqr_kernel<TASK, MODE, GYRO> (its matrices in lane-private LDS columns: one wavefront per CU) and the feedback
+# forward rollout_feedback_kernel<TASK, MODE> (DESIGN.md section 13)."""}
 
 
 def main(path, which="rollout_mlp"):
