@@ -127,6 +127,17 @@ class RolloutFeedbackIO(C.Structure):
                 ("actions_out_dev", C.c_void_p)]
 
 
+class RolloutMppiIO(C.Structure):
+    """Mirror of `struct cs_rollout_mppi_io` (cs_rollout_mppi_costs / cs_rollout_mppi_update)."""
+    _fields_ = [("struct_size", C.c_uint32), ("num_samples", C.c_int32), ("noise_stream", C.c_uint32),
+                ("x_ref_steps", C.c_uint32), ("lam", C.c_double), ("reward_weight", C.c_double),
+                ("sigma_dev", C.c_void_p), ("x_ref_dev", C.c_void_p), ("a_ref_dev", C.c_void_p),
+                ("Q_dev", C.c_void_p), ("Q_final_dev", C.c_void_p), ("R_dev", C.c_void_p),
+                ("costs_dev", C.c_void_p), ("best_dev", C.c_void_p), ("actions_out_dev", C.c_void_p),
+                ("ess_dev", C.c_void_p), ("cost_min_dev", C.c_void_p)]
+
+
+MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
 JAC_INTEGRATED, JAC_LANDED, JAC_CONTACT, JAC_LEVELING, JAC_CRASHED, JAC_RESET, JAC_CLIPPED = 1, 2, 4, 8, 16, 32, 64
@@ -196,6 +207,8 @@ SYMBOLS = {
     "cs_mlp_param_grad": (C.c_int, [_P, C.POINTER(MlpGradIO), _P]),
     "cs_rollout_lqr": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqrIO), _P]),
     "cs_rollout_feedback_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO), _P]),
+    "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
+    "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

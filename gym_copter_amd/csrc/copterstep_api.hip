@@ -329,6 +329,7 @@ int serve_make_stream(cs_ctx* ctx) {
 namespace cs {
 int report_error(int code, const char* message) { return fail(code, message); }
 int report_hip(hipError_t e, const char* what) { return hip_fail(e, what); }
+uint64_t context_seed(const cs_ctx* ctx) { return ctx->cfg.seed; }
 int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, ParamView* out) {
   const cs_config& g = ctx->cfg;
   if (g.action_arith == CS_ARITH_F32)

@@ -17,6 +17,8 @@ int enter_context(cs_ctx* ctx, const char* who, void* stream, ContextView* out);
 // (copterstep_api.hip) set cs_last_error() and return `code` / CS_ERR_HIP
 int report_error(int code, const char* message);
 int report_hip(hipError_t e, const char* what);
+// (copterstep_api.hip) the context's 64-bit seed (cs_seed): the MPPI noise key is a mix of it (mppi_noise.h)
+uint64_t context_seed(const cs_ctx* ctx);
 
 // (copterstep_rollout_grad.hip) the cs_rollout_io checks of cs_rollout_states / cs_rollout_vjp (vjp: the backward's),
 // made before the context; also those of cs_rollout_mlp_* (copterstep_rollout_mlp.hip)

@@ -1,0 +1,356 @@
+// copterstep_rollout_mppi.hip -- MPPI on gfx950 (cs_rollout_mppi_costs / cs_rollout_mppi_update, include/copterstep.h):
+// P noisy copies of an action tape rolled out per env with the cost accumulated in registers, and the cost-weighted
+// average of the perturbations.  Neither a state nor a noise value is written to memory: the noise is a counter-based
+// draw (mppi_noise.h) that the update makes again.  Nothing of the env state is written.  DESIGN.md section 14.
+//
+// Upstream lines replaced: lander.py:40-65 (the action loop) with sampled actions; the step is rollout_step
+// (rollout_step.h), the one cs_rollout_states runs.
+//
+// Costs: one lane per env on the tile layout of the step kernels (tile t -> workgroup t in x), the sample in grid y.
+// The loop is rollout_forward's (rollout_sweep.h) with the noise as the action source and no stores but one float64 per
+// lane at the end.  Update: one lane per env, the step in grid y; every wavefront recomputes its 64 envs' weights from
+// the cost columns ([P,N]: each row a coalesced load) and accumulates the A components of its step.
+#include <cmath>
+#include <string>
+
+#include "copterstep_jacobian.h"
+
+// the samples' states must be cs_rollout_states' bit for bit; the cost's float64 arithmetic is not contracted either
+#pragma clang fp contract(off)
+
+#include "dev_tile.h"
+#include "dev_codec.h"
+#include "dev_math.h"
+#include "dev_physics.h"
+#include "dev_task.h"
+#include "jacobian_tangents.h"
+#include "rollout_adjoint.h"
+#include "rollout_step.h"
+#include "mppi_noise.h"
+#include "dev_launch.h"
+
+namespace cs {
+namespace {
+
+// cs_rollout_mppi_io, checked, with the noise key of the context's seed
+struct MppiArgs {
+  const float* sigma;
+  const double* xref;
+  const double* aref;
+  const double* Q;
+  const double* Qf;  // Q at the last step (== Q without a Q_final)
+  const double* R;
+  double* costs;
+  int32_t* best;
+  float* out;
+  double* ess;
+  double* cost_min;
+  double lambda, wr;
+  uint32_t key, nonce, samples, xref_steps;
+};
+
+__device__ __forceinline__ bool finite64(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+// The cost's matrices in the LDS: the upper triangle of a symmetric D x D matrix, row-major (row i from tri_at(D, i)),
+// its diagonal halved, so that 1/2 d^T M d = sum_i d_i (M'_ii d_i + sum_{j > i} M_ij d_j).  Every lane reads the same
+// address (a broadcast).  Not through the scalar unit as cs_rollout_lqr's are: the step already holds every SGPR
+// (DevConst), and the 78 values' loads, hoisted out of the step loop, spilled 110-250 SGPRs into the vector file.
+constexpr int tri_at(int D, int i) { return i * D - i * (i - 1) / 2; }
+constexpr int tri_size(int D) { return D * (D + 1) / 2; }
+
+template <int D>
+__device__ __forceinline__ void stage_triangle(const double* M, double* dst, int lane) {
+#pragma clang loop unroll(disable)
+  for (int idx = lane; idx < D * D; idx += kBlock) {
+    const int i = idx / D, j = idx - i * D;
+    if (j >= i) dst[tri_at(D, i) + (j - i)] = i == j ? 0.5 * M[idx] : M[idx];
+  }
+}
+
+template <int D>
+__device__ __forceinline__ double half_quadratic(const double* tri, const double (&d)[D]) {
+  double s = 0.0;
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    double t = tri[tri_at(D, i)] * d[i];
+#pragma unroll
+    for (int j = i + 1; j < D; ++j) t += tri[tri_at(D, i) + (j - i)] * d[j];
+    s += d[i] * t;
+  }
+  return s;
+}
+
+// the task's motor fan-out of an action row, as load_action_at()
+template <int A>
+__device__ __forceinline__ float4 fan_out(const float (&a)[A]) {
+  if constexpr (A == 4)
+    return make_float4(a[0], a[1], a[2], a[3]);
+  else if constexpr (A == 2)
+    return make_float4(a[0], a[1], a[1], a[0]);
+  else
+    return make_float4(a[0], a[0], a[0], a[0]);
+}
+
+template <int TASK, int MODE>
+__global__ __launch_bounds__(kBlock, 2) void rollout_mppi_costs_kernel(const DevConst c, const DevState s,
+                                                                    const cs_rollout_io io, const MppiArgs m) {
+  constexpr int A = task_act_dim(TASK);
+  __shared__ __attribute__((aligned(16))) double wts[2 * tri_size(12) + tri_size(A)];  // Q, Q at the last step, R
+  const int lane = threadIdx.x;
+  const uint32_t tile_index = blockIdx.x, p = blockIdx.y;  // tile t -> workgroup t in x; the sample in y
+  stage_triangle<12>(m.Q, wts, lane);
+  stage_triangle<12>(m.Qf, wts + tri_size(12), lane);
+  stage_triangle<A>(m.R, wts + 2 * tri_size(12), lane);
+  __syncthreads();
+  const uint32_t i = tile_index * kBlock + threadIdx.x;
+  const uint32_t n = s.n;
+  const bool valid = i < n;
+  const uint32_t ii = valid ? i : 0u;  // (padding lanes roll env 0's actions out and store nothing)
+
+  Coef q = uniform_coef(c);
+  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
+  // the start point, decoded as rollout_forward decodes it
+  using TILE = TileIO<MODE>;
+  const TILE tile(s, tile_index, lane);
+  Env<MODE> e;
+  unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
+  resolve_episode<MODE>(c, tile, e);
+  double px, py, pz;
+  if (io.start_x_dev != nullptr) {
+    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
+    e.reset_pending = false;
+  } else {
+    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+  }
+
+  float sig[A];
+  double aref[A];
+#pragma unroll
+  for (int j = 0; j < A; ++j) {
+    sig[j] = m.sigma[j];
+    aref[j] = m.aref != nullptr ? m.aref[j] : 0.0;
+  }
+  const uint32_t gid = c.id_lo + ii;
+  const float* abar = io.actions_dev + (size_t)ii * A;
+  const size_t astep = (size_t)n * A;
+  const double* xr = m.xref + (size_t)ii * 12;
+  const size_t xstep = m.xref_steps ? (size_t)n * 12 : 0;
+  const int K = io.num_steps;
+  double S = 0.0;
+#pragma clang loop unroll(disable)
+  for (int k = 0; k < K; ++k) {
+    // the sample's action: abar + sigma eps in float32, one multiply and one add; sample 0 is abar itself
+    const float4 ab = load_action_at<TASK>(abar);
+    abar += astep;
+    const float abv[4] = {ab.x, ab.y, ab.z, ab.w};
+    float a[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) a[j] = abv[j];
+    if (p != 0u) {  // (uniform: the sample is the workgroup's)
+#pragma unroll
+      for (int j = 0; j < A; ++j) {
+        const float da = sig[j] * mppi_noise(m.key, gid, m.nonce, (uint32_t)k + 1u, p, (uint32_t)j);
+        a[j] = abv[j] + da;
+      }
+    }
+    const bool resetting = e.reset_pending;
+    double reward;
+    bool term, trunc;
+    rollout_step<TASK, MODE>(c, q, e, fan_out<A>(a), px, py, pz, reward, term, trunc);
+    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
+      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+    } else if (!e.pend) {
+      px = py = pz = -0.0;
+    }
+    // the step's cost terms, each added to S on its own
+    double dx[12], da[A];
+    const double2* xv = reinterpret_cast<const double2*>(xr);
+    xr += xstep;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const double2 v = xv[j];
+      dx[2 * j] = e.x[2 * j] - v.x;
+      dx[2 * j + 1] = e.x[2 * j + 1] - v.y;
+    }
+#pragma unroll
+    for (int j = 0; j < A; ++j) da[j] = (double)a[j] - aref[j];
+    // (the address is made opaque per step: the 166 loop-invariant reads would otherwise be hoisted into registers)
+    const double* w = wts;
+    asm volatile("" : "+v"(w));
+    S += half_quadratic<12>(k == K - 1 ? w + tri_size(12) : w, dx);
+    S += half_quadratic<A>(w + 2 * tri_size(12), da);
+    S -= m.wr * reward;
+  }
+  if (valid) m.costs[(size_t)p * n + i] = S;  // (64-bit: P x N doubles pass 4 GiB)
+}
+
+// best[i] = the arg-min over the finite costs of env i, the lowest index on ties, -1 if none is finite
+__global__ __launch_bounds__(kBlock) void mppi_best_kernel(uint32_t n, const MppiArgs m) {
+  const uint32_t tile = blockIdx.x;
+  const uint32_t i = tile * kBlock + threadIdx.x;
+  if (i >= n) return;
+  int32_t best = -1;
+  double beta = 0.0;
+#pragma clang loop unroll(disable)
+  for (uint32_t p = 0; p < m.samples; ++p) {
+    const double v = m.costs[(size_t)p * n + i];
+    if (finite64(v) && (best < 0 || v < beta)) {
+      best = (int32_t)p;
+      beta = v;
+    }
+  }
+  m.best[i] = best;
+}
+
+template <int TASK>
+__global__ __launch_bounds__(kBlock) void rollout_mppi_update_kernel(uint32_t n, uint32_t id_lo, const float* abar_dev,
+                                                                     const MppiArgs m) {
+  constexpr int A = task_act_dim(TASK);
+  const uint32_t tile = blockIdx.x, k0 = blockIdx.y;  // tile t -> workgroup t in x; step k0 + 1 in y
+  const uint32_t i = tile * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t gid = id_lo + i;
+  const uint32_t P = m.samples;
+  const double* col = m.costs + i;
+
+  bool any = false;
+  double beta = 0.0;
+#pragma clang loop unroll(disable)
+  for (uint32_t p = 0; p < P; ++p) {
+    const double v = col[(size_t)p * n];
+    if (finite64(v) && (!any || v < beta)) {
+      any = true;
+      beta = v;
+    }
+  }
+  float sig[A];
+#pragma unroll
+  for (int j = 0; j < A; ++j) sig[j] = m.sigma[j];
+  double eta = 0.0, eta2 = 0.0, acc[A];
+#pragma unroll
+  for (int j = 0; j < A; ++j) acc[j] = 0.0;
+  if (any) {
+#pragma clang loop unroll(disable)
+    for (uint32_t p = 0; p < P; ++p) {
+      const double v = col[(size_t)p * n];
+      const double w = finite64(v) ? exp(-(v - beta) / m.lambda) : 0.0;
+      eta += w;
+      eta2 += w * w;
+      if (p != 0u) {  // (sample 0 is the nominal: its perturbation is zero)
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+          const float da = sig[j] * mppi_noise(m.key, gid, m.nonce, k0 + 1u, p, (uint32_t)j);
+          acc[j] += w * (double)da;
+        }
+      }
+    }
+  }
+  const size_t at = ((size_t)k0 * n + i) * A;
+  const double inv_eta = 1.0 / eta;  // (eta >= 1 when any: the best sample's weight is exp(0))
+#pragma unroll
+  for (int j = 0; j < A; ++j) {
+    const float ab = abar_dev[at + j];
+    m.out[at + j] = any ? clip01((float)((double)ab + inv_eta * acc[j])) : ab;
+  }
+  if (k0 == 0u) {
+    if (m.ess != nullptr) m.ess[i] = any ? (eta * eta) / eta2 : 0.0;
+    if (m.cost_min != nullptr) m.cost_min[i] = any ? beta : __builtin_inf();
+  }
+}
+
+template <int TASK, int MODE>
+hipError_t mppi_costs_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const MppiArgs& m,
+                        hipStream_t stream) {
+  hipLaunchKernelGGL((rollout_mppi_costs_kernel<TASK, MODE>), dim3(grid_for(s.n), m.samples), dim3(kBlock), 0, stream,
+                     c, s, io, m);
+  return hipGetLastError();
+}
+
+template <int TASK, int MODE>
+hipError_t mppi_update_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const MppiArgs& m,
+                         hipStream_t stream) {
+  hipLaunchKernelGGL((rollout_mppi_update_kernel<TASK>), dim3(grid_for(s.n), (uint32_t)io.num_steps), dim3(kBlock), 0,
+                     stream, s.n, c.id_lo, io.actions_dev, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_mppi_costs(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                             const MppiArgs& m, hipStream_t stream) {
+  CS_DISPATCH(mppi_costs_t, c, s, io, m, stream)
+}
+
+hipError_t launch_mppi_update(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                              const MppiArgs& m, hipStream_t stream) {
+  CS_DISPATCH(mppi_update_t, c, s, io, m, stream)
+}
+
+// the checks both entry points share, made before the context
+int check_mppi_io(const cs_rollout_mppi_io* mio, const std::string& w) {
+  if (mio == nullptr) return report_error(CS_ERR_ARG, (w + ": null mio").c_str());
+  if (mio->struct_size != sizeof(cs_rollout_mppi_io))
+    return report_error(CS_ERR_ABI, (w + ": mio->struct_size " + std::to_string(mio->struct_size) + " != " +
+                                     std::to_string(sizeof(cs_rollout_mppi_io)) + " (sizeof(cs_rollout_mppi_io))").c_str());
+  if (mio->num_samples < 1 || mio->num_samples > CS_MPPI_MAX_SAMPLES)
+    return report_error(CS_ERR_ARG, (w + ": num_samples must be in [1, " + std::to_string(CS_MPPI_MAX_SAMPLES) +
+                                     "] (the sample index is the launch grid's y)").c_str());
+  if (mio->sigma_dev == nullptr || mio->costs_dev == nullptr)
+    return report_error(CS_ERR_ARG, (w + ": sigma_dev and costs_dev are required").c_str());
+  return CS_OK;
+}
+
+MppiArgs mppi_args(cs_ctx* ctx, const cs_rollout_mppi_io& o) {
+  return MppiArgs{o.sigma_dev, o.x_ref_dev, o.a_ref_dev, o.Q_dev, o.Q_final_dev != nullptr ? o.Q_final_dev : o.Q_dev,
+                  o.R_dev, o.costs_dev, o.best_dev, o.actions_out_dev, o.ess_dev, o.cost_min_dev, o.lam,
+                  o.reward_weight, mppi_noise_key(context_seed(ctx)), o.noise_stream, (uint32_t)o.num_samples,
+                  o.x_ref_steps};
+}
+
+}  // namespace
+}  // namespace cs
+
+extern "C" int cs_rollout_mppi_costs(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio,
+                                     void* stream) {
+  const char* who = "cs_rollout_mppi_costs";
+  if (int rc_ = cs::check_rollout_io(io, who, false)) return rc_;
+  if (int rc_ = cs::check_mppi_io(mio, who)) return rc_;
+  if (mio->x_ref_steps > 1u)
+    return cs::report_error(CS_ERR_ARG, "cs_rollout_mppi_costs: x_ref_steps must be 0 ([N,12]) or 1 ([K,N,12])");
+  if (mio->x_ref_dev == nullptr || mio->Q_dev == nullptr || mio->R_dev == nullptr)
+    return cs::report_error(CS_ERR_ARG, "cs_rollout_mppi_costs: x_ref_dev, Q_dev and R_dev are required");
+  if (!(mio->reward_weight >= 0.0) || !std::isfinite(mio->reward_weight))
+    return cs::report_error(CS_ERR_ARG, "cs_rollout_mppi_costs: reward_weight must be finite and >= 0");
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
+  const cs::MppiArgs m = cs::mppi_args(ctx, *mio);
+  hipError_t e = cs::launch_mppi_costs(v.task, v.mode, *v.c, *v.s, *io, m, (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mppi_costs: kernel launch");
+  if (m.best != nullptr) {
+    hipLaunchKernelGGL(cs::mppi_best_kernel, dim3(cs::grid_for(v.s->n)), dim3(cs::kBlock), 0, (hipStream_t)stream,
+                       v.s->n, m);
+    e = hipGetLastError();
+    if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mppi_costs: arg-min kernel launch");
+  }
+  return CS_OK;
+}
+
+extern "C" int cs_rollout_mppi_update(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio,
+                                      void* stream) {
+  const char* who = "cs_rollout_mppi_update";
+  if (int rc_ = cs::check_rollout_io(io, who, false)) return rc_;
+  if (int rc_ = cs::check_mppi_io(mio, who)) return rc_;
+  if (io->num_steps > CS_MPPI_MAX_SAMPLES)
+    return cs::report_error(CS_ERR_ARG, "cs_rollout_mppi_update: num_steps must be <= CS_MPPI_MAX_SAMPLES (the step "
+                                        "index is the launch grid's y)");
+  if (!(mio->lam > 0.0) || !std::isfinite(mio->lam))
+    return cs::report_error(CS_ERR_ARG, "cs_rollout_mppi_update: lambda must be finite and > 0");
+  if (mio->actions_out_dev == nullptr)
+    return cs::report_error(CS_ERR_ARG, "cs_rollout_mppi_update: actions_out_dev is required");
+  if (mio->actions_out_dev == io->actions_dev)
+    return cs::report_error(CS_ERR_ARG, "cs_rollout_mppi_update: actions_out_dev must not alias io->actions_dev");
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
+  const hipError_t e = cs::launch_mppi_update(v.task, v.mode, *v.c, *v.s, *io, cs::mppi_args(ctx, *mio),
+                                              (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mppi_update: kernel launch");
+  return CS_OK;
+}

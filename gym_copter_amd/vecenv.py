@@ -97,6 +97,9 @@ MlpRollout = collections.namedtuple("MlpRollout", "x reward terminated truncated
 # CopterVecEnv.rollout_lqr's result: the time-varying gains K [K,N,A,12] and d [K,N,A], the model's predicted cost change
 # dV [N,2], the value model at the start S0 [N,12,12], s0 [12,N], and ok [N] bool (every Cholesky pivot positive)
 LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
+# CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
+MppiCosts = collections.namedtuple("MppiCosts", "costs best")
+MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
 
 
 def _torch():
@@ -1316,9 +1319,10 @@ class CopterVecEnv(_VectorEnvBase):
         return gp, ga, g0
 
     # -- the iLQR backward pass and its line-search forward --------
-    def _lqr_weights(self, Q, R, Q_final):
-        """Q [12,12], R [A,A], Q_final [12,12] or None, checked on the host (symmetric, finite; R's diagonal > 0) and
-        kept on the device: the same values are uploaded once (the iLQR driver passes them every iteration)."""
+    def _lqr_weights(self, Q, R, Q_final, definite=True):
+        """Q [12,12], R [A,A], Q_final [12,12] or None, checked on the host (symmetric, finite; R's diagonal > 0, or
+        >= 0 with definite=False: MPPI inverts nothing) and kept on the device: the same values are uploaded once (the
+        iLQR and MPPI drivers pass them every iteration)."""
         torch = _torch()
         ad = self.action_dim
 
@@ -1333,8 +1337,10 @@ class CopterVecEnv(_VectorEnvBase):
             return np.ascontiguousarray(a)
         q = host(Q, (12, 12), "Q")
         r = host(R, (ad, ad), "R")
-        if not (np.diag(r) > 0).all():
+        if definite and not (np.diag(r) > 0).all():
             raise ValueError("R must be positive definite: its diagonal must be > 0")
+        if not (np.diag(r) >= 0).all():
+            raise ValueError("R must be positive semidefinite: its diagonal must be >= 0")
         qf = None if Q_final is None else host(Q_final, (12, 12), "Q_final")
         key = (q.tobytes(), r.tobytes(), None if qf is None else qf.tobytes())
         cache = getattr(self, "_lqr_w", None)
@@ -1447,6 +1453,130 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_rollout_feedback_states(self._ctx, C.byref(io), C.byref(fio), self._stream()))
         self._keep = keep + [xbar, Kg, d]
         return ro, acts
+
+    # -- MPPI: sampled rollouts, their costs and the weighted update --------
+    def _mppi_small(self, v, name, dtype, nonneg):
+        """sigma / a_ref: a scalar or [A] values, checked on the host and kept on the device: the same values are
+        uploaded once (the MPPI driver passes them every iteration)."""
+        torch = _torch()
+        ad = self.action_dim
+        a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+        if a.shape not in ((), (ad,)):
+            raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (name, ad, a.shape))
+        a = np.ascontiguousarray(np.broadcast_to(a, (ad,))).astype(dtype)
+        if not np.isfinite(a).all() or (nonneg and not (a >= 0).all()):
+            raise ValueError("%s must be finite%s" % (name, " and >= 0" if nonneg else ""))
+        cache = getattr(self, "_mppi_c", None)
+        if cache is None:
+            cache = self._mppi_c = {}
+        hit = cache.get(name)
+        if hit is None or hit[0] != a.tobytes():
+            hit = cache[name] = (a.tobytes(), torch.from_numpy(a).to(self.device))
+        return hit[1]
+
+    @staticmethod
+    def _mppi_stream(stream):
+        if not isinstance(stream, (int, np.integer)) or isinstance(stream, bool) or not 0 <= int(stream) < 1 << 32:
+            raise ValueError("stream must be an int in [0, 2**32), got %r" % (stream,))
+        return int(stream)
+
+    def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
+                           stream=0, state=None):
+        """The costs of P = `samples` noisy copies of the action tape `actions` [K,N,A] per env, one kernel: sample p
+        takes a_k = actions[k-1] + sigma * eps(p, k) in float32 (one multiply, one add), eps the library's counter-based
+        noise -- Irwin-Hall of order 4, mean 0, variance 1 - 2**-32, a pure function of (seed, global env id, `stream`,
+        k, p, component): tests/mppi_ref.py restates it in NumPy bit for bit -- and sample 0 is `actions` itself.  Each
+        copy is rolled out as rollout_states would (same start rules: state=None or get_state()'s layout; the step clips
+        the motors itself) and scored in float64, in registers:
+
+            S = sum_k 1/2 (x_k - x_ref)^T Q_k (x_k - x_ref) + 1/2 (a_k - a_ref)^T R (a_k - a_ref) - reward_weight reward_k
+
+        with Q_K = Q_final when given.  sigma: a scalar or [A], >= 0; x_ref: [12], [N,12] or [K,N,12]; Q [12,12] and
+        R [A,A] symmetric positive semidefinite, shared; a_ref [A] or None (zero); reward_weight >= 0 brings in the
+        task's own reward (rollout_states' float64 reward); `stream` is a nonce in [0, 2**32), for example the MPC
+        iteration.  No state tape and no noise tensor exist.
+
+        Returns MppiCosts(costs [P,N] float64, best [N] int32: the arg-min over the env's finite costs, the lowest index
+        on ties, -1 if none is finite).  Asynchronous on the current stream; the tensors are buffers of this env,
+        overwritten by its next call with the same P.  No env state changes."""
+        self._check_open()
+        torch = _torch()
+        if not isinstance(samples, (int, np.integer)) or isinstance(samples, bool) \
+                or not 1 <= int(samples) <= _lib.MPPI_MAX_SAMPLES:
+            raise ValueError("samples must be an int in [1, %d], got %r" % (_lib.MPPI_MAX_SAMPLES, samples))
+        P = int(samples)
+        wr = float(reward_weight)
+        if not (wr >= 0.0) or wr == float("inf"):
+            raise ValueError("reward_weight must be finite and >= 0, got %r" % (reward_weight,))
+        Qd, Rd, Qfd = self._lqr_weights(Q, R, Q_final, definite=False)
+        sg = self._mppi_small(sigma, "sigma", np.float32, True)
+        ar = None if a_ref is None else self._mppi_small(a_ref, "a_ref", np.float64, False)
+        io, K, keep = self._rollout_io(actions, state)
+        n, dev = self.num_envs, self.device
+        xr = x_ref if isinstance(x_ref, torch.Tensor) else torch.from_numpy(np.asarray(x_ref, dtype=np.float64))
+        if tuple(xr.shape) == (12,):
+            xr = xr.expand(n, 12)
+        if tuple(xr.shape) not in ((n, 12), (K, n, 12)) or not xr.dtype.is_floating_point:
+            raise ValueError("x_ref must be a floating-point array of shape (12,), (%d, 12) or (%d, %d, 12), got %s"
+                             % (n, K, n, tuple(xr.shape)))
+        xr = xr.detach().to(device=dev, dtype=torch.float64).contiguous()
+        keep.append(xr)
+        mio = _lib.RolloutMppiIO()
+        mio.struct_size = C.sizeof(_lib.RolloutMppiIO)
+        mio.num_samples, mio.noise_stream = P, self._mppi_stream(stream)
+        mio.x_ref_steps = 1 if xr.dim() == 3 else 0
+        mio.reward_weight = wr
+        mio.sigma_dev, mio.x_ref_dev = sg.data_ptr(), xr.data_ptr()
+        mio.a_ref_dev = None if ar is None else ar.data_ptr()
+        mio.Q_dev, mio.R_dev = Qd.data_ptr(), Rd.data_ptr()
+        mio.Q_final_dev = None if Qfd is None else Qfd.data_ptr()
+        out = self._rollout_cache(("mppi_costs", P), lambda: MppiCosts(
+            torch.empty((P, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)))
+        mio.costs_dev, mio.best_dev = out.costs.data_ptr(), out.best.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_mppi_costs(self._ctx, C.byref(io), C.byref(mio), self._stream()))
+        self._keep = keep + [Qd, Rd, Qfd, sg, ar]
+        return out
+
+    def rollout_mppi_update(self, actions, costs, sigma, lam, stream=0):
+        """The MPPI update, one kernel: per env, with beta = its minimum finite cost, w_p = exp(-(costs[p] - beta) / lam)
+        (0 for a cost that is not finite) and eta = sum_p w_p,
+
+            actions_out[k-1] = clip01(float32(actions[k-1] + (1 / eta) sum_p w_p sigma eps(p, k)))
+
+        in float64 with p ascending, eps drawn again from the counter: `costs` [P,N] float64 is what
+        rollout_mppi_costs(actions, sigma, P, ..., stream=stream) returned for the same actions, sigma and stream.
+        lam > 0 is the temperature.  Returns MppiUpdate(actions [K,N,A] float32, ess [N] float64 = eta^2 / sum_p w_p^2:
+        the effective sample size, cost_min [N] = beta).  An env without a finite cost keeps its actions (the same
+        bits) and reports ess = 0, cost_min = inf.  Every sum runs inside one lane in a fixed order: two calls give the
+        same bits.  Asynchronous on the current stream; the tensors are buffers of this env (two sets, so that the
+        result of one call can be the `actions` of the next), overwritten by its second next call with the same K.  No
+        env state changes."""
+        self._check_open()
+        torch = _torch()
+        lam = float(lam)
+        if not (lam > 0.0) or lam == float("inf"):
+            raise ValueError("lam must be finite and > 0, got %r" % (lam,))
+        sg = self._mppi_small(sigma, "sigma", np.float32, True)
+        io, K, keep = self._rollout_io(actions, None)
+        n, ad, dev = self.num_envs, self.action_dim, self.device
+        if not isinstance(costs, torch.Tensor) or costs.dim() != 2 or not 1 <= costs.shape[0] <= _lib.MPPI_MAX_SAMPLES:
+            raise ValueError("costs must be the [P,%d] float64 device tensor of rollout_mppi_costs" % n)
+        P = int(costs.shape[0])
+        self._check_tape("rollout_mppi_costs", (costs, "costs", (P, n), torch.float64))
+        sets = self._rollout_cache(("mppi_update", K), lambda: [MppiUpdate(
+            torch.empty((K, n, ad), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+            torch.empty(n, dtype=torch.float64, device=dev)) for _ in range(2)])
+        out = sets[1] if sets[0].actions.data_ptr() == io.actions_dev else sets[0]
+        mio = _lib.RolloutMppiIO()
+        mio.struct_size = C.sizeof(_lib.RolloutMppiIO)
+        mio.num_samples, mio.noise_stream, mio.lam = P, self._mppi_stream(stream), lam
+        mio.sigma_dev, mio.costs_dev = sg.data_ptr(), costs.data_ptr()
+        mio.actions_out_dev, mio.ess_dev, mio.cost_min_dev = (t.data_ptr() for t in out)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_mppi_update(self._ctx, C.byref(io), C.byref(mio), self._stream()))
+        self._keep = keep + [sg, costs]
+        return out
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

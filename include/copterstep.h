@@ -37,6 +37,9 @@
  *                            rollout's tape                      counterpart: a second-order trajectory optimiser)
  *   cs_rollout_feedback_states  cs_rollout_states under the     lander.py:40-65 with a time-varying affine feedback
  *                            feedback that pass returns          in place of the random action
+ *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
+ *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
+ *   cs_rollout_mppi_update   their cost-weighted average         (the same)
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -814,6 +817,73 @@ typedef struct cs_rollout_feedback_io {
   float* actions_out_dev;      /* [K,N,A] float32, required */
 } cs_rollout_feedback_io;
 int cs_rollout_feedback_states(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_feedback_io* fio, void* stream);
+
+/* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
+ * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,
+ * tilt, the motor clip).  For every env, P perturbed copies of the nominal action tape abar = io->actions_dev [K,N,A] are
+ * rolled out for K steps and scored (cs_rollout_mppi_costs); the cost-weighted average of the perturbations then replaces
+ * the nominal (cs_rollout_mppi_update).  Neither the states nor the noise touch memory: the cost accumulates in registers,
+ * and the noise is a counter-based draw that the update makes again.
+ *
+ * Noise.  Sample p in [0, P), step k in [1, K], action component j in [0, A), the env with global id g (cs_config.
+ * env_id_base + local index), the caller's nonce mio->noise_stream (for example the MPC iteration): ONE Philox2x32-10
+ * call with counter = (g, noise_stream) and key = key_noise + (((k - 1) << 16) + p) * 4 + j (mod 2^32) gives 64 bits;
+ * key_noise = lo32(splitmix64(splitmix64(seed))), a third mix of the seed beside the two keys of cs_seed.  Its four
+ * 16-bit halves u0..u3 give the exact integer T = u0 + u1 + u2 + u3 - 131070 and
+ *     eps = (float)T * CS_MPPI_NOISE_SCALE          (one float32 multiply; CS_MPPI_NOISE_SCALE = fl32(sqrt(3) 2^-16))
+ * -- Irwin-Hall of order 4: mean 0, variance 1 - 2^-32, support +-3.46.  It is a pure function of (seed, g, noise_stream,
+ * k, p, j): independent of the batch size, the sharding, P and the launch history (keys are distinct for k <= 16 384).
+ * Sample actions.  a(p)[k][j] = abar[k][j] + sigma[j] * eps(p, k, j) in float32, one multiply and one add, not fused;
+ * sample 0 is the nominal itself, a(0) = abar bit for bit, so costs[0] is the cost of the unperturbed plan.  sigma_dev [A]
+ * float32, each >= 0 (the caller's to guarantee), shared by all envs.  The step clips motors to [0, 1] itself, as always.
+ * Cost.  With x_k, reward_k what cs_rollout_states returns for that action tape from the same start, in float64 without
+ * contraction,
+ *     S = sum_{k=1..K} [ 1/2 (x_k - xref_k)^T Q_k (x_k - xref_k) + 1/2 (a_k - aref)^T R (a_k - aref) - w_r reward_k ]
+ * Q_k = Q_dev [12,12], Q_final_dev at k = K when given; R_dev [A,A]; both symmetric (their upper triangles are read),
+ * shared; a_k is the sample's float32 action before the clip; aref = a_ref_dev [A] float64 or NULL = 0; xref = x_ref_dev,
+ * [N,12] (x_ref_steps = 0) or [K,N,12] (x_ref_steps = 1); w_r = reward_weight >= 0 brings in the task's own reward.
+ *
+ * cs_rollout_mppi_costs writes costs_dev [P,N] float64 and, when best_dev != NULL, best_dev [N] int32: the arg-min over
+ * the finite costs of the env, the lowest index on ties, -1 if none is finite.  The start point -- stored or explicit, the
+ * pending perturbation, a pending NEXT_STEP reset, the step counter -- is cs_rollout_states'; io's outputs, cotangents and
+ * gradients are not used.  No env state is written.
+ * cs_rollout_mppi_update reads costs_dev [P,N] and, per env: beta = the minimum finite cost; w_p = exp(-(S_p - beta) /
+ * lambda) for a finite S_p, else 0; eta = sum_p w_p;
+ *     actions_out[k][j] = clip01( fl32( (double)abar[k][j] + (1 / eta) sum_p w_p (double)(sigma[j] * eps(p, k, j)) ) )
+ * with float64 sums over p ascending (sigma[j] * eps is the float32 product of the sample actions; the p = 0 term is 0)
+ * and eps drawn again from the counter.  It writes actions_out_dev [K,N,A] float32 (must not alias io->actions_dev),
+ * ess_dev [N] float64 = eta^2 / sum_p w_p^2 and cost_min_dev [N] = beta (each of the two may be NULL).  An env without a
+ * finite cost keeps its abar (the same bits) and reports ess = 0, cost_min = +inf.  lambda > 0, finite.  The call reads
+ * io->actions_dev and io->num_steps only (the start point plays no part); P, sigma and noise_stream must be those of the
+ * cs_rollout_mppi_costs call that made costs_dev.
+ * Every reduction runs inside one lane in a fixed order (no atomics, no cross-lane sums): two calls give the same bits.
+ * P <= CS_MPPI_MAX_SAMPLES and (update) K <= CS_MPPI_MAX_SAMPLES: the sample and step indices are the launch grid's y.
+ * Asynchronous on `stream`; mio->struct_size must be sizeof(cs_rollout_mppi_io) (else CS_ERR_ABI); both blocks are
+ * checked before the context.  The shared matrices are read by the scalar unit: 8-B aligned (sigma_dev 4-B), never
+ * written while a call runs; x_ref_dev is 16-B aligned. */
+#define CS_MPPI_MAX_SAMPLES 65535
+#define CS_MPPI_NOISE_SCALE 0x1.bb67aep-16f
+typedef struct cs_rollout_mppi_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_mppi_io) */
+  int32_t num_samples;         /* P in [1, CS_MPPI_MAX_SAMPLES] */
+  uint32_t noise_stream;       /* the nonce of the noise */
+  uint32_t x_ref_steps;        /* 0: x_ref_dev is [N,12]; 1: [K,N,12] */
+  double lam;                  /* update: lambda, the temperature, > 0 and finite */
+  double reward_weight;        /* costs: w_r >= 0, finite */
+  const float* sigma_dev;      /* [A] float32, required */
+  const double* x_ref_dev;     /* costs: required */
+  const double* a_ref_dev;     /* costs: [A] float64 or NULL = zero */
+  const double* Q_dev;         /* costs: [12,12], required */
+  const double* Q_final_dev;   /* costs: [12,12] or NULL */
+  const double* R_dev;         /* costs: [A,A], required */
+  double* costs_dev;           /* [P,N]: written by _costs, read by _update (required) */
+  int32_t* best_dev;           /* costs: [N] or NULL */
+  float* actions_out_dev;      /* update: [K,N,A], required */
+  double* ess_dev;             /* update: [N] or NULL */
+  double* cost_min_dev;        /* update: [N] or NULL */
+} cs_rollout_mppi_io;
+int cs_rollout_mppi_costs(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio, void* stream);
+int cs_rollout_mppi_update(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio, void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in

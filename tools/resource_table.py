@@ -3,7 +3,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
 
     python3 tools/resource_table.py remarks.txt > profiles/rollout_mlp_resources.txt
     python3 tools/resource_table.py remarks.txt mlp_grad > profiles/mlp_grad_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_lqr > profiles/rollout_lqr_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_lqr > profiles/rollout_lqr_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_mppi > profiles/rollout_mppi_resources.txt"""
 import re
 import sys
 
@@ -36,7 +37,10 @@ HEADS = {"rollout_mlp": """\
 # and mlp_grad_sum_kernel, the sum of its workgroups' partials (DESIGN.md section 12).""", "rollout_lqr": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_lqr.hip: the iLQR backward pass
 # rollout_lqr_kernel<TASK, MODE, GYRO> (its matrices in lane-private LDS columns: one wavefront per CU) and the feedback
-# forward rollout_feedback_kernel<TASK, MODE> (DESIGN.md section 13)."""}
+# forward rollout_feedback_kernel<TASK, MODE> (DESIGN.md section 13).""", "rollout_mppi": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_mppi.hip: the sampled rollouts' costs
+# rollout_mppi_costs_kernel<TASK, MODE> (the cost's matrices in 1.3 KiB of LDS), the arg-min mppi_best_kernel and the
+# weighted update rollout_mppi_update_kernel<TASK> (DESIGN.md section 14)."""}
 
 
 def main(path, which="rollout_mlp"):
