@@ -5,8 +5,10 @@ straight-through).  Every env's 2 x (12 + K A + P) perturbed copies -- of x0, of
 oracle batch, each lane with its own theta."""
 import numpy as np
 
-from oracle.refcpu import DJI_PHANTOM, G, task_action_dim
+from oracle.refcpu import DJI_PHANTOM, G, VehicleParams, task_action_dim
 from oracle.refvec import VecOracle
+
+from jacobian_fd import VEHICLE_FIELDS, _tile
 
 
 # (first observed state slot, obs_dim) of each task: gym_copter_amd.vecenv._TASK_SHAPES
@@ -34,15 +36,16 @@ def policy64(params, obs, hidden, act_dim):
     return np.einsum("chl,lh->lc", W2, h) + b2.T
 
 
-def oracle_mlp_rollout(task, x, status, params, hidden, K, offsets=None, substeps=1, vp=DJI_PHANTOM, g=G, steps=1):
+def oracle_mlp_rollout(task, x, status, params, hidden, K, offsets=None, substeps=1, vp=DJI_PHANTOM, g=G, steps=1,
+                       mars=None):
     """K closed-loop steps of VecOracle(task, auto-reset disabled, float64 storage) from x [12,n] / status [n]
-    (prev_shaping = shaping(x0)); params [P] or [P,n]; offsets [K,n,A] or None.  Returns (x [K,n,12], reward [K,n],
-    obs [K,n,OBS] (o_{k-1}), actions [K,n,A])."""
+    (prev_shaping = shaping(x0)); params [P] or [P,n]; offsets [K,n,A] or None; vp / g / mars as VecOracle takes them
+    (fields may be arrays [n]).  Returns (x [K,n,12], reward [K,n], obs [K,n,OBS] (o_{k-1}), actions [K,n,A])."""
     x = np.asarray(x, dtype=np.float64)
     n = x.shape[1]
     first, od = OBS_SHAPE[task]
     A = task_action_dim(task)
-    orc = VecOracle(task, n, vp=vp, substeps=substeps, store_mode="float64", g=g)
+    orc = VecOracle(task, n, vp=vp, substeps=substeps, store_mode="float64", g=g, mars=mars)
     orc.x[:] = x
     orc.status[:] = np.asarray(status, dtype=np.uint8)
     orc.steps[:] = steps
@@ -62,9 +65,10 @@ def oracle_mlp_rollout(task, x, status, params, hidden, K, offsets=None, substep
 
 
 def fd_mlp_rollout_vjp(task, x, status, params, hidden, K, offsets=None, gx=None, gr=None, substeps=1, h_x=1e-6,
-                       h_u=1e-6, h_p=1e-6):
-    """Central differences of L = sum(gx * X) + sum(gr * R) over oracle_mlp_rollout.  Returns (g_params [P] summed over
-    the envs, g_u [K,n,A], g_x0 [12,n])."""
+                       h_u=1e-6, h_p=1e-6, vp=DJI_PHANTOM, g=G, mars=None):
+    """Central differences of L = sum(gx * X) + sum(gr * R) over oracle_mlp_rollout; vp / g / mars (fields may be arrays
+    [n]) are tiled over the perturbed copies as tests/rollout_fd.py tiles them.  Returns (g_params [P] summed over the
+    envs, g_u [K,n,A], g_x0 [12,n])."""
     x = np.asarray(x, dtype=np.float64)
     n = x.shape[1]
     A = task_action_dim(task)
@@ -73,6 +77,8 @@ def fd_mlp_rollout_vjp(task, x, status, params, hidden, K, offsets=None, gx=None
     u = np.zeros((K, n, A)) if offsets is None else np.asarray(offsets, np.float64)
     D = 12 + K * A + P
     reps = 2 * D                                    # lane = (2 d + s) n + env, s = 0: +h, 1: -h
+    vpl = VehicleParams(**{k: _tile(getattr(vp, k), reps) for k in VEHICLE_FIELDS})
+    marsl = None if mars is None else tuple(_tile(m, reps) for m in mars)
     X = np.tile(x, (1, reps))
     U = np.tile(u, (1, reps, 1))
     Pl = np.repeat(params[:, None], reps * n, axis=1)
@@ -87,7 +93,7 @@ def fd_mlp_rollout_vjp(task, x, status, params, hidden, K, offsets=None, gx=None
             else:
                 Pl[d - 12 - K * A, sl] += sign * h_p
     xs, rs, _, _ = oracle_mlp_rollout(task, X, np.tile(np.asarray(status, np.uint8), reps), Pl, hidden, K, offsets=U,
-                                      substeps=substeps)
+                                      substeps=substeps, vp=vpl, g=_tile(g, reps), mars=marsl)
     L = np.zeros(reps * n)
     if gx is not None:
         L += np.einsum("knj,knj->n", xs, np.tile(np.asarray(gx, dtype=np.float64), (1, reps, 1)))

@@ -3,10 +3,14 @@ cs_rollout_mlp_vjp_ex; CopterVecEnv.mlp_param_grad, rollout_mlp_vjp(g_actions_in
 differentiable_mlp_rollout(action_grad=, reduce=)): the device reduction against gym_copter_amd.mlp.param_grad within a
 derived summation bound, bit-for-bit determinism, no cotangent = the plain backward, the cotangent against chained
 step Jacobians and against central differences of the float64 oracle (tests/mlp_action_fd.py), a resetting lane,
-autograd, policy training with an effort penalty, offsets past 4 GiB, the sharded passthrough and errors."""
+autograd, policy training with an effort penalty, offsets past 4 GiB, the sharded passthrough and errors.  The cotangent
+chain and the plain-backward identity also run under the rotor-gyro models of tests/model_variants.py."""
+import zlib
+
 import numpy as np
 import pytest
 
+import model_variants
 from gpu_util import have_gpu, to_np
 from jacobian_fd import hover_action
 from mlp_action_fd import fd_mlp_action_vjp
@@ -26,12 +30,13 @@ def _env(task, n, mode="float64", autoreset="disabled", **kw):
     return gym_copter_amd.CopterVecEnv(task=task, num_envs=n, state_dtype=mode, autoreset_mode=autoreset, **kw)
 
 
-def _theta(task, hidden, seed, scale=0.1, env=None):
-    """A policy near hover: the output bias is the hover motor value, the output weights small."""
+def _theta(task, hidden, seed, scale=0.1, env=None, bias=None):
+    """A policy near hover: the output bias is the hover motor value (`bias`: that of a model variant), the output
+    weights small."""
     import torch
     from gym_copter_amd import mlp
     p = mlp.init(OBS_SHAPE[task][1], TASK_A[task], hidden, generator=torch.Generator().manual_seed(seed),
-                 out_bias=hover_action(), out_scale=scale)
+                 out_bias=hover_action() if bias is None else bias, out_scale=scale)
     return p if env is None else p.to(env.device)
 
 
@@ -200,24 +205,30 @@ def test_device_reduction_is_deterministic_and_overwrites():
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. no cotangent gives the plain backward
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("task,hidden", [("lander3d", 0), ("lander3d", 32), ("hover3d", 16)])
-def test_no_cotangent_is_the_plain_backward(task, hidden):
+@pytest.mark.parametrize("task,hidden,variant", [
+    pytest.param("lander3d", 0, None, id="lander3d-0"), pytest.param("lander3d", 32, None, id="lander3d-32"),
+    pytest.param("hover3d", 16, None, id="hover3d-16"), ("lander3d", 32, "gyro_only")])
+def test_no_cotangent_is_the_plain_backward(task, hidden, variant):
     """cs_rollout_mlp_vjp_ex with no block, with a block whose cotangent is NULL, and with an all-zero cotangent, all
-    against cs_rollout_mlp_vjp itself."""
+    against cs_rollout_mlp_vjp itself.  Under gyro_only the two sides are the rotor-gyro backward kernel with and
+    without the cotangent."""
     import ctypes as C
     import torch
     from gym_copter_amd import _lib
     n, K, A = 3000, 12, 4
     rng = np.random.default_rng(hidden)
-    env = _env(task, n, "float32", seed=6)
+    env = _env(task, n, "float32", seed=6, **model_variants.env_kwargs(variant))
     try:
+        model_variants.install(variant, env, rng)
         env.reset()
         x, st = _point(n, rng)
         state = {"x": x.astype(np.float32).astype(np.float64), "status": st}
-        p = _theta(task, hidden, 4, scale=0.3, env=env)
+        p = _theta(task, hidden, 4, scale=0.3, env=env, bias=model_variants.hover(variant))
         gx, gr = _dev(rng.standard_normal((K, n, 12)), env), _dev(rng.standard_normal((K, n)), env)
         r = env.rollout_mlp_states(p, K, hidden, state=state)
         r = type(r)(*(t.clone() for t in r))
+        if variant is not None:
+            model_variants.assert_differs_from_default(variant, r.x, task, "float32", 1, state, r.actions)
         # the plain entry point, called as the parent's rollout_mlp_vjp called it
         io, _, keep = env._rollout_io(None, state, K)
         mio, _ = env._mlp_io(p, hidden, K, None, keep)
@@ -261,18 +272,25 @@ def _policy_jac(theta, hidden, obs, A):
     return np.einsum("ch,nh,hj->ncj", p["W2"], 1 - h * h, p["W1"])
 
 
-@pytest.mark.parametrize("task,hidden", [("lander3d", 0), ("lander3d", 32), ("hover3d", 16)])
-def test_cotangent_equals_chained_step_jacobians_and_policy_jacobian(task, hidden):
+SPREAD_INERTIA = ("vehicles", "vehicles_mars_gyro")    # motors near hover there: see tests/test_gpu_rollout_mlp.py
+
+
+@pytest.mark.parametrize("task,hidden,variant", [
+    pytest.param("lander3d", 0, None, id="lander3d-0"), pytest.param("lander3d", 32, None, id="lander3d-32"),
+    pytest.param("hover3d", 16, None, id="hover3d-16"), ("lander3d", 32, "mars_gyro"), ("hover3d", 0, "vehicles_mars_gyro")])
+def test_cotangent_equals_chained_step_jacobians_and_policy_jacobian(task, hidden, variant):
     """The construction of test_gradient_equals_chained_step_jacobians_and_policy_jacobian (test_gpu_rollout_mlp: 2 048
     envs, K = 24, LANDED lanes, clipped actions, an explicit start) with want[k] += gact[k]: g_u, g_x0 and g_theta (the
-    device reduction) within 1e-9 scaled."""
+    device reduction) within 1e-9 scaled.  Under a model variant (600 envs, as there) this is the rotor-gyro backward
+    kernel with a cotangent, and the x tape differs from the default model's on the same action tape."""
     import torch
     from gym_copter_amd import mlp
-    n, K, A = 2048, 24, 4
+    n, K, A = 2048 if variant is None else 600, 24, 4
     first, od = OBS_SHAPE[task]
-    rng = np.random.default_rng(31 + hidden)
-    env = _env(task, n, "float32", seed=4)
+    rng = np.random.default_rng(31 + hidden if variant is None else zlib.crc32(repr((task, hidden, variant)).encode()))
+    env = _env(task, n, "float32", seed=4, **model_variants.env_kwargs(variant))
     try:
+        model_variants.install(variant, env, rng)
         env.reset()
         x, st = _point(n, rng)
         x = x.astype(np.float32).astype(np.float64)
@@ -280,12 +298,19 @@ def test_cotangent_equals_chained_step_jacobians_and_policy_jacobian(task, hidde
         x[4, :q], x[5, :q], st[:q] = 0.0, 0.0, LANDED
         u = np.zeros((K, n, A), np.float32)
         u[:, q:2 * q] = rng.uniform(-0.8, 0.8, (K, q, A))                     # some clipped
+        scale = 0.3
+        if variant in SPREAD_INERTIA:
+            ah = model_variants.hover(variant)
+            u[:, q:2 * q] = ah * rng.uniform(-2.0, 2.0, (K, q, A))            # some clipped, at 0 only
+            scale = (0.003 if hidden else 0.0015) * ah / hover_action()
         state = {"x": x, "status": st}
-        p = _theta(task, hidden, 5, scale=0.3, env=env)
+        p = _theta(task, hidden, 5, scale=scale, env=env, bias=model_variants.hover(variant))
         gx, gr = rng.standard_normal((K, n, 12)), rng.standard_normal((K, n))
         gact = rng.standard_normal((K, n, A))
         r = env.rollout_mlp_states(p, K, hidden, offsets=_dev(u, env), state=state)
         r = type(r)(*(t.clone() for t in r))
+        if variant is not None:
+            model_variants.assert_differs_from_default(variant, r.x, task, "float32", 1, state, r.actions)
         gp, ga, g0 = env.rollout_mlp_vjp(p, r, gx=_dev(gx, env), gr=_dev(gr, env), state=state, hidden=hidden,
                                          g_actions_in=_dev(gact, env), reduce="device")
         gp, ga, g0 = to_np(gp).copy(), to_np(ga).copy(), to_np(g0).copy()
@@ -315,7 +340,8 @@ def test_cotangent_equals_chained_step_jacobians_and_policy_jacobian(task, hidde
             lam = new
         wp = mlp.param_grad(p.cpu(), hidden, torch.from_numpy(obs), torch.from_numpy(want)).numpy()
         errs = (_scaled(ga, want), _scaled(g0, lam.T), float(np.max(np.abs(gp - wp) / np.maximum(1.0, np.abs(wp)))))
-        print("chained Jacobians with a cotangent %s H=%d: g_u %.2e g_x0 %.2e g_theta %.2e" % ((task, hidden) + errs))
+        print("chained Jacobians with a cotangent %s H=%d%s: g_u %.2e g_x0 %.2e g_theta %.2e"
+              % ((task, hidden, " " + variant if variant else "") + errs))
         assert max(errs) <= 1e-9, errs
     finally:
         env.close()

@@ -1,13 +1,17 @@
 """The iLQR backward pass and feedback rollout on the device (cs_rollout_lqr / cs_rollout_feedback_states,
 CopterVecEnv.rollout_lqr / rollout_feedback_states, gym_copter_amd.ilqr): the gains against the NumPy recursion
 (tests/lqr_ref.py) on the chained step_jacobian blocks, the Cholesky's failure path on the host, the feedback forward
-bit for bit, the model's first-order consistency, the iLQR driver against a first-order baseline, and the plumbing."""
+bit for bit, the model's first-order consistency, the iLQR driver against a first-order baseline, and the plumbing;
+the gains and the feedback forward also under the non-default vehicle models of tests/model_variants.py."""
 import os
 import subprocess
+
+import zlib
 
 import numpy as np
 import pytest
 
+import model_variants
 from gpu_util import have_gpu, to_np
 from jacobian_fd import hover_action
 from lqr_ref import chol_solve, cholesky, feedback_actions, lqr_backward
@@ -91,14 +95,37 @@ CHAIN_CASES = [("lander3d", "float64", 1, 0.0), ("lander3d", "float32", 1, 0.3),
                ("hover3d", "float32", 1, 0.0), ("lander2d", "float64", 10, 0.0), ("hover1d", "float64", 1, 0.0)]
 
 
+# the same comparison under the non-default vehicle models of tests/model_variants.py: the gyro instantiations of the
+# backward kernel, its per-env coefficient load and the lift law's derivative
+VARIANT_CHAIN_CASES = [("lander3d", "float64", 1, 0.0, "mars_gyro"), ("lander3d", "float32", 10, 0.3, "mars_gyro"),
+                       ("hover3d", "float64", 1, 0.0, "gyro_only"), ("lander3d", "float32", 1, 0.3, "vehicles"),
+                       ("hover3d", "float64", 1, 0.0, "vehicles_mars_gyro"), ("lander2d", "float64", 10, 0.0, "vehicles")]
+
+
 @pytest.mark.parametrize("task,mode,substeps,mu", CHAIN_CASES)
 def test_gains_equal_the_recursion_on_chained_step_jacobians(task, mode, substeps, mu):
     """K = 16, 300 envs (four whole wavefronts and a partial one), a stored start with the reset's perturbation pending,
     LANDED and CRASHED lanes and lanes with clipped motors; diagonal R so that a clipped motor's gain row is exact."""
+    _gains_against_the_chain(task, mode, substeps, mu, None)
+
+
+@pytest.mark.parametrize("task,mode,substeps,mu,variant", VARIANT_CHAIN_CASES)
+def test_gains_equal_the_recursion_under_model_variants(task, mode, substeps, mu, variant):
+    """The case above under a non-default vehicle model, the motors centred on that model's hover value; the bars are
+    the same (both sides run the same model), and the x tape differs from the default model's in every airborne lane."""
+    _gains_against_the_chain(task, mode, substeps, mu, variant)
+
+
+def _gains_against_the_chain(task, mode, substeps, mu, variant):
     n, K, A = 300, 16, TASK_A[task]
-    rng = np.random.default_rng(500 + TASKS.index(task) * 10 + substeps + (mode == "float32"))
-    env = _env(task, n, mode, seed=4, substeps=substeps)
+    if variant is None:
+        rng = np.random.default_rng(500 + TASKS.index(task) * 10 + substeps + (mode == "float32"))
+    else:
+        rng = np.random.default_rng(zlib.crc32(repr((task, mode, substeps, variant)).encode()))
+    ah = model_variants.hover(variant)
+    env = _env(task, n, mode, seed=4, substeps=substeps, **model_variants.env_kwargs(variant))
     try:
+        model_variants.install(variant, env, rng)
         env.reset()
         x, st = _random_point(n, rng)
         g = n // 8
@@ -106,13 +133,16 @@ def test_gains_equal_the_recursion_on_chained_step_jacobians(task, mode, substep
         st[g:2 * g] = CRASHED
         s0 = env.get_state()
         env.set_state(x=x, status=st, steps=np.ones(n, np.int32), prev_shaping=np.zeros(n), flags=s0["flags"])
-        a = AH * rng.uniform(0.5, 1.5, (K, n, A))
+        a = ah * rng.uniform(0.5, 1.5, (K, n, A))
         a[:, 2 * g:3 * g] = rng.uniform(-0.3, 1.3, (K, g, A))                 # clipped
         a = a.astype(np.float32)
         acts = _dev(a, env)
         Q, Qf, R, q, r = _cost_model(rng, A, K, n)
         ro = env.rollout_states(acts)
         tape_x, tape_s = to_np(ro.x).copy(), to_np(ro.status).copy()
+        if variant is not None:
+            model_variants.assert_differs_from_default(variant, tape_x, task, mode, substeps,
+                                                       model_variants.stored_start(env), acts)
         got = env.rollout_lqr(acts, ro, Q, R, q=_dev(q, env), r=_dev(r, env), Q_final=Qf, mu=mu)
         Ab, Bb = np.zeros((K, n, 12, 12)), np.zeros((K, n, 12, A))
         for k in range(K):
@@ -120,7 +150,8 @@ def test_gains_equal_the_recursion_on_chained_step_jacobians(task, mode, substep
                 env.step_jacobian(acts[k], state={"x": tape_x[k - 1].T.copy(), "status": tape_s[k - 1]})
             Ab[k], Bb[k] = to_np(jac.dx).astype(np.float64), to_np(jac.du).astype(np.float64)
         assert (tape_s == LANDED).any() and (tape_s == CRASHED).any()
-        _compare("%s %s substeps=%d mu=%g" % (task, mode, substeps, mu), got, (Ab, Bb), Q, R, q, r, Qf, mu)
+        _compare("%s %s substeps=%d mu=%g%s" % (task, mode, substeps, mu, " " + variant if variant else ""), got,
+                 (Ab, Bb), Q, R, q, r, Qf, mu)
         assert to_np(got.ok).all()
         # clipped motors: B's column is zero, so the gain row is exactly 0 and d is -(R + mu I)^-1 r alone
         Kg, d = to_np(got.K), to_np(got.d)
@@ -213,16 +244,34 @@ def test_cholesky_reports_matrices_that_are_not_positive_definite():
 @pytest.mark.parametrize("mode", ["float32", "float32_rn", "float64"])
 @pytest.mark.parametrize("task", TASKS)
 def test_feedback_rollout_is_exact(task, mode, substeps):
+    _feedback_is_exact(task, mode, substeps, None)
+
+
+@pytest.mark.parametrize("variant,task,mode", [("mars_gyro", "lander3d", "float32"), ("mars_gyro", "hover3d", "float64"),
+                                               ("vehicles", "lander3d", "float64"), ("vehicles", "hover3d", "float32_rn"),
+                                               ("act_f32", "lander3d", "float32"), ("act_f32", "hover3d", "float64")])
+def test_feedback_rollout_is_exact_under_model_variants(variant, task, mode):
+    """The feedback loop's runtime rotor-gyro branch, its float32 motor law, the lift law and its per-env coefficient
+    load: the same exact statements, and the x tape differs from the default model's in every lane."""
+    _feedback_is_exact(task, mode, 1, variant)
+
+
+def _feedback_is_exact(task, mode, substeps, variant):
     import torch
     from gym_copter_amd import LqrGains
     n, K, A = 200, 8, TASK_A[task]
-    rng = np.random.default_rng(900 + TASKS.index(task) * 7 + substeps)
-    env = _env(task, n, mode, seed=2, substeps=substeps)
+    if variant is None:
+        rng = np.random.default_rng(900 + TASKS.index(task) * 7 + substeps)
+    else:
+        rng = np.random.default_rng(zlib.crc32(repr((task, mode, variant)).encode()))
+    ah = model_variants.hover(variant)
+    env = _env(task, n, mode, seed=2, substeps=substeps, **model_variants.env_kwargs(variant))
     try:
+        model_variants.install(variant, env, rng)
         env.reset()
         x0, st = _random_point(n, rng)
         state = {"x": x0, "status": st}
-        abar = _dev((AH * rng.uniform(0.9, 1.1, (K, n, A))).astype(np.float32), env)
+        abar = _dev((ah * rng.uniform(0.9, 1.1, (K, n, A))).astype(np.float32), env)
         Kg = _dev(0.002 * rng.standard_normal((K, n, A, 12)), env)
         d = _dev(0.01 * rng.standard_normal((K, n, A)), env)
         gains = LqrGains(Kg, d, None, None, None, None)
@@ -244,6 +293,8 @@ def test_feedback_rollout_is_exact(task, mode, substeps):
         ro = env.rollout_states(fa, state)
         for u, v in zip(fro, ro):
             assert torch.equal(u, v)
+        if variant is not None:
+            model_variants.assert_differs_from_default(variant, fro.x, task, mode, substeps, state, fa.clone())
     finally:
         env.close()
 

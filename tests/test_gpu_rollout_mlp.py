@@ -3,10 +3,14 @@ cs_rollout_mlp_vjp, CopterVecEnv.rollout_mlp_states / rollout_mlp_vjp, gym_copte
 primal bit-identical to a twin env stepped with the forward's own action tape, the tapes against the float32 observation
 and a float64 NumPy MLP, theta = 0 against the open-loop calls, the gradient against chained step_jacobian + a float64
 policy Jacobian and against central differences of the float64 closed-loop oracle (tests/mlp_rollout_fd.py), no side
-effects, autograd, policy training on Hover3D, the sharded passthrough, float32 outputs, errors and 64-bit offsets."""
+effects, autograd, policy training on Hover3D, the sharded passthrough, float32 outputs, errors and 64-bit offsets.  The
+primal and both gradient checks also run under the non-default vehicle models of tests/model_variants.py."""
+import zlib
+
 import numpy as np
 import pytest
 
+import model_variants
 from gpu_util import have_gpu, to_np
 from jacobian_fd import hover_action
 from mlp_rollout_fd import OBS_SHAPE, fd_mlp_rollout_vjp
@@ -26,12 +30,13 @@ def _env(task, n, mode="float64", autoreset="disabled", **kw):
     return gym_copter_amd.CopterVecEnv(task=task, num_envs=n, state_dtype=mode, autoreset_mode=autoreset, **kw)
 
 
-def _theta(task, hidden, seed, scale=0.1, env=None):
-    """A policy near hover: the output bias is the hover motor value, the output weights small."""
+def _theta(task, hidden, seed, scale=0.1, env=None, bias=None):
+    """A policy near hover: the output bias is the hover motor value (`bias`: that of a model variant), the output
+    weights small."""
     import torch
     from gym_copter_amd import mlp
     p = mlp.init(OBS_SHAPE[task][1], TASK_A[task], hidden, generator=torch.Generator().manual_seed(seed),
-                 out_bias=hover_action(), out_scale=scale)
+                 out_bias=hover_action() if bias is None else bias, out_scale=scale)
     return p if env is None else p.to(env.device)
 
 
@@ -105,20 +110,38 @@ def test_primal_is_bit_identical_to_a_twin(task, mode):
         twin.close()
 
 
-@pytest.mark.parametrize("case", ["substeps10_h32", "explicit_h64", "explicit_force_h1", "substeps10_f32_h0"])
+# the model variants of tests/model_variants.py: (variant, task, storage, hidden), each from a stored and an explicit start
+VARIANT_PRIMAL = {"mars_gyro": ("mars_gyro", "lander3d", "float64", 32),
+                  "gyro_only": ("gyro_only", "lander3d", "float32", 0),
+                  "vehicles": ("vehicles", "lander3d", "float32", 64),
+                  "vehicles_mars_gyro": ("vehicles_mars_gyro", "lander3d", "float64", 1),
+                  "act_f32": ("act_f32", "lander3d", "float32", 32),
+                  "hover2d_vehicles": ("vehicles", "hover2d", "float64", 32)}
+
+
+@pytest.mark.parametrize("case", ["substeps10_h32", "explicit_h64", "explicit_force_h1", "substeps10_f32_h0"]
+                         + ["%s_%s" % (k, start) for k in VARIANT_PRIMAL for start in ("stored", "explicit")])
 def test_primal_bit_identity_configurations(case):
+    """Substeps, storage modes and start forms on Lander3D; and the non-default vehicle models, where the twin is built
+    and given its per-env table identically and the x tape differs from the default model's on the same action tape."""
     n, K = 1024, 30
-    substeps = 10 if case.startswith("substeps10") else 1
-    mode = "float32" if "f32" in case or case.startswith("explicit_force") else "float64"
-    hidden = int(case.rsplit("_h", 1)[1])
-    env, twin = _env("lander3d", n, mode, seed=2, substeps=substeps), _env("lander3d", n, mode, seed=2,
-                                                                           substeps=substeps)
+    variant, task = None, "lander3d"
+    if case.rsplit("_", 1)[0] in VARIANT_PRIMAL:
+        variant, task, mode, hidden = VARIANT_PRIMAL[case.rsplit("_", 1)[0]]
+        substeps = 1
+    else:
+        substeps = 10 if case.startswith("substeps10") else 1
+        mode = "float32" if "f32" in case or case.startswith("explicit_force") else "float64"
+        hidden = int(case.rsplit("_h", 1)[1])
+    kw = model_variants.env_kwargs(variant)
+    env, twin = _env(task, n, mode, seed=2, substeps=substeps, **kw), _env(task, n, mode, seed=2, substeps=substeps, **kw)
     try:
+        rng = np.random.default_rng(9 if variant is None else zlib.crc32(case.encode()))
+        model_variants.install_same(twin, model_variants.install(variant, env, rng))
         env.reset()
         twin.reset()
-        rng = np.random.default_rng(9)
         state = None
-        if case.startswith("explicit"):
+        if case.startswith("explicit") or case.endswith("_explicit"):
             x, st = _point(n, rng)
             if mode != "float64":
                 x = x.astype(np.float32).astype(np.float64)
@@ -131,12 +154,17 @@ def test_primal_bit_identity_configurations(case):
             state["prev_shaping"] = np.full(n, np.nan)
             if f is not None:
                 state["force"] = f
-        p = _theta("lander3d", hidden, 2, env=env)
+        # gyro_only: the rotor-gyro term needs unequal motors; the default scale saturates all four alike in some lanes
+        p = _theta(task, hidden, 2, env=env, bias=model_variants.hover(variant),
+                   scale=0.0015 if variant == "gyro_only" else 0.1)
+        start = model_variants.stored_start(env) if state is None else {"x": state["x"], "status": state["status"]}
         r = env.rollout_mlp_states(p, K, hidden, state=state)
         r = type(r)(*(t.clone() for t in r))
         if state is not None:
-            assert np.array_equal(to_np(r.obs[0]), _obs_of("lander3d", state["x"].T))
+            assert np.array_equal(to_np(r.obs[0]), _obs_of(task, state["x"].T))
         _compare_with_twin(twin, r)
+        if variant is not None:
+            model_variants.assert_differs_from_default(variant, r.x, task, mode, substeps, start, r.actions)
     finally:
         env.close()
         twin.close()
@@ -265,18 +293,37 @@ def _policy_jac(theta, hidden, obs, A):
     return np.einsum("ch,nh,hj->ncj", p["W2"], 1 - h * h, p["W1"])
 
 
-@pytest.mark.parametrize("task,hidden", [("lander3d", 0), ("lander3d", 32), ("hover3d", 16)])
-def test_gradient_equals_chained_step_jacobians_and_policy_jacobian(task, hidden):
+# Under per-env inertias (Ix != Iy) the motors stay near hover.  The default case's policy (output scale 0.3) and its
+# offsets of +-0.8 saturate 9 motor values in 10, which spins a vehicle up to hundreds of rad/s inside the horizon; the
+# Euler step of the gyroscopic coupling (I_a - I_b) / I_c w_a w_b then grows without bound -- the float64 oracle reaches
+# 1e300 rad/s and overflows in a third of the lanes, and the device tape with it -- while the default vehicle, Ix = Iy,
+# has no yaw coupling and stays below 1e3.  So these variants take feedback of ~30 % of hover and offsets of +-2 x hover
+# (a quarter of that block's motor values clip at 0): the rates stay below 3 rad/s in the oracle.
+SPREAD_INERTIA = ("vehicles", "vehicles_mars_gyro")
+
+# (task, hidden, model variant): the default model at 2 048 envs; the variants of tests/model_variants.py at 600 (nine
+# whole wavefronts and a partial one) -- both gyro backward kernels, the per-env coefficient load, the lift law
+CHAIN_GRADIENT_CASES = [pytest.param("lander3d", 0, None, id="lander3d-0"), pytest.param("lander3d", 32, None, id="lander3d-32"),
+                        pytest.param("hover3d", 16, None, id="hover3d-16"),
+                        ("lander3d", 32, "mars_gyro"), ("hover3d", 0, "mars_gyro"), ("lander3d", 0, "gyro_only"),
+                        ("hover3d", 32, "gyro_only"), ("lander3d", 0, "vehicles"), ("hover3d", 32, "vehicles"),
+                        ("lander3d", 32, "vehicles_mars_gyro"), ("hover3d", 0, "vehicles_mars_gyro")]
+
+
+@pytest.mark.parametrize("task,hidden,variant", CHAIN_GRADIENT_CASES)
+def test_gradient_equals_chained_step_jacobians_and_policy_jacobian(task, hidden, variant):
     """2 048 envs, K = 24, float32 storage, an explicit start (g_x0), LANDED envs, offsets that clip some actions: g_u,
     g_x0 and g_theta equal the reverse product of step_jacobian at the tape plus J_o pi at the obs tape (and
-    -grad shaping(x_{k-1}) where a Lander step's reward has a gradient), within 1e-9 scaled."""
+    -grad shaping(x_{k-1}) where a Lander step's reward has a gradient), within 1e-9 scaled.  Under a model variant the
+    policy hovers at that model's motor value, and the x tape differs from the default model's on the same action tape."""
     import torch
     from gym_copter_amd import mlp
-    n, K, A = 2048, 24, 4
+    n, K, A = 2048 if variant is None else 600, 24, 4
     first, od = OBS_SHAPE[task]
-    rng = np.random.default_rng(31 + hidden)
-    env = _env(task, n, "float32", seed=4)
+    rng = np.random.default_rng(31 + hidden if variant is None else zlib.crc32(repr((task, hidden, variant)).encode()))
+    env = _env(task, n, "float32", seed=4, **model_variants.env_kwargs(variant))
     try:
+        model_variants.install(variant, env, rng)
         env.reset()
         x, st = _point(n, rng)
         x = x.astype(np.float32).astype(np.float64)
@@ -284,8 +331,13 @@ def test_gradient_equals_chained_step_jacobians_and_policy_jacobian(task, hidden
         x[4, :q], x[5, :q], st[:q] = 0.0, 0.0, LANDED
         u = np.zeros((K, n, A), np.float32)
         u[:, q:2 * q] = rng.uniform(-0.8, 0.8, (K, q, A))                     # some clipped
+        scale = 0.3
+        if variant in SPREAD_INERTIA:
+            ah = model_variants.hover(variant)
+            u[:, q:2 * q] = ah * rng.uniform(-2.0, 2.0, (K, q, A))            # some clipped, at 0 only
+            scale = (0.003 if hidden else 0.0015) * ah / hover_action()
         state = {"x": x, "status": st}
-        p = _theta(task, hidden, 5, scale=0.3, env=env)
+        p = _theta(task, hidden, 5, scale=scale, env=env, bias=model_variants.hover(variant))
         gx, gr = rng.standard_normal((K, n, 12)), rng.standard_normal((K, n))
         r = env.rollout_mlp_states(p, K, hidden, offsets=_dev(u, env), state=state)
         r = type(r)(*(t.clone() for t in r))
@@ -294,6 +346,8 @@ def test_gradient_equals_chained_step_jacobians_and_policy_jacobian(task, hidden
         tape_x, tape_s, obs = to_np(r.x).copy(), to_np(r.status).copy(), to_np(r.obs).copy()
         acts = r.actions
         assert (tape_s == LANDED).any() and (to_np(acts) < 0).any()
+        if variant is not None:
+            model_variants.assert_differs_from_default(variant, tape_x, task, "float32", 1, state, acts)
         lam = np.zeros((n, 12))
         want = np.zeros((K, n, A))
         max_angle = np.radians(45)
@@ -314,9 +368,12 @@ def test_gradient_equals_chained_step_jacobians_and_policy_jacobian(task, hidden
                 new -= (gr[k] * ~tilt)[:, None] * shaping_grad(xprev.T).T
             new[:, first:first + od] += np.einsum("ncj,nc->nj", _policy_jac(p.cpu(), hidden, obs[k], A), want[k])
             lam = new
+        wp = mlp.param_grad(p.cpu(), hidden, torch.from_numpy(obs), torch.from_numpy(want)).numpy()
+        print("chained Jacobians %s H=%d%s: g_u %.2e g_x0 %.2e g_theta %.2e"
+              % (task, hidden, " " + variant if variant else "", _scaled(ga, want), _scaled(g0, lam.T),
+                 float(np.max(np.abs(gp - wp) / np.maximum(1.0, np.abs(wp))))))
         assert _scaled(ga, want) <= 1e-9, _scaled(ga, want)
         assert _scaled(g0, lam.T) <= 1e-9, _scaled(g0, lam.T)
-        wp = mlp.param_grad(p.cpu(), hidden, torch.from_numpy(obs), torch.from_numpy(want)).numpy()
         assert np.max(np.abs(gp - wp) / np.maximum(1.0, np.abs(wp))) <= 1e-9
     finally:
         env.close()
@@ -325,28 +382,36 @@ def test_gradient_equals_chained_step_jacobians_and_policy_jacobian(task, hidden
 # ---------------------------------------------------------------------------------------------------------------------
 # 5. the gradient against central differences of the float64 closed-loop oracle
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("task,hidden,substeps", [("lander3d", 8, 1), ("hover3d", 0, 1), ("lander2d", 4, 10),
-                                                  ("hover1d", 3, 1)])
-def test_gradient_matches_central_differences(task, hidden, substeps):
+@pytest.mark.parametrize("task,hidden,substeps,variant", [
+    pytest.param("lander3d", 8, 1, None, id="lander3d-8-1"), pytest.param("hover3d", 0, 1, None, id="hover3d-0-1"),
+    pytest.param("lander2d", 4, 10, None, id="lander2d-4-10"), pytest.param("hover1d", 3, 1, None, id="hover1d-3-1"),
+    ("lander3d", 8, 1, "mars_gyro"), ("hover3d", 0, 1, "vehicles")])
+def test_gradient_matches_central_differences(task, hidden, substeps, variant):
     """float64 storage, K = 8, explicit starts away from every branch, a policy whose feedback moves the motors by ~10 %
     of hover: g_theta, g_u and g_x0 within 1e-5 scaled (the device's float32 observation and action roundings move the
-    trajectory by ~1e-7 relative; the bar covers that)."""
+    trajectory by ~1e-7 relative; the bar covers that).  Under a model variant the oracle runs the same model, and the
+    chained Jacobians are not the only witness of the gyro and per-env backward."""
     n, K, A = 48, 8, TASK_A[task]
     rng = np.random.default_rng(7)
-    env = _env(task, n, "float64", substeps=substeps)
+    ah = model_variants.hover(variant)
+    env = _env(task, n, "float64", substeps=substeps, **model_variants.env_kwargs(variant))
     try:
+        model = model_variants.oracle_model(variant, model_variants.install(variant, env, rng))
         x, st = _point(n, rng)
-        u = (hover_action() * rng.uniform(-0.2, 0.2, (K, n, A))).astype(np.float32)
-        p = _theta(task, hidden, 9, scale=0.001 if hidden else 0.0005, env=env)   # feedback of ~10 % of hover
+        u = (ah * rng.uniform(-0.2, 0.2, (K, n, A))).astype(np.float32)
+        # feedback of ~10 % of hover (the weights scale with the hover value)
+        p = _theta(task, hidden, 9, scale=(0.001 if hidden else 0.0005) * ah / hover_action(), env=env, bias=ah)
         gx, gr = rng.standard_normal((K, n, 12)), rng.standard_normal((K, n))
         state = {"x": x, "status": st}
         r = env.rollout_mlp_states(p, K, hidden, offsets=_dev(u, env), state=state)
         gp, ga, g0 = env.rollout_mlp_vjp(p, r, gx=_dev(gx, env), gr=_dev(gr, env), state=state, hidden=hidden)
         wp, wu, w0 = fd_mlp_rollout_vjp(task, x, st, p.cpu().double().numpy(), hidden, K, offsets=u.astype(np.float64),
-                                        gx=gx, gr=gr, substeps=substeps)
+                                        gx=gx, gr=gr, substeps=substeps, **model)
         errs = (_scaled(to_np(gp), wp), _scaled(to_np(ga), wu), _scaled(to_np(g0), w0))
-        print("central differences %s H=%d substeps=%d: g_theta %.2e g_u %.2e g_x0 %.2e" % ((task, hidden, substeps)
-                                                                                              + errs))
+        print("central differences %s H=%d substeps=%d%s: g_theta %.2e g_u %.2e g_x0 %.2e"
+              % ((task, hidden, substeps, " " + variant if variant else "") + errs))
+        if variant is not None:
+            model_variants.assert_differs_from_default(variant, r.x, task, "float64", substeps, state, r.actions)
         assert max(errs) <= 1e-5, errs
     finally:
         env.close()

@@ -1,9 +1,13 @@
 """cs_rollout_mppi_costs / cs_rollout_mppi_update on the GPU: the costs against the existing
 rollout_states fed the sample actions tests/mppi_ref.py rebuilds; the update against mppi_ref on the kernel's own costs;
-determinism, shard invariance, no side effects; the mppi driver; plumbing."""
+determinism, shard invariance, no side effects; the mppi driver; plumbing.  The costs also under the non-default vehicle
+models of tests/model_variants.py."""
+import zlib
+
 import numpy as np
 import pytest
 
+import model_variants
 import mppi_ref
 from gpu_util import have_gpu, to_np
 from jacobian_fd import hover_action
@@ -124,6 +128,59 @@ def test_costs_equal_the_cost_of_rollout_states_on_the_sample_actions(task, mode
         env.close()
 
 
+VARIANT_COST_CASES = [("mars_gyro", "lander3d", "float32", 1), ("mars_gyro", "hover3d", "float64", 1),
+                      ("vehicles", "lander2d", "float32_rn", 10), ("vehicles_mars_gyro", "lander3d", "float64", 1),
+                      ("act_f32", "lander3d", "float32", 1)]
+
+
+VARIANT_N, VARIANT_K, VARIANT_P, VARIANT_SEED, VARIANT_BASE, VARIANT_STREAM = 300, 16, 7, 21, 1000, (1 << 32) - 1
+
+
+def _variant_problem(variant, task, mode, substeps):
+    """the generator of a case under a model variant and what it draws first: the per-env table, the nominal tape
+    centred on the variant's hover value, sigma and the 5-20 m explicit start.  tests/test_rollout_mppi_cpu.py replays
+    samples 0, 3 and P - 1 of every case through VecOracle with the variant's model: no env terminates inside the
+    horizon (the per-env vehicles hover within 0.6-1.5 x the value the tape is centred on, and 0.16 s at up to twice
+    hover thrust leave the starts far from the ground, the bounds and the tilt limit)."""
+    n, K, A = VARIANT_N, VARIANT_K, TASK_A[task]
+    rng = np.random.default_rng(zlib.crc32(repr((variant, task, mode, substeps)).encode()))
+    ah = model_variants.hover(variant)
+    installed = model_variants.draw(variant, rng, n)
+    abar = (ah * rng.uniform(0.7, 1.3, (K, n, A))).astype(np.float32)
+    sigma = (0.05 * ah * rng.uniform(0.5, 2.0, A)).astype(np.float32)
+    x0, st = _random_point(n, rng)
+    return rng, installed, abar, sigma, {"x": x0, "status": st, "force": rng.uniform(-1, 1, (3, n))}
+
+
+@pytest.mark.parametrize("variant,task,mode,substeps", VARIANT_COST_CASES)
+def test_costs_under_model_variants(variant, task, mode, substeps):
+    """The comparison above under the non-default vehicle models of tests/model_variants.py (the rotor-gyro branch of the
+    sample loop, its float32 motor law, the lift law, the per-env coefficient load): N = 300, K = 16, P = 7, both start
+    forms, samples 0, 3 and P - 1, the same bar; no sample of the explicit start may terminate, and the nominal's x tape
+    differs from the default model's in every lane."""
+    n, K, P, A = VARIANT_N, VARIANT_K, VARIANT_P, TASK_A[task]
+    seed, base = VARIANT_SEED, VARIANT_BASE
+    rng, installed, a0, sigma, state = _variant_problem(variant, task, mode, substeps)
+    env = _env(task, n, mode, substeps=substeps, seed=seed, env_id_base=base, **model_variants.env_kwargs(variant))
+    try:
+        model_variants.install_same(env, installed)
+        env.reset()
+        ids = base + np.arange(n)
+        abar = _dev(a0, env)
+        Q, Qf, R, x_ref, a_ref = _cost_model(rng, A, n)
+        wr = 0.5 if "lander" in task else 0.0
+        name = "%s %s/%s/%d" % (variant, task, mode, substeps)
+        _check_costs(name + " stored", env, abar, sigma, P, x_ref, Q, R, Qf, a_ref, wr, 3, None, (0, 3, P - 1), ids,
+                     seed, expect_quiet=False)
+        _, _, _, x_ref_k, _ = _cost_model(rng, A, n, K)
+        _check_costs(name + " explicit", env, abar, sigma, P, x_ref_k, Q, R, None, None, wr, VARIANT_STREAM, state,
+                     (0, 3, P - 1), ids, seed)
+        model_variants.assert_differs_from_default(variant, env.rollout_states(abar, state).x, task, mode, substeps,
+                                                   state, abar)
+    finally:
+        env.close()
+
+
 def test_costs_with_next_step_resets_pending():
     """A next_step env (float32 storage) with resets pending at the start: those envs reset in step 1 and the new
     episode's perturbation enters step 2, in every sample as in rollout_states."""
@@ -173,6 +230,34 @@ def test_costs_through_touchdowns_and_crashes():
             assert len(np.unique(to_np(env.rollout_mppi_costs(abar, sigma, P, x_ref, Q, R, state=state).best))) > 3
         finally:
             env.close()
+
+
+def test_costs_through_touchdowns_and_crashes_under_per_env_mars_vehicles():
+    """The low, descending starts above under vehicles_mars_gyro (Lander3D, float32 storage): crashes and landings under
+    per-env coefficients, the lift law and the rotor-gyro term."""
+    variant, task, mode = "vehicles_mars_gyro", "lander3d", "float32"
+    n, K, P, A, seed = 512, 16, 12, 4, 5
+    rng = np.random.default_rng(88)
+    ah = model_variants.hover(variant)
+    env = _env(task, n, mode, seed=seed, **model_variants.env_kwargs(variant))
+    try:
+        model_variants.install(variant, env, rng)
+        env.reset()
+        x0, st = _random_point(n, rng, low=True)
+        state = {"x": x0, "status": st}
+        abar = _dev((ah * rng.uniform(0.2, 1.2, (K, n, A))).astype(np.float32), env)
+        sigma = np.full(A, 0.5 * ah, np.float32)
+        Q, Qf, R, x_ref, a_ref = _cost_model(rng, A, n)
+        costs, events = _check_costs("%s %s low starts" % (variant, task), env, abar, sigma, P, x_ref, Q, R, Qf, a_ref,
+                                     1.0, 9, state, range(P), np.arange(n), seed, expect_quiet=False)
+        ro = env.rollout_states(abar, state)
+        final = to_np(ro.status)[-1]
+        print("  nominal plan: %d crashed, %d landed, %d airborne of %d" % ((final == CRASHED).sum(),
+              (final == LANDED).sum(), (final == AIRBORNE).sum(), n))
+        assert events > 0 and (final == CRASHED).sum() > 10 and (final != CRASHED).sum() > 10
+        model_variants.assert_differs_from_default(variant, ro.x, task, mode, 1, state, abar)
+    finally:
+        env.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -147,6 +147,30 @@ def test_checker_with_zero_policy_is_the_open_loop_checker(task):
     assert np.all(np.isfinite(gp)) and np.abs(gp).max() > 0   # theta = 0 is no stationary point of the loss
 
 
+@pytest.mark.parametrize("variant", ["mars_gyro", "vehicles", "vehicles_mars_gyro"])
+def test_checker_passes_the_vehicle_model_through(variant):
+    """vp / g / mars (per-env arrays included) reach the oracle tiled over the perturbed copies as tests/rollout_fd.py
+    tiles them: with theta = 0 the closed-loop checker equals the open-loop one under the same model, and both differ
+    from the default model's."""
+    import model_variants
+    task, n, K, A = "lander3d", 3, 4, 4
+    rng = np.random.default_rng(5)
+    model = model_variants.oracle_model(variant, model_variants.draw(variant, rng, n))
+    x, st = _point(n, rng)
+    u = model_variants.hover(variant) * rng.uniform(0.8, 1.2, (K, n, A))
+    gx, gr = rng.normal(size=(K, n, 12)), rng.normal(size=(K, n))
+    P = mlp.num_params(OBS_SHAPE[task][1], A, 3)
+    gp, gu, g0 = fd_mlp_rollout_vjp(task, x, st, np.zeros(P), 3, K, offsets=u, gx=gx, gr=gr, **model)
+    ga, gx0 = fd_rollout_vjp(task, x, st, u, gx=gx, gr=gr, **model)
+    assert np.allclose(gu, ga, rtol=1e-9, atol=1e-9)
+    assert np.allclose(g0, gx0, rtol=1e-9, atol=1e-9)
+    _, plain, _ = fd_mlp_rollout_vjp(task, x, st, np.zeros(P), 3, K, offsets=u, gx=gx, gr=gr)
+    assert np.all(np.abs(gu - plain).max(axis=(0, 2)) > 1e-3 * np.abs(plain).max(axis=(0, 2)))     # in every env
+    xs, _, _, _ = oracle_mlp_rollout(task, x, st, np.zeros(P), 3, K, offsets=u, **model)
+    xd, _, _, _ = oracle_mlp_rollout(task, x, st, np.zeros(P), 3, K, offsets=u)
+    assert np.all(np.any(xs != xd, axis=(0, 2)))
+
+
 @pytest.mark.parametrize("hidden", [0, 4])
 def test_checker_theta_gradient_is_the_host_reduction_of_its_action_gradient(hidden):
     """Along one closed-loop trajectory, dL / d theta = sum_{k,n} J_theta pi(o_{k-1,n})^T dL / d a_k (the chain rule

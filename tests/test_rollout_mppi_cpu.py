@@ -1,7 +1,8 @@
 """CPU-side checks of cs_rollout_mppi_costs / cs_rollout_mppi_update: both entry points declared, exported and bound,
 the ctypes struct mirroring the header; bad argument blocks refused without touching a device; the noise draw of
 tests/mppi_ref.py against the kernels' own header compiled for the host (tests/host/mppi_noise_host), bit for bit, and
-its moments; mppi_ref's update against a brute-force evaluation in longdouble."""
+its moments; mppi_ref's update against a brute-force evaluation in longdouble; the explicit starts of the GPU cases under
+non-default vehicle models (tests/model_variants.py) replayed through the oracle: no env may terminate."""
 import ctypes as C
 import os
 import re
@@ -300,3 +301,28 @@ def test_cost_restatement():
     Sl = mppi_ref.cost(x, rew, a, xr, Q, R, Q_final=Qf, a_ref=ar, reward_weight=0.7, dtype=np.longdouble)
     assert Sl.dtype == np.longdouble and np.max(np.abs(Sl - S)) < 1e-11
     assert np.array_equal(mppi_ref.cost(x, rew, a, xr[0], Q, R), mppi_ref.cost(x, rew, a, np.broadcast_to(xr[0], x.shape), Q, R))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the GPU cases under non-default vehicle models keep every sample of their explicit start airborne
+# ---------------------------------------------------------------------------------------------------------------------
+def test_variant_cost_cases_terminate_nowhere_in_the_oracle():
+    """tests/test_gpu_rollout_mppi.py::test_costs_under_model_variants asserts that no sample of its explicit start
+    terminates (expect_quiet).  The same problem through VecOracle with the variant's vehicle, world and thrust law, in
+    the case's storage mode: samples 0, 3 and P - 1 stay airborne, inside the bounds and below the tilt limit.  (The
+    oracle has no float32 motor law: act_f32 is replayed on the float64 one, 1e-7 relative away.)"""
+    import model_variants
+    import test_gpu_rollout_mppi as gpu
+    from oracle.refcpu import AIRBORNE
+    from rollout_fd import oracle_rollout
+    ids = gpu.VARIANT_BASE + np.arange(gpu.VARIANT_N)
+    for variant, task, mode, substeps in gpu.VARIANT_COST_CASES:
+        _, installed, abar, sigma, state = gpu._variant_problem(variant, task, mode, substeps)
+        model = model_variants.oracle_model(None if variant == "act_f32" else variant, installed)
+        for p in (0, 3, gpu.VARIANT_P - 1):
+            a = mppi_ref.sample_actions(abar, sigma, gpu.VARIANT_SEED, ids, gpu.VARIANT_STREAM, p)
+            xs, _, term, trunc, orc = oracle_rollout(task, state["x"], state["status"], a, force=state["force"],
+                                                     substeps=substeps, store_mode=mode, **model)
+            assert not term.any() and not trunc.any(), (variant, task, p)
+            assert np.all(orc.status == AIRBORNE) and xs[..., 4].max() < -4.0, (variant, task, p)
+            assert np.abs(xs[..., [6, 8]]).max() < 0.7 and np.abs(xs[..., [0, 2]]).max() < 6.0, (variant, task, p)
