@@ -137,6 +137,15 @@ class RolloutMppiIO(C.Structure):
                 ("ess_dev", C.c_void_p), ("cost_min_dev", C.c_void_p)]
 
 
+class RolloutMppiExt(C.Structure):
+    """Mirror of `struct cs_rollout_mppi_ext` (cs_rollout_mppi_costs_ex / cs_rollout_mppi_update_ex /
+    cs_rollout_mppi_temperature)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved_", C.c_uint32), ("knot_dev", C.c_void_p),
+                ("knot_weights_dev", C.c_void_p), ("lam_dev", C.c_void_p), ("ess_target", C.c_double),
+                ("lam_min", C.c_double), ("lam_max", C.c_double), ("lam_out_dev", C.c_void_p),
+                ("ess_out_dev", C.c_void_p)]
+
+
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
@@ -209,6 +218,11 @@ SYMBOLS = {
     "cs_rollout_feedback_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
+    "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),
+                                           C.POINTER(RolloutMppiExt), _P]),
+    "cs_rollout_mppi_update_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),
+                                            C.POINTER(RolloutMppiExt), _P]),
+    "cs_rollout_mppi_temperature": (C.c_int, [_P, C.POINTER(RolloutMppiIO), C.POINTER(RolloutMppiExt), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

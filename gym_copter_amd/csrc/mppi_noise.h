@@ -2,7 +2,8 @@
 // copterstep_rollout_mppi.hip): one Philox2x32-10 call per (env, nonce, step, sample, action component) and the
 // Irwin-Hall sum of its four 16-bit halves.  Plain C++ with no dependence on the device headers, so that a host program
 // compiles the very same code (tests/host/mppi_noise_host.cpp prints draws; tests/mppi_ref.py restates them in NumPy,
-// bit for bit: integer arithmetic and ONE float32 multiply).  DESIGN.md section 14.
+// bit for bit: integer arithmetic and ONE float32 multiply).  DESIGN.md section 14.  Below it, the smooth noise of
+// section 15: two knot draws blended per step (tests/host/mppi_smooth_host.cpp; tests/mppi_smooth_ref.py).
 #pragma once
 
 #include <stdint.h>
@@ -54,6 +55,27 @@ CS_MPPI_FN float mppi_noise(uint32_t key_noise, uint32_t env_id, uint32_t stream
   mppi_philox2x32_10(env_id, stream, key_noise + ((((k - 1u) << kMppiSampleBits) + p) * 4u + j), r0, r1);
   const int32_t t = (int32_t)((r0 >> 16) + (r0 & 0xFFFFu) + (r1 >> 16) + (r1 & 0xFFFFu)) - 131070;
   return (float)t * kMppiNoiseScale;
+}
+
+// Smooth noise (cs_rollout_mppi_costs_ex / cs_rollout_mppi_update_ex, copterstep_rollout_mppi_smooth.hip; DESIGN.md
+// section 15): step k reads the draws of two neighbouring knots, eps(p, knot, j) and eps(p, knot + 1, j) -- mppi_noise
+// with the knot number in its step slot -- and blends them with the caller's two float32 weights of that step:
+//     eps~ = fl32( fl32(w0 * e0) + fl32(w1 * e1) )
+// two multiplies and one add, never fused; the second term is left out altogether when w1 == 0, so that knot = k with
+// w = (1, 0) is mppi_noise(k) bit for bit (1 * e is exact).  The caller guarantees knot >= 1 and knot + 1 <= 16 384.
+CS_MPPI_FN float mppi_knot_blend(float w0, float e0, float w1, float e1) {
+#pragma clang fp contract(off)
+  const float a = w0 * e0;
+  if (w1 == 0.0f) return a;
+  const float b = w1 * e1;
+  return a + b;
+}
+
+CS_MPPI_FN float mppi_noise_smooth(uint32_t key_noise, uint32_t env_id, uint32_t stream, uint32_t knot, float w0,
+                                   float w1, uint32_t p, uint32_t j) {
+  const float e0 = mppi_noise(key_noise, env_id, stream, knot, p, j);
+  if (w1 == 0.0f) return mppi_knot_blend(w0, e0, 0.0f, 0.0f);
+  return mppi_knot_blend(w0, e0, w1, mppi_noise(key_noise, env_id, stream, knot + 1u, p, j));
 }
 
 }  // namespace cs

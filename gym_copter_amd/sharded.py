@@ -217,16 +217,21 @@ class ShardedCopterVecEnv:
                                       mu=mu, state=state, dtype=dtype)
 
     def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
-                           stream=0, state=None):
+                           stream=0, state=None, knots=None):
         """CopterVecEnv.rollout_mppi_costs of this rank's envs: shard-local (x_ref, state: the local envs').  The noise
         is keyed by the global env id, so a sharded batch draws what the unsharded one draws."""
         return self.local.rollout_mppi_costs(self._local_rollout_actions(actions), sigma, samples, x_ref, Q, R,
                                              Q_final=Q_final, a_ref=a_ref, reward_weight=reward_weight, stream=stream,
-                                             state=state)
+                                             state=state, knots=knots)
 
-    def rollout_mppi_update(self, actions, costs, sigma, lam, stream=0):
-        """CopterVecEnv.rollout_mppi_update of this rank's envs: shard-local (costs: the local envs')."""
-        return self.local.rollout_mppi_update(self._local_rollout_actions(actions), costs, sigma, lam, stream=stream)
+    def rollout_mppi_update(self, actions, costs, sigma, lam, stream=0, knots=None):
+        """CopterVecEnv.rollout_mppi_update of this rank's envs: shard-local (costs, a per-env lam: the local envs')."""
+        return self.local.rollout_mppi_update(self._local_rollout_actions(actions), costs, sigma, lam, stream=stream,
+                                              knots=knots)
+
+    def rollout_mppi_temperature(self, costs, ess_target, lam_min=1e-6, lam_max=1e6):
+        """CopterVecEnv.rollout_mppi_temperature of this rank's envs: shard-local (costs: the local envs')."""
+        return self.local.rollout_mppi_temperature(costs, ess_target, lam_min=lam_min, lam_max=lam_max)
 
     def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
         """CopterVecEnv.rollout_feedback_states of this rank's envs: shard-local (rollout, gains, alpha: the local

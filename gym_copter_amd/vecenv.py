@@ -100,6 +100,30 @@ LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
 # CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
 MppiCosts = collections.namedtuple("MppiCosts", "costs best")
 MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
+# CopterVecEnv.rollout_mppi_temperature's result
+MppiTemperature = collections.namedtuple("MppiTemperature", "lam ess")
+MPPI_MAX_KNOT = 16384                                        # knot + 1 <= 16 384: the noise keys stay distinct
+
+
+def mppi_knots(K, hold):
+    """The knot table of K steps for normalised linear interpolation over holds of `hold` steps, as rollout_mppi_costs /
+    rollout_mppi_update take it (knots=): (knot [K] uint32, w [K,2] float32) with, for step k = 1..K,
+
+        knot[k] = (k - 1) // hold + 1,   t = ((k - 1) % hold) / hold,   w[k] = (1 - t, t) / sqrt((1 - t)^2 + t^2)
+
+    computed in float64 and rounded once: the noise of step k is w[k][0] eps(knot[k]) + w[k][1] eps(knot[k] + 1), of unit
+    variance at every step, and steps inside a hold are correlated.  hold = 1 is the white table (k, 1, 0)."""
+    if not isinstance(K, (int, np.integer)) or isinstance(K, bool) or K < 1:
+        raise ValueError("K must be an int >= 1, got %r" % (K,))
+    if not isinstance(hold, (int, np.integer)) or isinstance(hold, bool) or hold < 1:
+        raise ValueError("hold must be an int >= 1, got %r" % (hold,))
+    k0 = np.arange(int(K), dtype=np.int64)
+    t = (k0 % int(hold)).astype(np.float64) / float(hold)
+    w = np.stack([1.0 - t, t], axis=1) / np.sqrt((1.0 - t) ** 2 + t ** 2)[:, None]
+    knot = k0 // int(hold) + 1
+    if int(knot[-1]) + 1 > MPPI_MAX_KNOT:
+        raise ValueError("K / hold is too large: knot + 1 must be <= %d" % MPPI_MAX_KNOT)
+    return knot.astype(np.uint32), w.astype(np.float32)
 
 
 def _torch():
@@ -1480,8 +1504,49 @@ class CopterVecEnv(_VectorEnvBase):
             raise ValueError("stream must be an int in [0, 2**32), got %r" % (stream,))
         return int(stream)
 
+    def _mppi_knots(self, knots, K):
+        """knots=(knot [K], w [K,2]) (mppi_knots' layout), checked on the host and kept on the device: the same table is
+        uploaded once.  Returns the two device tensors."""
+        torch = _torch()
+        try:
+            knot, w = knots
+            knot = np.asarray(knot.detach().cpu() if isinstance(knot, torch.Tensor) else knot)
+            w = np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("knots must be a pair (knot [K], w [K,2]) as mppi_knots returns it") from None
+        if knot.shape != (K,) or knot.dtype.kind not in "iu" or w.shape != (K, 2):
+            raise ValueError("knots must be (knot: %d integers, w: shape (%d, 2)), got shapes %s and %s"
+                             % (K, K, knot.shape, w.shape))
+        if int(knot.min()) < 1 or int(knot.max()) + 1 > MPPI_MAX_KNOT:
+            raise ValueError("knot numbers must lie in [1, %d]" % (MPPI_MAX_KNOT - 1))
+        w = np.ascontiguousarray(w.astype(np.float32))
+        if not np.isfinite(w).all():
+            raise ValueError("knot weights must be finite")
+        knot = np.ascontiguousarray(knot.astype(np.uint32))
+        cache = getattr(self, "_mppi_c", None)
+        if cache is None:
+            cache = self._mppi_c = {}
+        tag = knot.tobytes() + w.tobytes()
+        hit = cache.get("knots")
+        if hit is None or hit[0] != tag:
+            # (int32 on the device: the same 32 bits; knot numbers are far below 2^31)
+            hit = cache["knots"] = (tag, torch.from_numpy(knot.view(np.int32)).to(self.device),
+                                    torch.from_numpy(w).to(self.device))
+        return hit[1], hit[2]
+
+    def _mppi_ext(self, knots, K):
+        """(cs_rollout_mppi_ext with the knot table filled in, the tensors it points to)."""
+        ext = _lib.RolloutMppiExt()
+        ext.struct_size = C.sizeof(_lib.RolloutMppiExt)
+        keep = []
+        if knots is not None:
+            kn, kw = self._mppi_knots(knots, K)
+            ext.knot_dev, ext.knot_weights_dev = kn.data_ptr(), kw.data_ptr()
+            keep = [kn, kw]
+        return ext, keep
+
     def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
-                           stream=0, state=None):
+                           stream=0, state=None, knots=None):
         """The costs of P = `samples` noisy copies of the action tape `actions` [K,N,A] per env, one kernel: sample p
         takes a_k = actions[k-1] + sigma * eps(p, k) in float32 (one multiply, one add), eps the library's counter-based
         noise -- Irwin-Hall of order 4, mean 0, variance 1 - 2**-32, a pure function of (seed, global env id, `stream`,
@@ -1495,6 +1560,10 @@ class CopterVecEnv(_VectorEnvBase):
         R [A,A] symmetric positive semidefinite, shared; a_ref [A] or None (zero); reward_weight >= 0 brings in the
         task's own reward (rollout_states' float64 reward); `stream` is a nonce in [0, 2**32), for example the MPC
         iteration.  No state tape and no noise tensor exist.
+
+        knots=(knot [K], w [K,2]) (mppi_knots(K, hold)) makes the noise smooth: step k takes
+        eps~ = float32(float32(w[k][0] eps(p, knot[k])) + float32(w[k][1] eps(p, knot[k] + 1))) in place of eps(p, k) --
+        tests/mppi_smooth_ref.py restates it bit for bit; None, or the white table mppi_knots(K, 1), is the noise above.
 
         Returns MppiCosts(costs [P,N] float64, best [N] int32: the arg-min over the env's finite costs, the lowest index
         on ties, -1 if none is finite).  Asynchronous on the current stream; the tensors are buffers of this env,
@@ -1533,12 +1602,17 @@ class CopterVecEnv(_VectorEnvBase):
         out = self._rollout_cache(("mppi_costs", P), lambda: MppiCosts(
             torch.empty((P, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)))
         mio.costs_dev, mio.best_dev = out.costs.data_ptr(), out.best.data_ptr()
+        ext, kept = (None, []) if knots is None else self._mppi_ext(knots, K)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_mppi_costs(self._ctx, C.byref(io), C.byref(mio), self._stream()))
-        self._keep = keep + [Qd, Rd, Qfd, sg, ar]
+            if ext is None:
+                _lib.check(self._lib.cs_rollout_mppi_costs(self._ctx, C.byref(io), C.byref(mio), self._stream()))
+            else:
+                _lib.check(self._lib.cs_rollout_mppi_costs_ex(self._ctx, C.byref(io), C.byref(mio), C.byref(ext),
+                                                              self._stream()))
+        self._keep = keep + [Qd, Rd, Qfd, sg, ar] + kept
         return out
 
-    def rollout_mppi_update(self, actions, costs, sigma, lam, stream=0):
+    def rollout_mppi_update(self, actions, costs, sigma, lam, stream=0, knots=None):
         """The MPPI update, one kernel: per env, with beta = its minimum finite cost, w_p = exp(-(costs[p] - beta) / lam)
         (0 for a cost that is not finite) and eta = sum_p w_p,
 
@@ -1546,7 +1620,9 @@ class CopterVecEnv(_VectorEnvBase):
 
         in float64 with p ascending, eps drawn again from the counter: `costs` [P,N] float64 is what
         rollout_mppi_costs(actions, sigma, P, ..., stream=stream) returned for the same actions, sigma and stream.
-        lam > 0 is the temperature.  Returns MppiUpdate(actions [K,N,A] float32, ess [N] float64 = eta^2 / sum_p w_p^2:
+        lam > 0 is the temperature: a scalar, or an [N] float64 device tensor with one temperature per env
+        (rollout_mppi_temperature's); an env whose entry is not finite and > 0 keeps its actions and reports ess = 0.
+        knots: the table rollout_mppi_costs was given.  Returns MppiUpdate(actions [K,N,A] float32, ess [N] float64 = eta^2 / sum_p w_p^2:
         the effective sample size, cost_min [N] = beta).  An env without a finite cost keeps its actions (the same
         bits) and reports ess = 0, cost_min = inf.  Every sum runs inside one lane in a fixed order: two calls give the
         same bits.  Asynchronous on the current stream; the tensors are buffers of this env (two sets, so that the
@@ -1554,12 +1630,16 @@ class CopterVecEnv(_VectorEnvBase):
         env state changes."""
         self._check_open()
         torch = _torch()
-        lam = float(lam)
-        if not (lam > 0.0) or lam == float("inf"):
-            raise ValueError("lam must be finite and > 0, got %r" % (lam,))
+        lam_t = lam if isinstance(lam, torch.Tensor) and lam.dim() > 0 else None
+        if lam_t is None:
+            lam = float(lam)
+            if not (lam > 0.0) or lam == float("inf"):
+                raise ValueError("lam must be finite and > 0, got %r" % (lam,))
         sg = self._mppi_small(sigma, "sigma", np.float32, True)
         io, K, keep = self._rollout_io(actions, None)
         n, ad, dev = self.num_envs, self.action_dim, self.device
+        if lam_t is not None:
+            self._check_tape("rollout_mppi_update", (lam_t, "lam", (n,), torch.float64))
         if not isinstance(costs, torch.Tensor) or costs.dim() != 2 or not 1 <= costs.shape[0] <= _lib.MPPI_MAX_SAMPLES:
             raise ValueError("costs must be the [P,%d] float64 device tensor of rollout_mppi_costs" % n)
         P = int(costs.shape[0])
@@ -1570,12 +1650,54 @@ class CopterVecEnv(_VectorEnvBase):
         out = sets[1] if sets[0].actions.data_ptr() == io.actions_dev else sets[0]
         mio = _lib.RolloutMppiIO()
         mio.struct_size = C.sizeof(_lib.RolloutMppiIO)
-        mio.num_samples, mio.noise_stream, mio.lam = P, self._mppi_stream(stream), lam
+        mio.num_samples, mio.noise_stream = P, self._mppi_stream(stream)
+        mio.lam = 0.0 if lam_t is not None else lam
         mio.sigma_dev, mio.costs_dev = sg.data_ptr(), costs.data_ptr()
         mio.actions_out_dev, mio.ess_dev, mio.cost_min_dev = (t.data_ptr() for t in out)
+        ext, kept = (None, []) if knots is None and lam_t is None else self._mppi_ext(knots, K)
+        if lam_t is not None:
+            ext.lam_dev = lam_t.data_ptr()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_mppi_update(self._ctx, C.byref(io), C.byref(mio), self._stream()))
-        self._keep = keep + [sg, costs]
+            if ext is None:
+                _lib.check(self._lib.cs_rollout_mppi_update(self._ctx, C.byref(io), C.byref(mio), self._stream()))
+            else:
+                _lib.check(self._lib.cs_rollout_mppi_update_ex(self._ctx, C.byref(io), C.byref(mio), C.byref(ext),
+                                                               self._stream()))
+        self._keep = keep + [sg, costs, lam_t] + kept
+        return out
+
+    def rollout_mppi_temperature(self, costs, ess_target, lam_min=1e-6, lam_max=1e6):
+        """The temperature per env at which the MPPI weights of `costs` [P,N] (rollout_mppi_costs') have the effective
+        sample size ess_target, one kernel: with E(lam) = (sum_p w_p)^2 / sum_p w_p^2 over the env's finite costs, 48
+        bisections of ln lam between ln lam_min and ln lam_max, keeping E >= ess_target at the upper end; lam_max where
+        even E(lam_max) < ess_target, lam_min where E(lam_min) >= ess_target, lam_max (and ess 0) for an env without a
+        finite cost.  ess_target >= 1, 0 < lam_min < lam_max.  Returns MppiTemperature(lam [N] float64, for
+        rollout_mppi_update(lam=), ess [N] float64 = E(lam)).  Two calls give the same bits.  Asynchronous on the
+        current stream; the tensors are buffers of this env, overwritten by its next call.  No env state changes."""
+        self._check_open()
+        torch = _torch()
+        n, dev = self.num_envs, self.device
+        target, lo, hi = float(ess_target), float(lam_min), float(lam_max)
+        if not (target >= 1.0) or target == float("inf"):
+            raise ValueError("ess_target must be finite and >= 1, got %r" % (ess_target,))
+        if not (0.0 < lo < hi) or hi == float("inf"):
+            raise ValueError("0 < lam_min < lam_max, both finite, is required, got %r and %r" % (lam_min, lam_max))
+        if not isinstance(costs, torch.Tensor) or costs.dim() != 2 or not 1 <= costs.shape[0] <= _lib.MPPI_MAX_SAMPLES:
+            raise ValueError("costs must be the [P,%d] float64 device tensor of rollout_mppi_costs" % n)
+        P = int(costs.shape[0])
+        self._check_tape("rollout_mppi_costs", (costs, "costs", (P, n), torch.float64))
+        out = self._rollout_cache(("mppi_temperature",), lambda: MppiTemperature(
+            torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)))
+        mio = _lib.RolloutMppiIO()
+        mio.struct_size = C.sizeof(_lib.RolloutMppiIO)
+        mio.num_samples, mio.costs_dev = P, costs.data_ptr()
+        ext = _lib.RolloutMppiExt()
+        ext.struct_size = C.sizeof(_lib.RolloutMppiExt)
+        ext.ess_target, ext.lam_min, ext.lam_max = target, lo, hi
+        ext.lam_out_dev, ext.ess_out_dev = out.lam.data_ptr(), out.ess.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_mppi_temperature(self._ctx, C.byref(mio), C.byref(ext), self._stream()))
+        self._keep = [costs]
         return out
 
     def set_motors(self, motors):

@@ -40,6 +40,10 @@
  *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
  *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
  *   cs_rollout_mppi_update   their cost-weighted average         (the same)
+ *   cs_rollout_mppi_*_ex     the same with smooth knot noise     (the same)
+ *                            and a per-env temperature
+ *   cs_rollout_mppi_temperature  that temperature, solved for    (the same)
+ *                            an effective sample size
  *   cs_get_state             Dynamics.getState / getStatus      dynamics/__init__.py:199-207,223-225
  *   cs_export_state          the same, to device tensors        dynamics/__init__.py:199-207,223-225
  *   cs_set_state             Dynamics.setState / perturb        dynamics/__init__.py:210-217,227-229
@@ -884,6 +888,53 @@ typedef struct cs_rollout_mppi_io {
 } cs_rollout_mppi_io;
 int cs_rollout_mppi_costs(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio, void* stream);
 int cs_rollout_mppi_update(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio, void* stream);
+
+/* MPPI with smooth knot noise and a per-env temperature.  cs_rollout_mppi_costs_ex and
+ * cs_rollout_mppi_update_ex are cs_rollout_mppi_costs and cs_rollout_mppi_update -- the same io and mio, the same
+ * outputs, the same rules -- with the noise law and the temperature taken from a second block, cs_rollout_mppi_ext.
+ *
+ * Noise.  Per step k = 1..K the caller gives a knot number knot_dev[k-1] >= 1 and two float32 weights
+ * knot_weights_dev[k-1][0..1].  With eps(p, m, j) the draw above made with the knot number m in its step slot,
+ *     eps~(p, k, j) = fl32( fl32(w[k][0] * eps(p, knot[k], j)) + fl32(w[k][1] * eps(p, knot[k] + 1, j)) )
+ * two float32 multiplies and one add, none fused; the second term is left out altogether when w[k][1] == 0.  The sample
+ * action and the update's perturbation use fl32(sigma[j] * eps~) exactly where they use fl32(sigma[j] * eps) above;
+ * sample 0 stays the nominal bit for bit.  knot[k] = k with w = (1, 0) is the white noise above, and both calls then
+ * give the bits of cs_rollout_mppi_costs / cs_rollout_mppi_update; so they do with knot_dev and knot_weights_dev both
+ * NULL (one without the other is CS_ERR_ARG).  The caller guarantees knot[k] + 1 <= 16 384 (the keys stay distinct), as
+ * it guarantees sigma >= 0.  Neighbouring steps that share a knot pair are correlated: w = (1 - t, t) / |(1 - t, t)| over
+ * a hold of h steps, t = ((k - 1) mod h) / h, is a piecewise-linear tape of unit variance at every step.
+ * Temperature.  cs_rollout_mppi_update_ex reads lam_dev [N] float64 when it is not NULL: env i weighs its samples with
+ * lambda = lam_dev[i] in place of mio->lam (which is then not looked at).  An entry that is not finite and > 0 leaves
+ * that env's plan unchanged (the same bits) and reports ess = 0; cost_min is beta as ever.
+ * cs_rollout_mppi_temperature solves that lambda per env, on the device, for a target effective sample size.  It
+ * reads mio->num_samples and mio->costs_dev [P,N] only (and checks mio as the other calls do, sigma_dev apart).  With
+ * E(lambda) = (sum_p w_p)^2 / sum_p w_p^2 over the finite costs, the weights above, sums over p ascending in float64:
+ * u_lo = ln lam_min, u_hi = ln lam_max; 48 times u = (u_lo + u_hi) / 2, and u_lo = u if E(exp u) < ess_target, else
+ * u_hi = u; the result is lambda = exp(u_hi).  lambda = lam_max where E(lam_max) < ess_target; lambda = lam_min where
+ * E(lam_min) >= ess_target; an env without a finite cost gets lambda = lam_max and E = 0.  It writes lam_out_dev [N]
+ * (required) and, when not NULL, ess_out_dev [N] = E(lambda).  ess_target >= 1 and 0 < lam_min < lam_max, all finite.
+ * Every sum runs inside one lane in a fixed order: two calls give the same bits.
+ * ext->struct_size must be sizeof(cs_rollout_mppi_ext) (else CS_ERR_ABI) and ext->reserved_ 0; all three blocks are
+ * checked before the context.  knot_dev and knot_weights_dev are 4-B aligned and never written while a call runs.
+ * Asynchronous on `stream`; no env state is written. */
+typedef struct cs_rollout_mppi_ext {
+  uint32_t struct_size;            /* sizeof(cs_rollout_mppi_ext) */
+  uint32_t reserved_;              /* 0 */
+  const uint32_t* knot_dev;        /* costs_ex, update_ex: [K] or NULL (with knot_weights_dev) = white noise */
+  const float* knot_weights_dev;   /* costs_ex, update_ex: [K,2] float32 or NULL */
+  const double* lam_dev;           /* update_ex: [N] float64 or NULL = mio->lam */
+  double ess_target;               /* temperature: >= 1, finite */
+  double lam_min;                  /* temperature: 0 < lam_min < lam_max, finite */
+  double lam_max;
+  double* lam_out_dev;             /* temperature: [N], required */
+  double* ess_out_dev;             /* temperature: [N] or NULL */
+} cs_rollout_mppi_ext;
+int cs_rollout_mppi_costs_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio,
+                             const cs_rollout_mppi_ext* ext, void* stream);
+int cs_rollout_mppi_update_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio,
+                              const cs_rollout_mppi_ext* ext, void* stream);
+int cs_rollout_mppi_temperature(cs_ctx* ctx, const cs_rollout_mppi_io* mio, const cs_rollout_mppi_ext* ext,
+                                void* stream);
 
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in

@@ -4,7 +4,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt > profiles/rollout_mlp_resources.txt
     python3 tools/resource_table.py remarks.txt mlp_grad > profiles/mlp_grad_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_lqr > profiles/rollout_lqr_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_mppi > profiles/rollout_mppi_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_mppi > profiles/rollout_mppi_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_mppi_smooth > profiles/rollout_mppi_smooth_resources.txt"""
 import re
 import sys
 
@@ -40,7 +41,12 @@ HEADS = {"rollout_mlp": """\
 # forward rollout_feedback_kernel<TASK, MODE> (DESIGN.md section 13).""", "rollout_mppi": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_mppi.hip: the sampled rollouts' costs
 # rollout_mppi_costs_kernel<TASK, MODE> (the cost's matrices in 1.3 KiB of LDS), the arg-min mppi_best_kernel and the
-# weighted update rollout_mppi_update_kernel<TASK> (DESIGN.md section 14)."""}
+# weighted update rollout_mppi_update_kernel<TASK> (DESIGN.md section 14).""", "rollout_mppi_smooth": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_mppi_smooth.hip: the costs under knot
+# noise rollout_mppi_smooth_costs_kernel<TASK, MODE> (the cost's matrices and the two knot draws of the A components,
+# a lane-private column each, in the LDS: the draws do not fit the registers of the 3D tasks without scratch), the
+# arg-min mppi_best_kernel, the update rollout_mppi_smooth_update_kernel<TASK> with its per-env temperature and the
+# bisection mppi_temperature_kernel (DESIGN.md section 15)."""}
 
 
 def main(path, which="rollout_mlp"):

@@ -9,9 +9,13 @@ For each configuration, in one process, interleaved over `--rounds` rounds with 
   baseline  noise = sigma randn [K, N P, A]; rollout_states(tiled actions + noise) on the N P env; the quadratic cost and
             the reward summed over the tape; softmin weights over P; the weighted mean of the noise -> us per iteration,
             with its rollout_states part alone beside it
-Timed with torch.cuda events around device-synchronised windows.  The sample-step rate is N P K / costs.
+  costs_smooth, update_smooth   the same two calls with knots=mppi_knots(K, hold) (the kernels of
+            cs_rollout_mppi_costs_ex / cs_rollout_mppi_update_ex), in the same rounds -> us per iteration
+Timed with torch.cuda events around device-synchronised windows.  The sample-step rate is N P K / costs.  The smooth
+kernels against the white ones go to `--smooth-out`; --pairs-only leaves the torch baseline (and its N x P env) out.
 
-    python tools/rollout_mppi_bench.py [--rounds 3] [--steps 64] [--out profiles/rollout_mppi_bench]
+    python tools/rollout_mppi_bench.py [--rounds 3] [--steps 64] [--hold 16] [--pairs-only]
+                                       [--out profiles/rollout_mppi_bench] [--smooth-out profiles/rollout_mppi_smooth_bench]
 """
 import argparse
 import json
@@ -33,24 +37,27 @@ def _time(fn):
     return t0.elapsed_time(t1) * 1e3          # us
 
 
-def measure(n, P, substeps, K, rounds):
+def measure(n, P, substeps, K, rounds, hold=16, pairs_only=False):
     import numpy as np
     import torch
     import gym_copter_amd
     kw = dict(task="lander3d", state_dtype="float32", substeps=substeps, autoreset_mode="disabled", seed=1,
               max_steps=100000)
     env = gym_copter_amd.CopterVecEnv(num_envs=n, **kw)
-    tiled = gym_copter_amd.CopterVecEnv(num_envs=n * P, **kw)
+    tiled = None if pairs_only else gym_copter_amd.CopterVecEnv(num_envs=n * P, **kw)
     try:
         env.reset()
-        tiled.reset()
+        if tiled is not None:
+            tiled.reset()
         dev = env.device
         rng = np.random.default_rng(0)
         a = torch.from_numpy(rng.uniform(0.45, 0.6, (K, n, 4)).astype(np.float32)).to(dev)
         x0 = np.zeros((12, n))
         x0[4] = -rng.uniform(5, 20, n)
         state = {"x": torch.from_numpy(x0).to(dev), "status": torch.full((n,), 3, dtype=torch.uint8, device=dev)}
-        big = {"x": state["x"].repeat(1, P).contiguous(), "status": state["status"].repeat(P).contiguous()}
+        big = None if pairs_only else {"x": state["x"].repeat(1, P).contiguous(),
+                                       "status": state["status"].repeat(P).contiguous()}
+        knots = gym_copter_amd.mppi_knots(K, hold)
         x_ref = torch.zeros((n, 12), dtype=torch.float64, device=dev)
         Q, R = np.eye(12), 0.1 * np.eye(4)
         Qd = torch.eye(12, dtype=torch.float64, device=dev)
@@ -62,6 +69,13 @@ def measure(n, P, substeps, K, rounds):
 
         def update():
             env.rollout_mppi_update(a, got["costs"], sigma, lam)
+
+        def costs_smooth():
+            got["costs_s"] = env.rollout_mppi_costs(a, sigma, P, x_ref, Q, R, reward_weight=1.0, state=state,
+                                                    knots=knots).costs
+
+        def update_smooth():
+            env.rollout_mppi_update(a, got["costs_s"], sigma, lam, knots=knots)
 
         def rollout():
             got["noise"] = sigma * torch.randn((K, n * P, 4), dtype=torch.float32, device=dev)
@@ -79,7 +93,9 @@ def measure(n, P, substeps, K, rounds):
             step = (w[None, :, :, None] * got["noise"].view(K, P, n, 4).double()).sum(1)
             got["new"] = (a.double() + step).float().clamp_(0, 1)
 
-        fns = {"costs": costs, "update": update, "rollout": rollout, "baseline": baseline}
+        fns = {"costs": costs, "costs_smooth": costs_smooth, "update": update, "update_smooth": update_smooth}
+        if not pairs_only:
+            fns.update({"rollout": rollout, "baseline": baseline})
         for fn in fns.values():                                   # warm-up of every shape
             fn()
         best = {}
@@ -89,15 +105,19 @@ def measure(n, P, substeps, K, rounds):
                 best[name] = min(best.get(name, t), t)
     finally:
         env.close()
-        tiled.close()
-    out = {"envs": n, "samples": P, "substeps": substeps, "K": K}
+        if tiled is not None:
+            tiled.close()
+    out = {"envs": n, "samples": P, "substeps": substeps, "K": K, "hold": hold}
     for name in fns:
         out[name + "_us"] = round(best[name], 1)
     out["iteration_us"] = round(best["costs"] + best["update"], 1)
     out["costs_us_per_step_per_1M"] = round(best["costs"] / K / (n * P / 2 ** 20), 3)
-    out["rollout_us_per_step_per_1M"] = round(best["rollout"] / K / (n * P / 2 ** 20), 3)
     out["sample_steps_per_s"] = round(n * P * K / best["costs"] * 1e6, -6)
-    out["baseline_over_iteration"] = round(best["baseline"] / (best["costs"] + best["update"]), 2)
+    out["costs_smooth_over_white"] = round(best["costs_smooth"] / best["costs"], 3)
+    out["update_smooth_over_white"] = round(best["update_smooth"] / best["update"], 3)
+    if not pairs_only:
+        out["rollout_us_per_step_per_1M"] = round(best["rollout"] / K / (n * P / 2 ** 20), 3)
+        out["baseline_over_iteration"] = round(best["baseline"] / (best["costs"] + best["update"]), 2)
     return out
 
 
@@ -108,13 +128,28 @@ def main():
     ap.add_argument("--envs", type=int, nargs="*", default=[256, 4096])
     ap.add_argument("--samples", type=int, nargs="*", default=[256, 1024])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rollout_mppi_bench"))
+    ap.add_argument("--hold", type=int, default=16, help="steps between two knots of the smooth rows")
+    ap.add_argument("--pairs-only", action="store_true", help="the white and smooth kernels only, no torch baseline")
+    ap.add_argument("--smooth-out", default=os.path.join(ROOT, "profiles", "rollout_mppi_smooth_bench"))
     args = ap.parse_args()
-    rows, lines = [], []
+    rows, lines, pairs = [], [], []
     for n in args.envs:
         for P in args.samples:
             for substeps in (1, 10):
-                r = measure(n, P, substeps, args.steps, args.rounds)
+                r = measure(n, P, substeps, args.steps, args.rounds, args.hold, args.pairs_only)
                 rows.append(r)
+                pairs.append("%5d envs x %4d samples  substeps %2d  K %d  hold %d: costs white %9.1f us, smooth %9.1f us "
+                             "(%.3fx) | update white %8.1f us, smooth %8.1f us (%.3fx)"
+                             % (n, P, substeps, args.steps, args.hold, r["costs_us"], r["costs_smooth_us"],
+                                r["costs_smooth_over_white"], r["update_us"], r["update_smooth_us"],
+                                r["update_smooth_over_white"]))
+                print(pairs[-1], flush=True)
+                with open(args.smooth_out + ".txt", "w") as f:
+                    f.write("# tools/rollout_mppi_bench.py: Lander3D, float32 storage, the knot-noise kernels against the "
+                            "white ones, each pair in one process, best of %d interleaved rounds\n" % args.rounds
+                            + "\n".join(pairs) + "\n")
+                if args.pairs_only:
+                    continue
                 lines.append("%5d envs x %4d samples  substeps %2d  K %d: costs %9.1f us (%6.2f us/step per 2^20 sample-envs, "
                              "%.3g sample-steps/s) + update %8.1f us = %9.1f us | baseline %10.1f us (its rollout_states "
                              "and noise %10.1f us, %6.2f us/step per 2^20) = %.2fx"
