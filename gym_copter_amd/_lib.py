@@ -146,6 +146,23 @@ class RolloutMppiExt(C.Structure):
                 ("ess_out_dev", C.c_void_p)]
 
 
+class RolloutPopulationIO(C.Structure):
+    """Mirror of `struct cs_rollout_population_io` (cs_rollout_mlp_population)."""
+    _fields_ = [("struct_size", C.c_uint32), ("hidden", C.c_int32), ("members", C.c_int32),
+                ("envs_per_member", C.c_int32), ("gamma", C.c_double), ("params_table_dev", C.c_void_p),
+                ("returns_dev", C.c_void_p), ("lengths_dev", C.c_void_p), ("end_flags_dev", C.c_void_p),
+                ("end_status_dev", C.c_void_p), ("member_returns_dev", C.c_void_p)]
+
+
+class EsIO(C.Structure):
+    """Mirror of `struct cs_es_io` (cs_es_perturb / cs_es_gradient)."""
+    _fields_ = [("struct_size", C.c_uint32), ("members", C.c_int32), ("num_params", C.c_int32),
+                ("noise_stream", C.c_uint32), ("pair_base", C.c_uint32), ("sigma", C.c_float),
+                ("params_dev", C.c_void_p), ("table_dev", C.c_void_p), ("weights_dev", C.c_void_p),
+                ("grad_dev", C.c_void_p)]
+
+
+ES_PAIR_CHUNK, ES_MAX_MEMBERS, ES_MAX_PARAMS = 32, 65536, 1092   # CS_ES_PAIR_CHUNK, CS_ES_MAX_MEMBERS, CS_ES_MAX_PARAMS
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
@@ -223,6 +240,9 @@ SYMBOLS = {
     "cs_rollout_mppi_update_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),
                                             C.POINTER(RolloutMppiExt), _P]),
     "cs_rollout_mppi_temperature": (C.c_int, [_P, C.POINTER(RolloutMppiIO), C.POINTER(RolloutMppiExt), _P]),
+    "cs_rollout_mlp_population": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutPopulationIO), _P]),
+    "cs_es_perturb": (C.c_int, [_P, C.POINTER(EsIO), _P]),
+    "cs_es_gradient": (C.c_int, [_P, C.POINTER(EsIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -43,5 +43,8 @@ int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, Pa
 // (copterstep_api.hip) the context's scratch of cs_mlp_param_grad (copterstep_mlp_grad.hip): `bytes` of workgroup
 // partials, allocated by the first call (refused while `stream` is being captured) and released by cs_destroy
 int mlp_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
+// (copterstep_api.hip) the context's scratch of cs_es_gradient (copterstep_rollout_es.hip), a buffer of its own under the
+// same rules; every call asks for the same `bytes` (the largest population's partials)
+int es_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
 
 }  // namespace cs

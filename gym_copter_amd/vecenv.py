@@ -102,6 +102,8 @@ MppiCosts = collections.namedtuple("MppiCosts", "costs best")
 MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
 # CopterVecEnv.rollout_mppi_temperature's result
 MppiTemperature = collections.namedtuple("MppiTemperature", "lam ess")
+# CopterVecEnv.rollout_mlp_population's result
+Population = collections.namedtuple("Population", "returns lengths end_flags end_status member_returns")
 MPPI_MAX_KNOT = 16384                                        # knot + 1 <= 16 384: the noise keys stay distinct
 
 
@@ -1699,6 +1701,142 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_rollout_mppi_temperature(self._ctx, C.byref(mio), C.byref(ext), self._stream()))
         self._keep = [costs]
         return out
+
+    # -- population rollouts and evolution strategies ---------------------
+    @staticmethod
+    def _es_u32(v, name):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 1 << 32:
+            raise ValueError("%s must be an int in [0, 2**32), got %r" % (name, v))
+        return int(v)
+
+    def rollout_mlp_population(self, table, K, hidden, envs_per_member, gamma=1.0, start_x=None, start_status=None,
+                               state=None):
+        """M = table.shape[0] policies, each rolled out closed-loop for K steps on its own E = envs_per_member envs and
+        scored by its episode return, one kernel and no tape: env i runs under theta = table[i // E] ([M,P] float32,
+        every row in gym_copter_amd.mlp's layout for `hidden`); N = M E, E a multiple of 64.  With the outputs
+        rollout_mlp_states(table[m], K, hidden) gives for the same start, and d the first step at which an env is
+        terminated or truncated (K if none):
+
+            returns[i] = sum_{k=1..d} gamma^(k-1) reward_k   (float64, k ascending, the discount a running product)
+            lengths[i] = d,  end_flags[i] = terminated_d | truncated_d << 1,  end_status[i] = status_d
+
+        exactly (the policy's float32 arithmetic and the step are rollout_mlp_states'), and member_returns[m] = the mean
+        of returns over the member's envs, summed in a fixed order (the same bits on every call).  The start is
+        rollout_mlp_states': the stored state (its pending perturbation; a pending NEXT_STEP reset is performed in step
+        1), or an explicit one -- start_x [12,N] float64 with start_status [N] (None: all airborne), or `state`,
+        get_state()'s layout.  With stored starts the members see different envs; give every member the same E start
+        points for common random numbers (gym_copter_amd.es does).
+
+        Returns Population(returns [N] float64, lengths [N] int32, end_flags [N] uint8, end_status [N] uint8,
+        member_returns [M] float64).  Asynchronous on the current stream; the tensors are buffers of this env,
+        overwritten by its next call with the same M.  No env state changes."""
+        self._check_open()
+        torch = _torch()
+        n, dev = self.num_envs, self.device
+        if not isinstance(K, (int, np.integer)) or isinstance(K, bool) or K < 1:
+            raise ValueError("K must be an int >= 1, got %r" % (K,))
+        P = _mlp.num_params(self.obs_dim, self.action_dim, hidden)    # (checks hidden)
+        if not isinstance(envs_per_member, (int, np.integer)) or isinstance(envs_per_member, bool) \
+                or envs_per_member < 64 or envs_per_member % 64:
+            raise ValueError("envs_per_member must be a positive multiple of 64, got %r" % (envs_per_member,))
+        E = int(envs_per_member)
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 \
+                or table.shape[1] != P or table.shape[0] < 1:
+            raise ValueError("table must be a [M,%d] float32 torch tensor (one gym_copter_amd.mlp vector of hidden %d per "
+                             "member), got %s" % (P, hidden, getattr(table, "shape", type(table).__name__)))
+        M = int(table.shape[0])
+        if M * E != n:
+            raise ValueError("members x envs_per_member = %d x %d is not num_envs = %d" % (M, E, n))
+        g = float(gamma)
+        if not np.isfinite(g):
+            raise ValueError("gamma must be finite, got %r" % (gamma,))
+        if start_x is not None:
+            if state is not None:
+                raise ValueError("give start_x (with start_status) or state, not both")
+            state = {"x": start_x,
+                     "status": np.full(n, _lib.STATUS_AIRBORNE, np.uint8) if start_status is None else start_status}
+        elif start_status is not None:
+            raise ValueError("start_status describes an explicit start: start_x is required")
+        tb = table.detach().to(dev).contiguous()
+        io, K, keep = self._rollout_io(None, state, int(K))
+        out = self._rollout_cache(("population", M), lambda: Population(
+            torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+            torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev),
+            torch.empty(M, dtype=torch.float64, device=dev)))
+        pio = _lib.RolloutPopulationIO()
+        pio.struct_size = C.sizeof(_lib.RolloutPopulationIO)
+        pio.hidden, pio.members, pio.envs_per_member, pio.gamma = hidden, M, E, g
+        pio.params_table_dev = tb.data_ptr()
+        pio.returns_dev, pio.lengths_dev, pio.end_flags_dev, pio.end_status_dev, pio.member_returns_dev = (
+            t.data_ptr() for t in out)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_mlp_population(self._ctx, C.byref(io), C.byref(pio), self._stream()))
+        self._keep = keep + [tb]
+        return out
+
+    def _es_io(self, members, num_params, nonce, pair_base):
+        if not isinstance(members, (int, np.integer)) or isinstance(members, bool) \
+                or not 2 <= int(members) <= _lib.ES_MAX_MEMBERS or int(members) % 2:
+            raise ValueError("members must be an even int in [2, %d], got %r" % (_lib.ES_MAX_MEMBERS, members))
+        if not isinstance(num_params, (int, np.integer)) or isinstance(num_params, bool) \
+                or not 1 <= int(num_params) <= _lib.ES_MAX_PARAMS:
+            raise ValueError("num_params must be an int in [1, %d], got %r" % (_lib.ES_MAX_PARAMS, num_params))
+        eio = _lib.EsIO()
+        eio.struct_size = C.sizeof(_lib.EsIO)
+        eio.members, eio.num_params = int(members), int(num_params)
+        eio.noise_stream, eio.pair_base = self._es_u32(nonce, "nonce"), self._es_u32(pair_base, "pair_base")
+        return eio
+
+    def es_perturb(self, params, sigma, members, nonce, pair_base=0):
+        """The mirrored population of an evolution strategy around the centre `params` ([P] float32), one kernel:
+
+            table[2i] = float32(params + float32(sigma eps_i)),   table[2i+1] = float32(params - float32(sigma eps_i))
+
+        for the pairs i = 0 .. members/2 - 1, eps_i [P] the library's counter-based noise -- Irwin-Hall of order 4, mean
+        0, variance 1 - 2**-32, a pure function of (seed, `nonce`, the global pair index pair_base + i, the parameter
+        index): tests/es_ref.py restates it in NumPy bit for bit.  sigma >= 0; members even; nonce and pair_base in
+        [0, 2**32) (pair_base: where this call's pairs sit in a population split over several calls or devices).
+        Returns table [members,P] float32, a buffer of this env overwritten by its next call with the same shape.
+        Asynchronous on the current stream."""
+        self._check_open()
+        torch = _torch()
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.dim() != 1:
+            raise ValueError("params must be a 1-D float32 torch tensor, got %s"
+                             % (getattr(params, "dtype", type(params).__name__),))
+        sg = float(sigma)
+        if not (sg >= 0.0) or sg == float("inf"):
+            raise ValueError("sigma must be finite and >= 0, got %r" % (sigma,))
+        eio = self._es_io(members, int(params.shape[0]), nonce, pair_base)
+        th = params.detach().to(self.device).contiguous()
+        table = self._rollout_cache(("es_table", eio.members, eio.num_params), lambda: torch.empty(
+            (eio.members, eio.num_params), dtype=torch.float32, device=self.device))
+        eio.sigma, eio.params_dev, eio.table_dev = sg, th.data_ptr(), table.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_es_perturb(self._ctx, C.byref(eio), self._stream()))
+        self._keep = [th]
+        return table
+
+    def es_gradient(self, weights, nonce, num_params, pair_base=0):
+        """The search gradient of an evolution strategy, g[p] = sum_i (weights[2i] - weights[2i+1]) eps_i[p] in float64,
+        two kernels: `weights` [M] float64 (a device tensor: the shaped fitness of es_perturb's members, for example
+        their centred ranks) and the noise of es_perturb(.., nonce, pair_base) drawn again -- no table is read.  The sum
+        runs in a fixed order (the same bits on every call) and the result is written, not accumulated; the scale
+        1 / (M sigma) is the caller's.  Returns g [num_params] float64, a buffer of this env overwritten by its next call
+        with the same num_params.  Asynchronous on the current stream."""
+        self._check_open()
+        torch = _torch()
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 1:
+            raise ValueError("weights must be a [M] float64 device tensor")
+        M = int(weights.shape[0])
+        eio = self._es_io(M, num_params, nonce, pair_base)
+        self._check_tape("the shaped fitness", (weights, "weights", (M,), torch.float64))
+        g = self._rollout_cache(("es_grad", eio.num_params), lambda: torch.empty(
+            eio.num_params, dtype=torch.float64, device=self.device))
+        eio.weights_dev, eio.grad_dev = weights.data_ptr(), g.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_es_gradient(self._ctx, C.byref(eio), self._stream()))
+        self._keep = [weights]
+        return g
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

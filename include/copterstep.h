@@ -936,6 +936,88 @@ int cs_rollout_mppi_update_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rol
 int cs_rollout_mppi_temperature(cs_ctx* ctx, const cs_rollout_mppi_io* mio, const cs_rollout_mppi_ext* ext,
                                 void* stream);
 
+/* Population rollouts and evolution strategies for the MLP policy: M parameter vectors, each
+ * rolled out closed-loop on its own E envs and scored by its episode return, without a tape; the mirrored population
+ * around a centre, and the search gradient of its shaped fitness, on the device.
+ *
+ * cs_rollout_mlp_population.  N = members x envs_per_member (else CS_ERR_ARG), envs_per_member a multiple of 64; env i
+ * belongs to member i / E and runs under theta = params_table_dev[i / E] ([M,P] float32, every row in
+ * cs_rollout_mlp_io's layout for `hidden`).  io gives the start and K as it does for cs_rollout_mlp_states (stored or
+ * explicit start, the pending perturbation, a pending NEXT_STEP reset, the step counter; io->actions_dev must be NULL,
+ * its outputs, cotangents and gradients are not used).  With reward_k, terminated_k, truncated_k, status_k what
+ * cs_rollout_mlp_states returns for that start with params_dev = the member's row and no offsets, and d = the first
+ * step k in 1..K with terminated_k or truncated_k set, or K if there is none:
+ *   returns_dev     [N] float64  sum_{k=1..d} disc_k reward_k: k ascending from 0.0, every product and every sum rounded
+ *                                on its own (no contraction), disc_1 = 1, disc_{k+1} = fl64(disc_k x gamma)   (required)
+ *   lengths_dev     [N] int32    d
+ *   end_flags_dev   [N] uint8    bit 0: terminated_d, bit 1: truncated_d
+ *   end_status_dev  [N] uint8    status_d (CS_STATUS_*)
+ * each of the last three may be NULL.  A lane with a NEXT_STEP reset pending performs that reset in step 1 (reward 0,
+ * no flag) and goes on with the new episode, as in cs_rollout_mlp_states.  The policy's float32 arithmetic is
+ * cs_rollout_mlp_states' bit for bit, so all four outputs are exactly what the tapes give.  No env state and no tape is
+ * written; a wavefront whose 64 envs are all past d leaves the step loop.
+ *   member_returns_dev [M] float64 or NULL: the mean of returns over the member's E envs, by a second kernel: lane l of
+ * the member's wavefront adds returns[m E + l + 64 t] for t = 0, 1, .. in that order from 0.0; then for off = 32, 16, 8,
+ * 4, 2, 1 lane l adds the sum of lane l + off (lanes below off only: a binary tree); the result is lane 0's sum / E.
+ * No atomics: the same inputs give the same bits on every call.
+ * pio->struct_size must be sizeof(cs_rollout_population_io) (else CS_ERR_ABI); both blocks are checked before the
+ * context, N = M E with it.  The table is read by the scalar unit: 4-B aligned, never written while a call runs.
+ * gamma is finite.  Asynchronous on `stream`. */
+typedef struct cs_rollout_population_io {
+  uint32_t struct_size;           /* sizeof(cs_rollout_population_io) */
+  int32_t hidden;                 /* 0 .. CS_MLP_MAX_HIDDEN */
+  int32_t members;                /* M >= 1 */
+  int32_t envs_per_member;        /* E: a positive multiple of 64 */
+  double gamma;                   /* the discount, finite */
+  const float* params_table_dev;  /* [M,P] float32, required */
+  double* returns_dev;            /* [N], required */
+  int32_t* lengths_dev;           /* [N] or NULL */
+  uint8_t* end_flags_dev;         /* [N] or NULL */
+  uint8_t* end_status_dev;        /* [N] or NULL */
+  double* member_returns_dev;     /* [M] or NULL */
+} cs_rollout_population_io;
+int cs_rollout_mlp_population(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_population_io* pio, void* stream);
+
+/* The mirrored population of an evolution strategy and its search gradient.  Noise: pair i = 0 .. M/2 - 1 of a call has
+ * the global pair index g = pair_base + i (mod 2^32); eps(g, p) for parameter p is ONE Philox2x32-10 call with counter =
+ * (g, noise_stream) and key = key_es + p (mod 2^32), key_es = lo32(splitmix64(splitmix64(splitmix64(seed)))): a fourth
+ * mix of the context's seed beside the two keys of cs_seed and the MPPI key.  The 64 bits give eps exactly as the MPPI
+ * draw above: eps = (float)(u0 + u1 + u2 + u3 - 131070) * CS_MPPI_NOISE_SCALE, Irwin-Hall of order 4, mean 0, variance
+ * 1 - 2^-32.  eps is a pure function of (seed, noise_stream, g, p): independent of M, P, of how a population is split
+ * over calls (pair_base) and of the launch history; g and noise_stream are full 32-bit numbers, p < 2^32.
+ *
+ * cs_es_perturb writes table_dev [M,P] float32 from the centre params_dev [P]:
+ *     table[2i][p] = fl32( theta[p] + fl32(sigma * eps(g, p)) ),  table[2i+1][p] = fl32( theta[p] - fl32(sigma * eps(g, p)) )
+ * one float32 multiply and one add (subtract), not fused.  sigma >= 0 and finite; sigma = 0 gives M copies of theta.
+ * cs_es_gradient writes grad_dev [P] float64 from the caller's weights_dev [M] float64 (the shaped fitness):
+ *     g[p] = sum_{i} (w[2i] - w[2i+1]) * (double)eps(g_i, p)
+ * with eps drawn again (neither the table nor theta is read), every difference, product and sum rounded on its own.  The
+ * order is fixed: pairs in chunks of CS_ES_PAIR_CHUNK, i ascending from 0.0 inside a chunk, then the chunks' partial
+ * sums added in chunk order from 0.0.  No floating-point atomics: the same inputs give the same bits on every call, and
+ * grad_dev is WRITTEN, not accumulated.  The scale (1 / (M sigma) for the usual estimator) is the caller's.  The partial
+ * sums live in a scratch of the context (8.9 MB, allocated by the first cs_es_gradient call on it: make that call outside
+ * graph capture; released by cs_destroy): cs_es_gradient calls on one context must be ordered on one stream.
+ * M is even, 2 <= M <= CS_ES_MAX_MEMBERS; 1 <= num_params <= CS_ES_MAX_PARAMS (the largest policy of cs_rollout_mlp_io).
+ * eio->struct_size must be sizeof(cs_es_io) (else CS_ERR_ABI); the block is checked before the context.  Asynchronous on
+ * `stream`; no env state is read or written. */
+#define CS_ES_PAIR_CHUNK 32
+#define CS_ES_MAX_MEMBERS 65536
+#define CS_ES_MAX_PARAMS 1092
+typedef struct cs_es_io {
+  uint32_t struct_size;        /* sizeof(cs_es_io) */
+  int32_t members;             /* M: even, in [2, CS_ES_MAX_MEMBERS] */
+  int32_t num_params;          /* P in [1, CS_ES_MAX_PARAMS] */
+  uint32_t noise_stream;       /* the nonce of the noise */
+  uint32_t pair_base;          /* the global index of this call's pair 0 */
+  float sigma;                 /* perturb: >= 0, finite */
+  const float* params_dev;     /* perturb: [P] theta, required */
+  float* table_dev;            /* perturb: [M,P], required */
+  const double* weights_dev;   /* gradient: [M], required */
+  double* grad_dev;            /* gradient: [P], required */
+} cs_es_io;
+int cs_es_perturb(cs_ctx* ctx, const cs_es_io* eio, void* stream);
+int cs_es_gradient(cs_ctx* ctx, const cs_es_io* eio, void* stream);
+
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in
  * upstream slot order (the full state, incl. psi / dpsi, which the Lander observation omits),

@@ -5,7 +5,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt mlp_grad > profiles/mlp_grad_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_lqr > profiles/rollout_lqr_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_mppi > profiles/rollout_mppi_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_mppi_smooth > profiles/rollout_mppi_smooth_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_mppi_smooth > profiles/rollout_mppi_smooth_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_es > profiles/rollout_es_resources.txt"""
 import re
 import sys
 
@@ -46,7 +47,11 @@ HEADS = {"rollout_mlp": """\
 # noise rollout_mppi_smooth_costs_kernel<TASK, MODE> (the cost's matrices and the two knot draws of the A components,
 # a lane-private column each, in the LDS: the draws do not fit the registers of the 3D tasks without scratch), the
 # arg-min mppi_best_kernel, the update rollout_mppi_smooth_update_kernel<TASK> with its per-env temperature and the
-# bisection mppi_temperature_kernel (DESIGN.md section 15)."""}
+# bisection mppi_temperature_kernel (DESIGN.md section 15).""", "rollout_es": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_es.hip: the population rollout
+# rollout_mlp_population_kernel<TASK, MODE> (each wavefront under its member's weights, read by scalar loads; no LDS; 3 wavefronts per SIMD),
+# the member mean member_mean_kernel, the mirrored population es_perturb_kernel and the search gradient
+# es_gradient_kernel with its fixed-order sum es_gradient_sum_kernel (DESIGN.md section 16)."""}
 
 
 def main(path, which="rollout_mlp"):
