@@ -5,12 +5,13 @@ and the Gymnasium-style vector-env host class.  See DESIGN.md and INTEGRATION.md
 """
 from ._lib import CopterStepError  # noqa: F401
 from .vecenv import CopterVecEnv, LqrGains, MlpRollout, MppiCosts, MppiUpdate, Rollout, StepJacobian  # noqa: F401
-from .vecenv import MppiTemperature, Population, mppi_knots  # noqa: F401
+from .vecenv import ActorCritic, MppiTemperature, Population, mppi_knots  # noqa: F401
 from .autodiff import differentiable_mlp_rollout, differentiable_rollout  # noqa: F401
 from . import mlp  # noqa: F401
 from .ilqr import ilqr  # noqa: F401
 from .mppi import mppi  # noqa: F401
 from .es import es  # noqa: F401
+from .ppo import ppo  # noqa: F401
 from .spaces import box_class as _box_class
 
 # The Box class the envs' spaces are instances of: gymnasium.spaces.Box when Gymnasium is importable (so that

@@ -162,6 +162,24 @@ class EsIO(C.Structure):
                 ("grad_dev", C.c_void_p)]
 
 
+class RolloutAcIO(C.Structure):
+    """Mirror of `struct cs_rollout_ac_io` (cs_rollout_actor_critic)."""
+    _fields_ = [("struct_size", C.c_uint32), ("num_steps", C.c_int32), ("hidden", C.c_int32),
+                ("critic_hidden", C.c_int32), ("nonce", C.c_uint32), ("deterministic", C.c_uint32),
+                ("actor_dev", C.c_void_p), ("critic_dev", C.c_void_p), ("log_std_dev", C.c_void_p),
+                ("obs_dev", C.c_void_p), ("actions_dev", C.c_void_p), ("means_dev", C.c_void_p),
+                ("logp_dev", C.c_void_p), ("values_dev", C.c_void_p), ("reward_dev", C.c_void_p),
+                ("flags_dev", C.c_void_p), ("live_dev", C.c_void_p)]
+
+
+class GaeIO(C.Structure):
+    """Mirror of `struct cs_gae_io` (cs_gae)."""
+    _fields_ = [("struct_size", C.c_uint32), ("num_steps", C.c_int32), ("flag_stride", C.c_uint32),
+                ("reserved_", C.c_uint32), ("gamma", C.c_double), ("lam", C.c_double), ("reward_dev", C.c_void_p),
+                ("values_dev", C.c_void_p), ("terminated_dev", C.c_void_p), ("truncated_dev", C.c_void_p),
+                ("advantages_dev", C.c_void_p), ("returns_dev", C.c_void_p)]
+
+
 ES_PAIR_CHUNK, ES_MAX_MEMBERS, ES_MAX_PARAMS = 32, 65536, 1092   # CS_ES_PAIR_CHUNK, CS_ES_MAX_MEMBERS, CS_ES_MAX_PARAMS
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
@@ -243,6 +261,8 @@ SYMBOLS = {
     "cs_rollout_mlp_population": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutPopulationIO), _P]),
     "cs_es_perturb": (C.c_int, [_P, C.POINTER(EsIO), _P]),
     "cs_es_gradient": (C.c_int, [_P, C.POINTER(EsIO), _P]),
+    "cs_rollout_actor_critic": (C.c_int, [_P, C.POINTER(RolloutAcIO), _P]),
+    "cs_gae": (C.c_int, [_P, C.POINTER(GaeIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -104,6 +104,8 @@ MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
 MppiTemperature = collections.namedtuple("MppiTemperature", "lam ess")
 # CopterVecEnv.rollout_mlp_population's result
 Population = collections.namedtuple("Population", "returns lengths end_flags end_status member_returns")
+# CopterVecEnv.rollout_actor_critic's result
+ActorCritic = collections.namedtuple("ActorCritic", "obs actions means logp values reward terminated truncated live")
 MPPI_MAX_KNOT = 16384                                        # knot + 1 <= 16 384: the noise keys stay distinct
 
 
@@ -1837,6 +1839,123 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_es_gradient(self._ctx, C.byref(eio), self._stream()))
         self._keep = [weights]
         return g
+
+    # -- on-policy actor-critic collection and GAE ---------------------------
+    def rollout_actor_critic(self, actor, critic, log_std, K, hidden, critic_hidden=None, nonce=0, deterministic=False,
+                             means=False):
+        """K closed-loop steps under a Gaussian MLP policy with a value head, one kernel, with everything a PPO / A2C
+        learner needs of them.  The env ADVANCES (its own auto-reset mode), exactly as step_many would under the
+        returned actions.  actor [P] float32 is a gym_copter_amd.mlp vector of `hidden`; critic [Pv] float32 one with
+        act_dim = 1 and `critic_hidden` (None: `hidden`), or None for no values; log_std [A] float32.  Per step, on the
+        observation o the previous step returned (step 1: the stored state's):
+
+            mu = actor(o), V = critic(o), a = float32(mu + float32(exp(log_std) eps)), eps ~ N(0, 1)
+
+        (deterministic=True: a = mu) and logp = log N(a; mu, exp(log_std)^2) computed in float64 from the stored a and
+        mu.  eps is the library's counter-based Box-Muller draw, a pure function of (seed, `nonce`, global env id, step,
+        component): tests/ppo_ref.py restates it.  Returns ActorCritic(obs [K+1,N,OBS] -- row 0 the stored state's
+        observation, row K the bootstrap observation --, actions [K,N,A], means [K,N,A] or None (means=True), logp [K,N],
+        values [K+1,N] or None, reward [K,N], terminated [K,N], truncated [K,N], live [K,N] bool: False for a next_step
+        reset step, whose action the env ignores).  Asynchronous on the current stream; the tensors are buffers of this
+        env, overwritten by its next call with the same K."""
+        self._check_open()
+        torch = _torch()
+        n, dev, A, od = self.num_envs, self.device, self.action_dim, self.obs_dim
+        if not isinstance(K, (int, np.integer)) or isinstance(K, bool) or K < 1:
+            raise ValueError("K must be an int >= 1, got %r" % (K,))
+        K = int(K)
+        P = _mlp.num_params(od, A, hidden)                                # (checks hidden)
+        if critic_hidden is None:
+            critic_hidden = hidden
+        Pv = _mlp.num_params(od, 1, critic_hidden)
+        nonce = self._es_u32(nonce, "nonce")
+
+        def vec(t, size, name):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (size,):
+                raise ValueError("%s must be a [%d] float32 torch tensor, got %s"
+                                 % (name, size, getattr(t, "shape", type(t).__name__)))
+            return t.detach().to(dev).contiguous()
+        th = vec(actor, P, "actor")
+        tv = vec(critic, Pv, "critic") if critic is not None else None
+        ls = vec(log_std, A, "log_std")
+
+        def make():
+            flags = torch.empty((K, n, 2), dtype=torch.uint8, device=dev)        # interleaved flags
+            return {"obs": torch.empty((K + 1, n, od), dtype=torch.float32, device=dev),
+                    "actions": torch.empty((K, n, A), dtype=torch.float32, device=dev),
+                    "logp": torch.empty((K, n), dtype=torch.float32, device=dev),
+                    "reward": torch.empty((K, n), dtype=torch.float32, device=dev),
+                    "flags": flags, "live": torch.empty((K, n), dtype=torch.uint8, device=dev)}
+        buf = self._rollout_cache(("actor_critic", K), make)
+        if means and "means" not in buf:
+            buf["means"] = torch.empty((K, n, A), dtype=torch.float32, device=dev)
+        if tv is not None and "values" not in buf:
+            buf["values"] = torch.empty((K + 1, n), dtype=torch.float32, device=dev)
+        aio = _lib.RolloutAcIO()
+        aio.struct_size = C.sizeof(_lib.RolloutAcIO)
+        aio.num_steps, aio.hidden, aio.critic_hidden = K, hidden, critic_hidden
+        aio.nonce, aio.deterministic = nonce, 1 if deterministic else 0
+        aio.actor_dev, aio.log_std_dev = th.data_ptr(), ls.data_ptr()
+        aio.critic_dev = tv.data_ptr() if tv is not None else None
+        aio.obs_dev, aio.actions_dev, aio.logp_dev = (buf[k].data_ptr() for k in ("obs", "actions", "logp"))
+        aio.reward_dev, aio.flags_dev, aio.live_dev = (buf[k].data_ptr() for k in ("reward", "flags", "live"))
+        aio.means_dev = buf["means"].data_ptr() if means else None
+        aio.values_dev = buf["values"].data_ptr() if tv is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_actor_critic(self._ctx, C.byref(aio), self._stream()))
+        self._keep = [th, tv, ls]
+        flags = buf["flags"]
+        return ActorCritic(buf["obs"], buf["actions"], buf["means"] if means else None, buf["logp"],
+                           buf["values"] if tv is not None else None, buf["reward"], flags[:, :, 0].view(torch.bool),
+                           flags[:, :, 1].view(torch.bool), buf["live"].view(torch.bool))
+
+    def gae(self, reward, values, terminated, truncated, gamma=0.99, lam=0.95):
+        """Generalised advantage estimation over rollout_actor_critic's tapes, one kernel: reward [K,N] float32, values
+        [K+1,N] float32, terminated and truncated [K,N] bool or uint8 (device tensors) -> (advantages, returns), both
+        [K,N] float32:
+
+            delta_k = r_k + gamma V_{k+1} nd_k - V_k,   adv_k = delta_k + gamma lam nd_k adv_{k+1},   ret_k = adv_k + V_k
+
+        with nd_k = 0 where step k terminated OR truncated its episode (truncation cuts the bootstrap as termination
+        does: the K-step forms return no final observation to bootstrap from) and 1 elsewhere.  float32 in a fixed order,
+        no fused operation: tests/ppo_ref.py gives the same bits in NumPy.  Asynchronous on the current stream; the
+        results are buffers of this env, overwritten by its next call with the same K."""
+        self._check_open()
+        torch = _torch()
+        n, dev = self.num_envs, self.device
+        if not isinstance(reward, torch.Tensor) or reward.dim() != 2:
+            raise ValueError("reward must be a [K,%d] float32 device tensor" % n)
+        K = int(reward.shape[0])
+        self._check_tape("rollout_actor_critic", (reward, "reward", (K, n), torch.float32),
+                         (values, "values", (K + 1, n), torch.float32))
+        g, l = float(gamma), float(lam)
+        with np.errstate(over="ignore"):
+            narrowed = (np.float32(g), np.float32(l), np.float32(g) * np.float32(l))
+        if not np.isfinite(g) or not np.isfinite(l) or not np.all(np.isfinite(narrowed)):
+            raise ValueError("gamma and lam must be finite (in float32, and their product too), got %r and %r"
+                             % (gamma, lam))
+        flags = []
+        for t, name in ((terminated, "terminated"), (truncated, "truncated")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (K, n) or t.dtype not in (torch.bool, torch.uint8) \
+                    or t.device != dev:
+                raise ValueError("%s must be a [%d,%d] bool or uint8 tensor on %s" % (name, K, n, dev))
+            flags.append(t.view(torch.uint8) if t.dtype == torch.bool else t)
+        # the two columns of one interleaved [K,N,2] array (what rollout_actor_critic returns) are read in place
+        stride = 2 if all(t.stride() == (2 * n, 2) for t in flags) else 1
+        if stride == 1:
+            flags = [t.contiguous() for t in flags]
+        out = self._rollout_cache(("gae", K), lambda: (torch.empty((K, n), dtype=torch.float32, device=dev),
+                                                       torch.empty((K, n), dtype=torch.float32, device=dev)))
+        gio = _lib.GaeIO()
+        gio.struct_size = C.sizeof(_lib.GaeIO)
+        gio.num_steps, gio.flag_stride, gio.gamma, gio.lam = K, stride, g, l
+        gio.reward_dev, gio.values_dev = reward.data_ptr(), values.data_ptr()
+        gio.terminated_dev, gio.truncated_dev = flags[0].data_ptr(), flags[1].data_ptr()
+        gio.advantages_dev, gio.returns_dev = out[0].data_ptr(), out[1].data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_gae(self._ctx, C.byref(gio), self._stream()))
+        self._keep = [reward, values] + flags
+        return out
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

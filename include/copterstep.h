@@ -1018,6 +1018,89 @@ typedef struct cs_es_io {
 int cs_es_perturb(cs_ctx* ctx, const cs_es_io* eio, void* stream);
 int cs_es_gradient(cs_ctx* ctx, const cs_es_io* eio, void* stream);
 
+/* On-policy actor-critic collection and generalised advantage estimation: what a PPO or A2C
+ * learner needs of K closed-loop steps, in one launch, with the env in registers between the steps.
+ *
+ * cs_rollout_actor_critic runs K = num_steps steps under the env's own auto-reset mode and ADVANCES the stored state
+ * exactly as cs_step_many would under the same actions (the step is the one cs_step runs).  With o_{k-1} the float32
+ * observation the previous step returned (k = 1: that of the stored state), per step k = 1..K:
+ *     mu  = pi_actor(o_{k-1})    cs_rollout_mlp_io's policy and float32 arithmetic (fmaf chains from the bias in index
+ *                                order, the device library's tanhf, nothing contracted), hidden in 0 .. CS_MLP_MAX_HIDDEN
+ *     V   = pi_critic(o_{k-1})   the same arithmetic with A = 1 and critic_hidden (critic_dev NULL: no values)
+ *     a_c = fl32( mu_c + fl32(sigma_c * eps_c) ),  sigma_c = expf(log_std[c]) in float32: one multiply and one add, not
+ *                                fused; with `deterministic` != 0, a = mu and no noise is drawn
+ *     logp = -1/2 sum_c z_c^2 - sum_c log_std[c] - (A/2) ln(2 pi) in float64, c ascending, stored as float32, with
+ *                                z_c = ((double)a_c - (double)mu_c) * exp(-(double)log_std[c]): computed from the
+ *                                STORED action, so a learner that recomputes it from the tapes gets the ratio 1
+ * then the step with that action.  Noise: eps of (g, nonce, k, c), g = the global env id the reset draw uses (sharding
+ * cannot change a draw): ONE Philox2x32-10 call per pair of components with counter = (g, nonce) and key = key_pi + 2 k +
+ * (c >> 1) (mod 2^32), key_pi = lo32(splitmix64^4(seed)): a fifth mix of the context's seed beside the two keys of cs_seed,
+ * the MPPI key and the ES key.  With m1, m2 the top 24 bits of the two output words, in float32: u1 = (m1 + 0.5) 2^-24,
+ * u2 = m2 2^-24, R = sqrtf(-2 logf(u1)), eps_even = R cosf(2 pi u2), eps_odd = R sinf(2 pi u2) -- Box-Muller: a true
+ * Gaussian, a pure function of (seed, nonce, g, k, c), independent of N, K and the launch history.  u1 and u2 are
+ * reproducible bit for bit, eps to the device library's logf / sinf / cosf accuracy.
+ * Outputs, [K..] row blocks, every pointer 16-B aligned:
+ *   obs_dev     [K+1,N,OBS] float32  row 0 = the stored state's observation, row k = what step k returned (required)
+ *   actions_dev [K,N,A] float32      the action taken                                                      (required)
+ *   means_dev   [K,N,A] float32      mu, or NULL
+ *   logp_dev    [K,N] float32        as above                                                               (required)
+ *   values_dev  [K+1,N] float32      row k = V(obs row k), k = 0..K; required with critic_dev, else must be NULL
+ *   reward_dev  [K,N] float32        as cs_step_many                                                        (required)
+ *   flags_dev   [K,N,2] uint8        terminated, truncated interleaved                                      (required)
+ *   live_dev    [K,N] uint8          0 for a CS_AUTORESET_NEXT_STEP reset step (the env ignores its action, the reward is
+ *                                    0), else 1: always 1 under SAME_STEP and with auto-reset disabled         (required)
+ * aio->struct_size must be sizeof(cs_rollout_ac_io) (else CS_ERR_ABI); the block is checked before the context.  An
+ * open served session is refused, and so are packed rows (reward_dev == obs_dev + OBS ...: cs_step_io).  The weights
+ * are read by the scalar unit: 4-B aligned, never written while a call runs.  Asynchronous on `stream`. */
+typedef struct cs_rollout_ac_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_ac_io) */
+  int32_t num_steps;           /* K >= 1 */
+  int32_t hidden;              /* the actor's, 0 .. CS_MLP_MAX_HIDDEN */
+  int32_t critic_hidden;       /* the critic's, 0 .. CS_MLP_MAX_HIDDEN */
+  uint32_t nonce;              /* the nonce of the noise */
+  uint32_t deterministic;      /* 0: sample, 1: a = mu */
+  const float* actor_dev;      /* [P] float32, cs_rollout_mlp_io's layout, required */
+  const float* critic_dev;     /* [Pv] float32, the same layout with A = 1, or NULL */
+  const float* log_std_dev;    /* [A] float32, required */
+  float* obs_dev;              /* [K+1,N,OBS] */
+  float* actions_dev;          /* [K,N,A] */
+  float* means_dev;            /* [K,N,A] or NULL */
+  float* logp_dev;             /* [K,N] */
+  float* values_dev;           /* [K+1,N], with critic_dev */
+  float* reward_dev;           /* [K,N] */
+  uint8_t* flags_dev;          /* [K,N,2] */
+  uint8_t* live_dev;           /* [K,N] */
+} cs_rollout_ac_io;
+int cs_rollout_actor_critic(cs_ctx* ctx, const cs_rollout_ac_io* aio, void* stream);
+
+/* Generalised advantage estimation over the tapes above, one kernel: lane = env, k descending, float32 in a fixed order
+ * with every operation rounded on its own (no fma), so that NumPy float32 reproduces both outputs bit for bit:
+ *     nd_k  = 1 - (terminated_k | truncated_k)
+ *     delta = (r_k + (g * V_{k+1}) * nd_k) - V_k
+ *     adv_k = delta + ((gl * nd_k) * adv_{k+1}),  adv_{K+1} = 0
+ *     ret_k = adv_k + V_k
+ * with g = fl32(gamma) and gl = fl32(fl32(gamma) * fl32(lam)), rounded once on the host.  A truncated step cuts the
+ * bootstrap exactly as a terminated one does (the K-step forms return no final observation to bootstrap from).
+ * N is the context's; terminated_dev / truncated_dev are [K,N] uint8 with `flag_stride` bytes between an env's and the
+ * next env's flag: 1 = two plain arrays, 2 = the two columns of one interleaved [K,N,2] array.  gamma and lam are finite.
+ * gio->struct_size must be sizeof(cs_gae_io) (else CS_ERR_ABI); the block is checked before the context.  No env state is
+ * read or written; no atomics.  Asynchronous on `stream`. */
+typedef struct cs_gae_io {
+  uint32_t struct_size;          /* sizeof(cs_gae_io) */
+  int32_t num_steps;             /* K >= 1 */
+  uint32_t flag_stride;          /* 1 or 2 */
+  uint32_t reserved_;            /* 0 */
+  double gamma;
+  double lam;
+  const float* reward_dev;       /* [K,N], required */
+  const float* values_dev;       /* [K+1,N], required */
+  const uint8_t* terminated_dev; /* [K,N] (stride flag_stride), required */
+  const uint8_t* truncated_dev;  /* [K,N] (stride flag_stride), required */
+  float* advantages_dev;         /* [K,N], required */
+  float* returns_dev;            /* [K,N], required */
+} cs_gae_io;
+int cs_gae(cs_ctx* ctx, const cs_gae_io* gio, void* stream);
+
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in
  * upstream slot order (the full state, incl. psi / dpsi, which the Lander observation omits),

@@ -6,7 +6,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_lqr > profiles/rollout_lqr_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_mppi > profiles/rollout_mppi_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_mppi_smooth > profiles/rollout_mppi_smooth_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_es > profiles/rollout_es_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_es > profiles/rollout_es_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_ac > profiles/rollout_ac_resources.txt"""
 import re
 import sys
 
@@ -51,7 +52,10 @@ HEADS = {"rollout_mlp": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_es.hip: the population rollout
 # rollout_mlp_population_kernel<TASK, MODE> (each wavefront under its member's weights, read by scalar loads; no LDS; 3 wavefronts per SIMD),
 # the member mean member_mean_kernel, the mirrored population es_perturb_kernel and the search gradient
-# es_gradient_kernel with its fixed-order sum es_gradient_sum_kernel (DESIGN.md section 16)."""}
+# es_gradient_kernel with its fixed-order sum es_gradient_sum_kernel (DESIGN.md section 16).""", "rollout_ac": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_ac.hip: the actor-critic collection
+# rollout_ac_kernel<TASK, MODE> (both networks' weights read by scalar loads; no LDS) and the advantages gae_kernel
+# (DESIGN.md section 17)."""}
 
 
 def main(path, which="rollout_mlp"):
