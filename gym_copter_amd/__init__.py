@@ -5,8 +5,8 @@ and the Gymnasium-style vector-env host class.  See DESIGN.md and INTEGRATION.md
 """
 from ._lib import CopterStepError  # noqa: F401
 from .vecenv import CopterVecEnv, LqrGains, MlpRollout, MppiCosts, MppiUpdate, Rollout, StepJacobian  # noqa: F401
-from .vecenv import ActorCritic, MppiTemperature, Population, mppi_knots  # noqa: F401
-from .autodiff import differentiable_mlp_rollout, differentiable_rollout  # noqa: F401
+from .vecenv import ActorCritic, MppiTemperature, Population, PpoGrad, mppi_knots  # noqa: F401
+from .autodiff import differentiable_mlp_rollout, differentiable_rollout, ppo_loss  # noqa: F401
 from . import mlp  # noqa: F401
 from .ilqr import ilqr  # noqa: F401
 from .mppi import mppi  # noqa: F401

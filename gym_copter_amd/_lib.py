@@ -180,6 +180,17 @@ class GaeIO(C.Structure):
                 ("advantages_dev", C.c_void_p), ("returns_dev", C.c_void_p)]
 
 
+class PpoGradIO(C.Structure):
+    """Mirror of `struct cs_ppo_grad_io` (cs_ppo_grad)."""
+    _fields_ = [("struct_size", C.c_uint32), ("hidden", C.c_int32), ("critic_hidden", C.c_int32),
+                ("normalize", C.c_uint32), ("num_rows", C.c_int64), ("num_samples", C.c_int64),
+                ("row_base", C.c_int64), ("clip", C.c_double), ("vf_coef", C.c_double), ("ent_coef", C.c_double),
+                ("actor_dev", C.c_void_p), ("critic_dev", C.c_void_p), ("log_std_dev", C.c_void_p),
+                ("obs_dev", C.c_void_p), ("actions_dev", C.c_void_p), ("logp_dev", C.c_void_p),
+                ("advantages_dev", C.c_void_p), ("returns_dev", C.c_void_p), ("live_dev", C.c_void_p),
+                ("index_dev", C.c_void_p), ("grad_dev", C.c_void_p), ("stats_dev", C.c_void_p)]
+
+
 ES_PAIR_CHUNK, ES_MAX_MEMBERS, ES_MAX_PARAMS = 32, 65536, 1092   # CS_ES_PAIR_CHUNK, CS_ES_MAX_MEMBERS, CS_ES_MAX_PARAMS
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
@@ -263,6 +274,7 @@ SYMBOLS = {
     "cs_es_gradient": (C.c_int, [_P, C.POINTER(EsIO), _P]),
     "cs_rollout_actor_critic": (C.c_int, [_P, C.POINTER(RolloutAcIO), _P]),
     "cs_gae": (C.c_int, [_P, C.POINTER(GaeIO), _P]),
+    "cs_ppo_grad": (C.c_int, [_P, C.POINTER(PpoGradIO), _P]),
     "cs_step_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "cs_clock_probe": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), _P]),
     "cs_device_pci_address": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -7,6 +7,7 @@ from .vecenv import MlpRollout, Rollout, _torch
 
 _FN = None
 _FN_MLP = None
+_FN_PPO = None
 
 
 def _function():
@@ -161,3 +162,47 @@ def differentiable_mlp_rollout(env, params, num_steps, hidden, offsets=None, sta
         raise ValueError("reduce must be 'torch' or 'device', got %r" % (reduce,))
     out = _function_mlp().apply(params, offsets, x0, env, num_steps, hidden, state, bool(action_grad), reduce)
     return MlpRollout(*out)
+
+
+def _function_ppo():
+    global _FN_PPO
+    if _FN_PPO is not None:
+        return _FN_PPO
+    torch = _torch()
+    from torch.autograd.function import once_differentiable
+
+    class PpoLossFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, actor, critic, log_std, env, hidden, critic_hidden, tapes, kw):
+            g = env.ppo_grad(actor, critic, log_std, hidden, critic_hidden, *tapes, **kw)
+            stats = g.stats
+            ctx.mark_non_differentiable(stats)
+            ctx.sizes = (actor.shape[0], 0 if critic is None else critic.shape[0])
+            ctx.dtypes = (actor.dtype, None if critic is None else critic.dtype, log_std.dtype)
+            ctx.save_for_backward(g.grad)
+            return stats[4].clone(), stats
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g_loss, _g_stats):
+            grad, = ctx.saved_tensors
+            P, Pv = ctx.sizes
+            g = g_loss * grad
+            return (g[:P].to(ctx.dtypes[0]), g[P:P + Pv].to(ctx.dtypes[1]) if ctx.dtypes[1] is not None else None,
+                    g[P + Pv:].to(ctx.dtypes[2]), None, None, None, None, None)
+
+    _FN_PPO = PpoLossFunction
+    return _FN_PPO
+
+
+def ppo_loss(env, actor, critic, log_std, hidden, critic_hidden, obs, actions, logp, advantages, returns, **kw):
+    """PPO's clipped-surrogate minibatch loss L as a differentiable float64 scalar, for a caller with an optimizer of
+    their own: one CopterVecEnv.ppo_grad call (its arguments and keywords: live, index, row_base, num_samples, clip,
+    vf_coef, ent_coef, normalize) makes the loss and its gradient together, and the backward hands grad_output x
+    gradient to `actor`, `critic` (None: no value term) and `log_std` in their dtype.  Returns (L, stats [8] float64 --
+    vecenv.PPO_STATS, without gradient).  Once differentiable: a double backward raises.  The tapes carry no gradient."""
+    for name in ("out", "stats_out"):
+        if name in kw:
+            raise ValueError("ppo_loss makes its own outputs: %s is not accepted" % name)
+    return _function_ppo().apply(actor, critic, log_std, env, hidden, critic_hidden,
+                                 (obs, actions, logp, advantages, returns), kw)

@@ -32,6 +32,7 @@ struct cs_ctx {
   double* veh_gcoef = nullptr;  // ... and the coefficient adjoints [11][N]
   double* mlp_partials = nullptr;  // scratch of cs_mlp_param_grad: its workgroups' partial sums
   double* es_partials = nullptr;   // scratch of cs_es_gradient: its chunks' partial sums
+  double* ppo_partials = nullptr;  // scratch of cs_ppo_grad: its workgroups' partial sums
   cs::Tuning tune{};
   // the per-launch constants, derived from cfg once and again after cs_seed / cs_set_altitude
   cs::DevConst dc;
@@ -377,6 +378,18 @@ int es_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, do
   return CS_OK;
 }
 
+int ppo_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out) {
+  if (ctx->ppo_partials == nullptr) {
+    if (capturing((hipStream_t)stream))
+      return fail(CS_ERR_ARG, std::string(who) + ": the first call on a context allocates its scratch: make it outside "
+                                                 "graph capture");
+    DeviceGuard guard(ctx->cfg.device);
+    CS_HIP(hipMalloc((void**)&ctx->ppo_partials, bytes));
+  }
+  *out = ctx->ppo_partials;
+  return CS_OK;
+}
+
 int enter_context(cs_ctx* ctx, const char* who, void* stream, ContextView* out) {
   if (int rc_ = check_idle(ctx, who, stream, true)) return rc_;
   out->task = ctx->cfg.task;
@@ -576,6 +589,7 @@ int cs_destroy(cs_ctx* ctx) {
   if (ctx->veh_gcoef) (void)hipFree(ctx->veh_gcoef);
   if (ctx->mlp_partials) (void)hipFree(ctx->mlp_partials);
   if (ctx->es_partials) (void)hipFree(ctx->es_partials);
+  if (ctx->ppo_partials) (void)hipFree(ctx->ppo_partials);
   if (ctx->serve_fork) (void)hipEventDestroy(ctx->serve_fork);
   if (ctx->serve_join) (void)hipEventDestroy(ctx->serve_join);
   if (ctx->serve_mem) (void)hipFree(ctx->serve_mem);

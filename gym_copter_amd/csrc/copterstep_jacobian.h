@@ -46,5 +46,8 @@ int mlp_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, d
 // (copterstep_api.hip) the context's scratch of cs_es_gradient (copterstep_rollout_es.hip), a buffer of its own under the
 // same rules; every call asks for the same `bytes` (the largest population's partials)
 int es_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
+// (copterstep_api.hip) the context's scratch of cs_ppo_grad (copterstep_ppo_grad.hip), a buffer of its own under the
+// same rules; every call asks for the same `bytes` (the widest networks' partials)
+int ppo_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
 
 }  // namespace cs

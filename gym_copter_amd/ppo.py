@@ -35,7 +35,7 @@ def gaussian_logp(torch, actions, means, log_std):
 
 
 def ppo(env, actor0, critic0, log_std0, hidden, critic_hidden, K, iterations, epochs=4, minibatches=4, clip=0.2,
-        lr=3e-4, gamma=0.99, lam=0.95, vf_coef=0.5, ent_coef=0.0, seed=0):
+        lr=3e-4, gamma=0.99, lam=0.95, vf_coef=0.5, ent_coef=0.0, seed=0, update="torch"):
     """Proximal policy optimisation of the Gaussian MLP policy (actor0 [P], log_std0 [A]) and the MLP value function
     (critic0 [Pv]; gym_copter_amd.mlp's layout for `hidden` / `critic_hidden`, the critic with act_dim = 1) on `env`,
     which keeps stepping under its own auto-reset mode from wherever it stands.  Iteration t:
@@ -52,10 +52,17 @@ def ppo(env, actor0, critic0, log_std0, hidden, critic_hidden, K, iterations, ep
     from the stored actions, so r = 1 up to float32 rounding in the first minibatch of every iteration (recorded in
     stats).  `seed` seeds the minibatch permutations.  No host read happens inside the loop.
 
+    update="torch" (the default) is the above; update="device" makes every minibatch's loss and gradient with one
+    library call instead (env.ppo_grad, DESIGN.md section 18: the same function in float64, reduced on the device in a
+    fixed order), copies the gradient into the three leaves' .grad as float32 and takes the same Adam step.  The
+    permutations, the optimizer and the statistics columns are the same; the two paths differ by rounding.
+
     Returns PpoResult(actor [P], critic [Pv], log_std [A] float32 after the last update, history [iterations] float32:
     the mean reward per live step of every iteration's collection, stats [iterations, 6] float32: the columns
     STATS of this module)."""
     torch = _torch()
+    if update not in ("torch", "device"):
+        raise ValueError("update must be 'torch' or 'device', got %r" % (update,))
     dev = env.device
     for v, name in ((iterations, "iterations"), (epochs, "epochs")):
         if not isinstance(v, int) or isinstance(v, bool) or v < 0:
@@ -82,6 +89,12 @@ def ppo(env, actor0, critic0, log_std0, hidden, critic_hidden, K, iterations, ep
     gen.manual_seed(int(seed))
     one = torch.ones((), dtype=torch.float32, device=dev)
     rows = []
+    P, Pv = actor.shape[0], critic.shape[0]
+    if update == "device":
+        grad64 = torch.empty(P + Pv + A, dtype=torch.float64, device=dev)
+        grad32 = torch.zeros(P + Pv + A, dtype=torch.float32, device=dev)
+        actor.grad, critic.grad, log_std.grad = grad32[:P], grad32[P:P + Pv], grad32[P + Pv:]
+        mb_stats = torch.empty(8, dtype=torch.float64, device=dev)
     for t in range(iterations):
         with torch.no_grad():
             roll = env.rollout_actor_critic(actor, critic, log_std, K, hidden, critic_hidden, nonce=t)
@@ -98,6 +111,17 @@ def ppo(env, actor0, critic0, log_std0, hidden, critic_hidden, K, iterations, ep
             perm = torch.randperm(B, device=dev, generator=gen)
             for mb in range(minibatches):
                 idx = perm[mb * B // minibatches:(mb + 1) * B // minibatches]
+                if update == "device":
+                    with torch.no_grad():
+                        env.ppo_grad(actor, critic, log_std, hidden, critic_hidden, obs, act, logp_old, adv, ret,
+                                     live=roll.live.reshape(B), index=idx, clip=clip, vf_coef=vf_coef,
+                                     ent_coef=ent_coef, out=grad64, stats_out=mb_stats)
+                        grad32.copy_(grad64)
+                        if ep == 0 and mb == 0:
+                            first_err = mb_stats[7].to(torch.float32)
+                        pol_loss, val_loss = mb_stats[1].to(torch.float32), mb_stats[2].to(torch.float32)
+                    opt.step()
+                    continue
                 w = live[idx]
                 wsum = torch.maximum(w.sum(), one)
                 a_mb = adv[idx]

@@ -106,6 +106,10 @@ MppiTemperature = collections.namedtuple("MppiTemperature", "lam ess")
 Population = collections.namedtuple("Population", "returns lengths end_flags end_status member_returns")
 # CopterVecEnv.rollout_actor_critic's result
 ActorCritic = collections.namedtuple("ActorCritic", "obs actions means logp values reward terminated truncated live")
+# ppo_grad: grad [P + Pv + A] float64 (actor | critic | log_std), stats [8] float64 (PPO_STATS)
+PpoGrad = collections.namedtuple("PpoGrad", "grad stats")
+PPO_STATS = ("live_samples", "policy_loss", "value_loss", "entropy", "loss", "approx_kl", "clip_fraction",
+             "max_ratio_error")
 MPPI_MAX_KNOT = 16384                                        # knot + 1 <= 16 384: the noise keys stay distinct
 
 
@@ -1956,6 +1960,114 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_gae(self._ctx, C.byref(gio), self._stream()))
         self._keep = [reward, values] + flags
         return out
+
+    def ppo_grad(self, actor, critic, log_std, hidden, critic_hidden, obs, actions, logp, advantages, returns, live=None,
+                 index=None, row_base=0, num_samples=None, clip=0.2, vf_coef=0.5, ent_coef=0.0, normalize=True, out=None,
+                 stats_out=None):
+        """PPO's clipped-surrogate minibatch loss and its gradient, ON THE DEVICE (cs_ppo_grad): what
+        the minibatch step of gym_copter_amd.ppo differentiates, evaluated in float64 from the float32 tapes,
+
+            L = -mean_w min(r A, clip(r, 1 - clip, 1 + clip) A) + vf_coef mean_w (V - ret)^2 / 2 - ent_coef H
+
+        over the minibatch's live samples (w = live), r = exp(logp_new - logp), A the advantages normalised over the
+        minibatch's live samples (normalize=True), H the Gaussian's entropy.  actor [P], critic [Pv] (None: no value
+        term) and log_std [A] are float32 device tensors in gym_copter_amd.mlp's layout for `hidden` / `critic_hidden`.
+        The tapes are what rollout_actor_critic and gae returned -- obs [K,N,OBS] or the [K+1,N,OBS] tape (its first K
+        rows are used), actions [K,N,A], logp, advantages, returns [K,N] float32, live [K,N] bool or uint8 (None: every
+        row live) -- or the same flattened to R rows: obs [R,OBS], actions [R,A], the others [R].  The minibatch is
+        `index`, a contiguous int64 device tensor of row numbers (a slice of torch.randperm; an entry outside [0, R) is
+        skipped by the kernel, a duplicate counts twice), or, with index=None, the `num_samples` (default: all) rows
+        from `row_base` on.
+
+        Returns PpoGrad(grad [P + Pv + A] float64: dL / d(actor | critic | log_std), stats [8] float64: PPO_STATS of this
+        module -- live samples, policy loss, value loss, entropy, L, the approximate KL, the clipped share, max |r - 1|),
+        written into `out` / `stats_out` or into new tensors.  The sums run in a fixed order: the same inputs give the
+        same bits.  Asynchronous on the current stream; nothing is read by the host."""
+        self._check_open()
+        torch = _torch()
+        dev, A, od = self.device, self.action_dim, self.obs_dim
+        P = _mlp.num_params(od, A, hidden)                                # (checks hidden)
+        Pv = _mlp.num_params(od, 1, critic_hidden) if critic is not None else 0
+        if critic is None:
+            critic_hidden = 0 if critic_hidden is None else critic_hidden
+            _mlp.num_params(od, 1, critic_hidden)
+
+        def vec(t, size, name):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (size,) \
+                    or t.device != dev:
+                raise ValueError("%s must be a [%d] float32 tensor on %s, got %s"
+                                 % (name, size, dev, getattr(t, "shape", type(t).__name__)))
+            return t.detach().contiguous()
+        th = vec(actor, P, "actor")
+        tv = vec(critic, Pv, "critic") if critic is not None else None
+        ls = vec(log_std, A, "log_std")
+        if not isinstance(actions, torch.Tensor) or actions.dim() not in (2, 3):
+            raise ValueError("actions must be the [K,N,%d] action tape of rollout_actor_critic or its rows [R,%d]"
+                             % (A, A))
+        lead = tuple(actions.shape[:-1])
+        R = int(np.prod(lead))
+        if R < 1:
+            raise ValueError("the tapes hold no rows")
+        if not isinstance(obs, torch.Tensor):
+            raise ValueError("obs must be the obs tape of rollout_actor_critic, a device tensor")
+        if len(lead) == 2 and tuple(obs.shape) == (lead[0] + 1, lead[1], od):
+            obs = obs[:lead[0]]                                           # (the [K+1,N,OBS] tape: a contiguous prefix)
+        tapes = [(obs, "obs", lead + (od,), torch.float32), (actions, "actions", lead + (A,), torch.float32),
+                 (logp, "logp", lead, torch.float32), (advantages, "advantages", lead, torch.float32)]
+        if tv is not None or returns is not None:
+            tapes.append((returns, "returns", lead, torch.float32))
+        self._check_tape("rollout_actor_critic / gae", *tapes)
+        if live is not None:
+            if not isinstance(live, torch.Tensor) or live.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("live must be a bool or uint8 device tensor of shape %s" % (lead,))
+            self._check_tape("rollout_actor_critic", (live, "live", lead, live.dtype))
+            live = live.view(torch.uint8) if live.dtype == torch.bool else live
+        if index is not None:
+            if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.dtype != torch.int64 \
+                    or index.device != dev or not index.is_contiguous() or index.shape[0] < 1:
+                raise ValueError("index must be a contiguous 1-D int64 tensor on %s with at least one entry" % (dev,))
+            if num_samples is not None and int(num_samples) != int(index.shape[0]):
+                raise ValueError("num_samples = %r disagrees with index [%d]" % (num_samples, index.shape[0]))
+            B, base = int(index.shape[0]), 0
+        else:
+            if not isinstance(row_base, (int, np.integer)) or isinstance(row_base, bool):
+                raise ValueError("row_base must be an int, got %r" % (row_base,))
+            base = int(row_base)
+            B = R - base if num_samples is None else num_samples
+            if not isinstance(B, (int, np.integer)) or isinstance(B, bool) or B < 1 or base < 0 or base + B > R:
+                raise ValueError("rows row_base .. row_base + num_samples - 1 must lie in [0, %d), got row_base %r, "
+                                 "num_samples %r" % (R, row_base, num_samples))
+            B = int(B)
+        cl, vf, en = float(clip), float(vf_coef), float(ent_coef)
+        if not np.isfinite(cl) or not cl > 0.0:
+            raise ValueError("clip must be finite and > 0, got %r" % (clip,))
+        if not np.isfinite(vf) or not np.isfinite(en):
+            raise ValueError("vf_coef and ent_coef must be finite, got %r and %r" % (vf_coef, ent_coef))
+        if out is None:
+            out = torch.empty(P + Pv + A, dtype=torch.float64, device=dev)
+        else:
+            self._check_tape("ppo_grad", (out, "out", (P + Pv + A,), torch.float64))
+        if stats_out is None:
+            stats_out = torch.empty(8, dtype=torch.float64, device=dev)
+        else:
+            self._check_tape("ppo_grad", (stats_out, "stats_out", (8,), torch.float64))
+        pio = _lib.PpoGradIO()
+        pio.struct_size = C.sizeof(_lib.PpoGradIO)
+        pio.hidden, pio.critic_hidden, pio.normalize = hidden, critic_hidden, 1 if normalize else 0
+        pio.num_rows, pio.num_samples, pio.row_base = R, B, base
+        pio.clip, pio.vf_coef, pio.ent_coef = cl, vf, en
+        pio.actor_dev, pio.log_std_dev = th.data_ptr(), ls.data_ptr()
+        pio.critic_dev = tv.data_ptr() if tv is not None else None
+        pio.obs_dev, pio.actions_dev, pio.logp_dev = obs.data_ptr(), actions.data_ptr(), logp.data_ptr()
+        pio.advantages_dev = advantages.data_ptr()
+        pio.returns_dev = returns.data_ptr() if returns is not None else None
+        pio.live_dev = live.data_ptr() if live is not None else None
+        pio.index_dev = index.data_ptr() if index is not None else None
+        pio.grad_dev, pio.stats_dev = out.data_ptr(), stats_out.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_ppo_grad(self._ctx, C.byref(pio), self._stream()))
+        self._keep = [th, tv, ls, obs, actions, logp, advantages, returns, live, index]
+        return PpoGrad(out, stats_out)
 
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""

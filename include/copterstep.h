@@ -1101,6 +1101,66 @@ typedef struct cs_gae_io {
 } cs_gae_io;
 int cs_gae(cs_ctx* ctx, const cs_gae_io* gio, void* stream);
 
+/* The clipped-surrogate minibatch loss of PPO and its gradient over the tapes above: what
+ * gym_copter_amd.ppo's minibatch step differentiates, evaluated in float64 from the float32 tapes and parameters.
+ *
+ * R = num_rows rows, row-major ([K,N] flattened, or any other row set): obs_dev [R,OBS], actions_dev [R,A], logp_dev [R],
+ * advantages_dev [R], returns_dev [R] float32, live_dev [R] uint8 (NULL: every row live).  OBS and A are the context's
+ * task's; the context supplies the shape, the device, the stream rules and the scratch, and no env state is read or
+ * written.  The minibatch is B = num_samples samples: sample s is row index_dev[s] (int64, what a slice of
+ * torch.randperm is), or row row_base + s with index_dev NULL.  A sample whose row is < 0 or >= R is skipped IN THE KERNEL
+ * (weight 0, counted nowhere, nothing read); duplicates count as often as they occur.
+ *
+ * With i the row of sample s, w = live[i] (0 or 1), W = max(sum w, 1), and, with `normalize`, m = sum w adv / W,
+ * sd = sqrt(sum w (adv - m)^2 / W) (the centred form) and Ahat = (adv - m) / (sd + 1e-8), else Ahat = adv:
+ *     mu = pi_actor(o_i), V = pi_critic(o_i)   cs_rollout_mlp_io's layout, the weights widened to double; the hidden
+ *                                 units are fma chains from the bias in index order and the device library's double
+ *                                 tanh, the outputs the bias plus a fixed pairwise tree over the hidden units
+ *                                 (hidden = 0: an fma chain from the bias); nothing contracted
+ *     z_c = (a_c - mu_c) exp(-ls_c),  logp = -1/2 sum_c z_c^2 - sum_c ls_c - (A/2) ln(2 pi), c ascending
+ *     rho = exp(logp - logp_old); a sample is CLIPPED iff (Ahat > 0 and rho > 1 + clip) or (Ahat < 0 and rho < 1 - clip)
+ *     L_pi = -(1/W) sum w Ahat (clipped ? clamp(rho, 1 - clip, 1 + clip) : rho)
+ *     L_V  = (1/2W) sum w (V - ret)^2,   H = sum_c ls_c + A (1 + ln(2 pi)) / 2,   L = L_pi + vf_coef L_V - ent_coef H
+ * grad_dev [P + Pv + A] float64 = dL / d(actor | critic | log_std), written, not accumulated: with dL/dlogp =
+ * -w Ahat rho / W on the samples that are not clipped and 0 on the others, g_mu_c = dL/dlogp z_c exp(-ls_c), g_ls_c =
+ * sum dL/dlogp (z_c^2 - 1) - ent_coef, g_V = vf_coef w (V - ret) / W, and the two networks' parameter gradients follow
+ * from g_mu and g_V as cs_mlp_param_grad forms them from g_actions.  critic_dev NULL: no value term, Pv = 0.
+ * stats_dev [8] float64: sum w, L_pi, L_V, H, L, sum w (logp_old - logp) / W, the clipped share of the live samples,
+ * max over the live samples of |rho - 1| (0 if there are none).
+ *
+ * Every sum runs in an order that depends on (B, the widths, the task) alone -- per-workgroup partials added in index
+ * order, no floating-point atomics --: equal inputs give equal bits, and index_dev = 0..B-1 gives the bits of index_dev
+ * NULL with row_base 0.  clip finite and > 0, vf_coef and ent_coef finite, normalize 0 or 1; obs_dev 16-byte aligned,
+ * index_dev, grad_dev and stats_dev 8-byte, every other float pointer 4-byte; with index_dev NULL, 0 <= row_base and
+ * row_base + B <= R.  pio->struct_size must be sizeof(cs_ppo_grad_io) (else CS_ERR_ABI); the block is checked before
+ * the context and every argument error is raised before any launch.  An open served session is refused.  The first call
+ * on a context allocates its scratch (16.5 MB; not under graph capture).  Asynchronous on `stream`; 64-bit offsets. */
+typedef struct cs_ppo_grad_io {
+  uint32_t struct_size;          /* sizeof(cs_ppo_grad_io) */
+  int32_t hidden;                /* the actor's, 0 .. CS_MLP_MAX_HIDDEN */
+  int32_t critic_hidden;         /* the critic's, 0 .. CS_MLP_MAX_HIDDEN */
+  uint32_t normalize;            /* 0 or 1 */
+  int64_t num_rows;              /* R >= 1 */
+  int64_t num_samples;           /* B >= 1 */
+  int64_t row_base;              /* index_dev NULL: the first row of the minibatch */
+  double clip;
+  double vf_coef;
+  double ent_coef;
+  const float* actor_dev;        /* [P] float32, required */
+  const float* critic_dev;       /* [Pv] float32, or NULL */
+  const float* log_std_dev;      /* [A] float32, required */
+  const float* obs_dev;          /* [R,OBS], required */
+  const float* actions_dev;      /* [R,A], required */
+  const float* logp_dev;         /* [R], required */
+  const float* advantages_dev;   /* [R], required */
+  const float* returns_dev;      /* [R], required with critic_dev */
+  const uint8_t* live_dev;       /* [R], or NULL */
+  const int64_t* index_dev;      /* [B], or NULL */
+  double* grad_dev;              /* [P + Pv + A], required */
+  double* stats_dev;             /* [8], required */
+} cs_ppo_grad_io;
+int cs_ppo_grad(cs_ctx* ctx, const cs_ppo_grad_io* pio, void* stream);
+
 /* Dynamics.getState() / getStatus() / getTime() (dynamics/__init__.py:199-207, :219-225) for the batch, on
  * the DEVICE and asynchronous (enqueue only, graph-capturable): x_dev [12,N] float32 struct-of-arrays in
  * upstream slot order (the full state, incl. psi / dpsi, which the Lander observation omits),
