@@ -16,7 +16,8 @@ from oracle.refcpu import AIRBORNE
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not have_gpu(), reason="needs a HIP device")]
 
-TASK_SHAPE = {"lander3d": (10, 4), "hover3d": (12, 4), "lander2d": (6, 2), "hover1d": (2, 1)}
+TASK_SHAPE = {"lander3d": (10, 4), "hover3d": (12, 4), "lander2d": (6, 2), "hover1d": (2, 1), "lander1d": (2, 1),
+              "hover2d": (6, 2)}
 AH = hover_action()
 U32 = 2.0 ** -24
 
