@@ -1977,7 +1977,12 @@ class CopterVecEnv(_VectorEnvBase):
         row live) -- or the same flattened to R rows: obs [R,OBS], actions [R,A], the others [R].  The minibatch is
         `index`, a contiguous int64 device tensor of row numbers (a slice of torch.randperm; an entry outside [0, R) is
         skipped by the kernel, a duplicate counts twice), or, with index=None, the `num_samples` (default: all) rows
-        from `row_base` on.
+        from `row_base` on.  A row is live iff its `live` byte is nonzero: a uint8 tape holding 2 or 255 gives the bits
+        of one holding 1; a dead row, a row the index does not name and an out-of-range sample are never read.  The
+        tapes may be contiguous views that start inside larger buffers (`buf[k:]`), with one condition the library
+        checks: obs must start on a 16-byte boundary.  Every row of a [R,12] tape does; of a [R,10], [R,6] or [R,2] tape
+        only every second row does, and a view from another row is refused with a CopterStepError that names
+        the alignment, before any launch.
 
         Returns PpoGrad(grad [P + Pv + A] float64: dL / d(actor | critic | log_std), stats [8] float64: PPO_STATS of this
         module -- live samples, policy loss, value loss, entropy, L, the approximate KL, the clipped share, max |r - 1|),

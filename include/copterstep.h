@@ -1111,7 +1111,8 @@ int cs_gae(cs_ctx* ctx, const cs_gae_io* gio, void* stream);
  * torch.randperm is), or row row_base + s with index_dev NULL.  A sample whose row is < 0 or >= R is skipped IN THE KERNEL
  * (weight 0, counted nowhere, nothing read); duplicates count as often as they occur.
  *
- * With i the row of sample s, w = live[i] (0 or 1), W = max(sum w, 1), and, with `normalize`, m = sum w adv / W,
+ * With i the row of sample s, w = (live[i] != 0) (any nonzero byte is live; a dead row, like a row the minibatch does not
+ * name, is never read), W = max(sum w, 1), and, with `normalize`, m = sum w adv / W,
  * sd = sqrt(sum w (adv - m)^2 / W) (the centred form) and Ahat = (adv - m) / (sd + 1e-8), else Ahat = adv:
  *     mu = pi_actor(o_i), V = pi_critic(o_i)   cs_rollout_mlp_io's layout, the weights widened to double; the hidden
  *                                 units are fma chains from the bias in index order and the device library's double
@@ -1154,7 +1155,7 @@ typedef struct cs_ppo_grad_io {
   const float* logp_dev;         /* [R], required */
   const float* advantages_dev;   /* [R], required */
   const float* returns_dev;      /* [R], required with critic_dev */
-  const uint8_t* live_dev;       /* [R], or NULL */
+  const uint8_t* live_dev;       /* [R], or NULL; a row is live iff its byte is nonzero (2 or 255 count as 1) */
   const int64_t* index_dev;      /* [B], or NULL */
   double* grad_dev;              /* [P + Pv + A], required */
   double* stats_dev;             /* [8], required */

@@ -15,7 +15,8 @@ import numpy as np
 
 import ppo_ref
 
-TASK_SHAPE = {"lander3d": (10, 4), "hover3d": (12, 4), "lander2d": (6, 2), "hover1d": (2, 1)}
+TASK_SHAPE = {"lander3d": (10, 4), "hover3d": (12, 4), "lander2d": (6, 2), "hover1d": (2, 1), "lander1d": (2, 1),
+              "hover2d": (6, 2)}
 U64 = 2.0 ** -53
 LN_2PI = math.log(2.0 * math.pi)
 STATS = ("live_samples", "policy_loss", "value_loss", "entropy", "loss", "approx_kl", "clip_fraction",
@@ -38,6 +39,65 @@ CASES = [("lander3d", 16, 16, 4096, 1000, 1, {}), ("lander3d", 0, 0, 4096, 1000,
 # that covers reference()'s budget, c_needed, over the cases above -- 54.3 at the smallest minibatch (B = 37, where 2 B +
 # 64 = 138 is least against the per-term errors, which do not shrink with B), 3.0 to 9.4 at B >= 200.
 BAR_C = 64.0
+
+
+def width_class(H):
+    """The kernel's HP of a hidden width (head_launch in copterstep_ppo_grad.hip): 0 = linear, else H rounded up to
+    8, 16, 32 or 64 lanes per row."""
+    return 0 if H == 0 else 8 if H <= 8 else 16 if H <= 16 else 32 if H <= 32 else 64
+
+
+# The instantiation matrix of tests/test_gpu_ppo_grad_matrix.py: task, H, Hv, R, B, seed.  cs_ppo_grad is one template
+# <OBS, A, HP, head> with 4 shapes x 5 width classes x {policy, value} = 40 instantiations; five width pairs per shape
+# reach every (shape, class, head), and over the matrix each class runs at its full width (no idle lanes) and at a
+# ragged one, for both heads (tests/test_ppo_grad_cpu.py asserts both from this list).  lander1d and hover2d share
+# hover1d's and lander2d's kernels and run once each, by name.  R = 512, B = 300: four full tiles and a ragged one of 44.
+# The seeds are the first for which check_conditions() holds and the bar's constant covers the budget (clip 0.2, vf_coef
+# 0.5, ent_coef 0.01), found on the CPU.
+MATRIX_R, MATRIX_B = 512, 300
+_LANDER_PAIRS = [(0, 24), (5, 64), (16, 0), (32, 8), (40, 12)]
+_HOVER_PAIRS = [(0, 32), (8, 33), (9, 0), (17, 5), (64, 16)]
+_MATRIX_SEEDS = {("lander2d", 0, 24): 2}
+MATRIX = [(task, H, Hv, MATRIX_R, MATRIX_B, _MATRIX_SEEDS.get((task, H, Hv), 1))
+          for task, pairs in (("lander3d", _LANDER_PAIRS), ("lander2d", _LANDER_PAIRS), ("hover3d", _HOVER_PAIRS),
+                              ("hover1d", _HOVER_PAIRS), ("lander1d", [(17, 5)]), ("hover2d", [(17, 5)]))
+          for H, Hv in pairs]
+
+# Two minibatches of 200 000 samples: 3 125 tiles, 4 per workgroup on 782 workgroups, so that all four wavefronts of a
+# workgroup take a tile and the last workgroup holds one tile only.  task, H, Hv, R, B, seed (found as above).
+LARGE = [("hover1d", 12, 33, 210000, 200000, 1), ("lander3d", 40, 12, 210000, 200000, 1)]
+
+
+# Degenerate minibatches (tests/test_gpu_ppo_grad_matrix.py), R = 512: task, H, Hv, seed.
+#   ONE_LIVE: 65 samples of which one is live (one_live()).  With normalize the normalised advantage is exactly 0; without,
+#     the case is compared with the reference, and the seed is the first whose reference has c_needed, c_stats <= BAR_C
+#     (one live row cannot meet check_conditions(): its clipped share is 0 or 1).
+#   EQUAL_ADV: 256 samples, every advantage 0.5 (equal_advantages()).  With normalize m = 0.5 and Ahat = 0 exactly; without,
+#     an ordinary case: the first seed that meets check_conditions() and the bar's constant.
+#   RANGE_LIVE: rows 100 .. 399 as a row range WITH the live mask: the first seed as for EQUAL_ADV.
+DEGENERATE_R = 512
+ONE_LIVE = [("lander3d", 16, 16, 1), ("hover1d", 5, 0, 1)]
+EQUAL_ADV = [("lander3d", 16, 16, 1), ("hover1d", 5, 0, 1), ("hover3d", 0, 33, 1)]
+RANGE_LIVE = ("lander3d", 16, 16, 1)
+RANGE_BASE, RANGE_B = 100, 300
+
+
+def one_live(task, H, Hv, seed, B=65, at=37):
+    """synthetic() with every row dead but the one sample `at` of the minibatch perm[:B].  Returns (tapes, index)."""
+    import torch
+    s = synthetic(task, H, Hv, DEGENERATE_R, seed)
+    idx = s["perm"][:B].contiguous()
+    s["live"] = torch.zeros_like(s["live"])
+    s["live"][idx[at]] = True
+    return s, idx
+
+
+def equal_advantages(task, H, Hv, seed, B=256):
+    """synthetic() with every advantage 0.5 (sums of 0.5 are exact in any order).  Returns (tapes, index = perm[:B])."""
+    import torch
+    s = synthetic(task, H, Hv, DEGENERATE_R, seed)
+    s["advantages"] = torch.full_like(s["advantages"], 0.5)
+    return s, s["perm"][:B].contiguous()
 
 
 def check_conditions(ref, need_dead=True):

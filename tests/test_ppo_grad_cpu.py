@@ -1,7 +1,8 @@
 """CPU-side checks of cs_ppo_grad: the entry point declared, exported and bound, the ctypes struct
 mirroring the header; bad argument blocks refused without touching a device; ppo() refusing an unknown `update` before
 it touches its env; and the reference of tests/ppo_update_ref.py: its autograd gradient against central differences of
-its own loss and the conditions of the GPU cases (self-checks that need no library: they pass without the feature)."""
+its own loss and the conditions of the GPU cases (self-checks that need no library: they pass without the feature); and
+that the instantiation matrix of tests/test_gpu_ppo_grad_matrix.py reaches all 40 instantiations of the kernel's template."""
 import ctypes as C
 import os
 import re
@@ -167,3 +168,69 @@ def test_the_gpu_cases_meet_their_conditions_on_the_reference():
             ppo_update_ref.check_conditions(ref, need_dead=not rng)
             assert ref["c_needed"] <= ppo_update_ref.BAR_C and ref["c_stats"] <= ppo_update_ref.BAR_C
             assert ppo_update_ref.float32_distance(s, idx, ref["grad"], **kw) > 1e-8
+
+
+def test_the_matrix_reaches_every_instantiation_full_and_ragged():
+    """ppo_update_ref.MATRIX against the kernel's dispatch, restated: the (OBS, A) shape of the task, HP =
+    width_class(hidden), the head.  All 4 x 5 x 2 = 40 instantiations of <OBS, A, HP, head> occur; over the matrix every
+    class H > 0 runs at its full width (H = HP: no idle lanes) and at a ragged one, for both heads; lander1d and hover2d,
+    which share two of the shapes, occur by name; and B leaves a ragged last tile after more than one full one.  A later
+    edit of the list cannot lose coverage silently."""
+    pur = ppo_update_ref
+    assert [pur.width_class(H) for H in (0, 1, 8, 9, 16, 17, 32, 33, 64)] == [0, 8, 8, 16, 16, 32, 32, 64, 64]
+    shapes = {pur.TASK_SHAPE[t] for t in ("lander3d", "hover3d", "lander2d", "hover1d")}
+    assert len(shapes) == 4 and pur.TASK_SHAPE["lander1d"] == pur.TASK_SHAPE["hover1d"]
+    assert pur.TASK_SHAPE["hover2d"] == pur.TASK_SHAPE["lander2d"]
+    from gym_copter_amd import vecenv
+    for task, shape in pur.TASK_SHAPE.items():
+        assert vecenv._TASK_SHAPES[task][1:] == shape, task
+    triples, widths = set(), {"policy": set(), "value": set()}
+    for task, H, Hv, R, B, seed in pur.MATRIX:
+        assert (R, B) == (512, 300) and B // 64 > 1 and B % 64 != 0
+        triples.add((pur.TASK_SHAPE[task], pur.width_class(H), "policy"))
+        triples.add((pur.TASK_SHAPE[task], pur.width_class(Hv), "value"))
+        widths["policy"].add(H)
+        widths["value"].add(Hv)
+    assert triples == {(shape, hp, head) for shape in shapes for hp in (0, 8, 16, 32, 64) for head in ("policy", "value")}
+    assert len(triples) == 40
+    for head, seen in widths.items():
+        for hp in (8, 16, 32, 64):
+            assert hp in seen, (head, hp)                                             # full
+            assert any(pur.width_class(H) == hp and H != hp for H in seen), (head, hp)    # ragged
+    assert {"lander1d", "hover2d"} <= {case[0] for case in pur.MATRIX}
+    assert len(set(pur.MATRIX)) == len(pur.MATRIX) == 22
+
+
+def test_the_matrix_and_degenerate_cases_meet_their_conditions_on_the_reference():
+    """The conditions of the cases of tests/test_gpu_ppo_grad_matrix.py that are small enough to check here (the two of
+    200 000 samples are checked where they run), on the reference alone: check_conditions() and the bar's constant over
+    MATRIX, the equal-advantage cases without normalisation and the row range with a live mask; the bar's constant over
+    the one-live-sample cases.  With normalisation the two degenerate set-ups have a deviation of exactly 0 in float64
+    too.  A self-check of the test inputs that passes without the feature."""
+    import torch
+    pur = ppo_update_ref
+    kw = dict(clip=0.2, vf_coef=0.5, ent_coef=0.01)
+
+    def holds(ref, conditions=True):
+        if conditions:
+            pur.check_conditions(ref)
+        assert ref["c_needed"] <= pur.BAR_C and ref["c_stats"] <= pur.BAR_C, (ref["c_needed"], ref["c_stats"])
+    for task, H, Hv, R, B, seed in pur.MATRIX:
+        s = pur.synthetic(task, H, Hv, R, seed)
+        holds(pur.reference(s, s["perm"][:B], **kw))
+    for task, H, Hv, seed in pur.ONE_LIVE:
+        s, idx = pur.one_live(task, H, Hv, seed)
+        assert idx.shape[0] == 65 and int(s["live"][idx].sum()) == 1 == int(s["live"].sum())
+        holds(pur.reference(s, idx, normalize=False, **kw), conditions=False)
+    for task, H, Hv, seed in pur.EQUAL_ADV:
+        s, idx = pur.equal_advantages(task, H, Hv, seed)
+        ref = pur.reference(s, idx, normalize=False, **kw)
+        holds(ref)
+        w, a = s["live"][idx].double(), s["advantages"][idx].double()
+        assert 1 < ref["count"] < idx.shape[0] == 256 and float((a * w).sum() / w.sum()) == 0.5
+    task, H, Hv, seed = pur.RANGE_LIVE
+    s = pur.synthetic(task, H, Hv, pur.DEGENERATE_R, seed)
+    holds(pur.reference(s, torch.arange(pur.RANGE_BASE, pur.RANGE_BASE + pur.RANGE_B), **kw))
+    for task, H, Hv, R, B, seed in pur.LARGE:
+        tiles = -(-B // 64)
+        assert -(-tiles // 1024) == 4 and tiles % 4 != 0 and B <= R
