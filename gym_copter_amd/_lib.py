@@ -127,6 +127,15 @@ class RolloutFeedbackIO(C.Structure):
                 ("actions_out_dev", C.c_void_p)]
 
 
+class RolloutEkfIO(C.Structure):
+    """Mirror of `struct cs_rollout_ekf_io` (cs_rollout_ekf)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_meas", C.c_int32),
+                ("reserved_", C.c_uint32), ("H_dev", C.c_void_p), ("r_dev", C.c_void_p), ("Q_dev", C.c_void_p),
+                ("P0_dev", C.c_void_p), ("z_dev", C.c_void_p), ("x_pred_dev", C.c_void_p), ("P_dev", C.c_void_p),
+                ("P_tape_dev", C.c_void_p), ("var_dev", C.c_void_p), ("nis_dev", C.c_void_p),
+                ("loglik_dev", C.c_void_p), ("branch_dev", C.c_void_p), ("ok_dev", C.c_void_p)]
+
+
 class RolloutMppiIO(C.Structure):
     """Mirror of `struct cs_rollout_mppi_io` (cs_rollout_mppi_costs / cs_rollout_mppi_update)."""
     _fields_ = [("struct_size", C.c_uint32), ("num_samples", C.c_int32), ("noise_stream", C.c_uint32),
@@ -192,6 +201,7 @@ class PpoGradIO(C.Structure):
 
 
 ES_PAIR_CHUNK, ES_MAX_MEMBERS, ES_MAX_PARAMS = 32, 65536, 1092   # CS_ES_PAIR_CHUNK, CS_ES_MAX_MEMBERS, CS_ES_MAX_PARAMS
+EKF_MAX_MEAS = 12                                            # CS_EKF_MAX_MEAS
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
@@ -262,6 +272,7 @@ SYMBOLS = {
     "cs_mlp_param_grad": (C.c_int, [_P, C.POINTER(MlpGradIO), _P]),
     "cs_rollout_lqr": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqrIO), _P]),
     "cs_rollout_feedback_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO), _P]),
+    "cs_rollout_ekf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutEkfIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),

@@ -1,0 +1,67 @@
+"""A small streaming driver on CopterVecEnv.rollout_ekf: an extended Kalman filter per env whose
+measurements arrive a chunk of steps at a time, and the synthetic measurements to try it on.
+
+    z = H x + e,  e ~ N(0, diag(r));     x- = step(xhat, a),  P- = A P A^T + Q;     sequential scalar updates
+
+The filter's state (mean, covariance, flight status) is carried from call to call on the device; nothing is read by the
+host."""
+from .vecenv import EkfResult
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def measure(x_tape, H, r, seed, missing=0.0):
+    """Synthetic measurements of a rollout_states tape: z [K,N,M] float64 = H x + sqrt(r) N(0, 1) on x_tape's device, from
+    a torch generator seeded with `seed` on that device; where a Bernoulli(missing) draw says so the entry is NaN ("no
+    measurement", which rollout_ekf skips).  x_tape [K,N,12]; H [M,12]; r [M] > 0 the variances."""
+    torch = _torch()
+    if not isinstance(x_tape, torch.Tensor) or x_tape.dim() != 3 or x_tape.shape[2] != 12:
+        raise ValueError("x_tape must be a tensor of shape (K, N, 12) (rollout_states' x)")
+    if not 0.0 <= float(missing) <= 1.0:
+        raise ValueError("missing must be a probability, got %r" % (missing,))
+    dev = x_tape.device
+    Hd = torch.as_tensor(H, dtype=torch.float64).to(dev)
+    rd = torch.as_tensor(r, dtype=torch.float64).to(dev)
+    if Hd.dim() != 2 or Hd.shape[1] != 12 or tuple(rd.shape) != (Hd.shape[0],):
+        raise ValueError("H must have shape (M, 12) and r shape (M,), got %s and %s" % (tuple(Hd.shape), tuple(rd.shape)))
+    if not bool((rd > 0).all()):
+        raise ValueError("r must be positive: the measurement variances")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    K, n, M = x_tape.shape[0], x_tape.shape[1], Hd.shape[0]
+    noise = torch.randn((K, n, M), generator=gen, dtype=torch.float64, device=dev)
+    z = x_tape.to(torch.float64) @ Hd.T + noise * torch.sqrt(rd)
+    if missing > 0.0:
+        gone = torch.rand((K, n, M), generator=gen, dtype=torch.float64, device=dev) < float(missing)
+        z = torch.where(gone, torch.full_like(z, float("nan")), z)
+    return z
+
+
+def ekf(env, actions, z, H, r, Q, x0, P0, status0=None, chunk=None):
+    """Run env.rollout_ekf over actions [K,N,A] and z [K,N,M] in chunks of `chunk` steps (None: one call), as a filter
+    whose measurements arrive `chunk` at a time: the mean, the covariance and the status after each chunk start the next.
+    Returns EkfResult with the tapes of all K steps concatenated (P_tape included), P the last posterior, loglik the sum
+    of the chunks' and ok their conjunction -- tensors of their own, not the env's buffers.  Every tape, P and ok are
+    bit-identical to the single call's: a chunk boundary rounds nothing (float64 throughout).  loglik equals the single
+    call's to rounding only: it is the sum of the chunks' sums.  The arguments are rollout_ekf's."""
+    torch = _torch()
+    K = int(actions.shape[0])
+    chunk = K if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1, got %r" % (chunk,))
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] != K:
+        raise ValueError("z must be a tensor of shape (K, N, M) with K = %d steps" % K)
+    parts = []
+    x, P, status = x0, P0, status0
+    loglik, ok = None, None
+    for k0 in range(0, K, chunk):
+        res = env.rollout_ekf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, x, P, status0=status, tape=True)
+        parts.append([t.clone() for t in (res.x, res.x_pred, res.var, res.nis, res.status, res.branch, res.P_tape)])
+        x, P, status = res.x[-1].T.contiguous(), res.P.clone(), res.status[-1].clone()
+        loglik = res.loglik.clone() if loglik is None else loglik + res.loglik
+        ok = res.ok.clone() if ok is None else ok & res.ok
+    xs, xp, var, nis, st, br, pt = (torch.cat([p[j] for p in parts]) for j in range(7))
+    return EkfResult(xs, xp, P, var, nis, loglik, st, br, ok, pt)

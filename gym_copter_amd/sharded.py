@@ -216,6 +216,11 @@ class ShardedCopterVecEnv:
         return self.local.rollout_lqr(self._local_rollout_actions(actions), rollout, Q, R, q=q, r=r, Q_final=Q_final,
                                       mu=mu, state=state, dtype=dtype)
 
+    def rollout_ekf(self, actions, z, H, r, Q, x0, P0, status0=None, tape=False, dtype=None):
+        """CopterVecEnv.rollout_ekf of this rank's envs: shard-local (z, x0, P0, status0: the local envs')."""
+        return self.local.rollout_ekf(self._local_rollout_actions(actions), z, H, r, Q, x0, P0, status0=status0,
+                                      tape=tape, dtype=dtype)
+
     def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
                            stream=0, state=None, knots=None):
         """CopterVecEnv.rollout_mppi_costs of this rank's envs: shard-local (x_ref, state: the local envs').  The noise

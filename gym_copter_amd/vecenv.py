@@ -97,6 +97,10 @@ MlpRollout = collections.namedtuple("MlpRollout", "x reward terminated truncated
 # CopterVecEnv.rollout_lqr's result: the time-varying gains K [K,N,A,12] and d [K,N,A], the model's predicted cost change
 # dV [N,2], the value model at the start S0 [N,12,12], s0 [12,N], and ok [N] bool (every Cholesky pivot positive)
 LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
+# CopterVecEnv.rollout_ekf's result: the filtered means x [K,N,12] and the priors x_pred [K,N,12], the
+# last posterior covariance P [N,12,12], its diagonal per step var [K,N,12], nis [K,N], loglik [N], the status [K,N] and
+# step_jacobian branch bits [K,N] of the filter's own mean, ok [N] bool, and P_tape [K,N,12,12] (None without tape=True)
+EkfResult = collections.namedtuple("EkfResult", "x x_pred P var nis loglik status branch ok P_tape")
 # CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
 MppiCosts = collections.namedtuple("MppiCosts", "costs best")
 MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
@@ -1485,6 +1489,134 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_rollout_feedback_states(self._ctx, C.byref(io), C.byref(fio), self._stream()))
         self._keep = keep + [xbar, Kg, d]
         return ro, acts
+
+    # -- the extended Kalman filter over the env step --------
+    def _ekf_model(self, H, r, Q):
+        """H [M,12], r [M] and Q [12,12], checked on the host (finite; 1 <= M <= 12; r > 0; Q symmetric) and kept on the
+        device: the same values are uploaded once (a streaming filter passes them with every chunk).  Host arrays are
+        compared by value; device tensors are recognised by identity and version (the same, unmodified tensors as in the
+        last call cost no device-to-host copy), and checked on the host once when they are new."""
+        torch = _torch()
+        tensors = all(isinstance(m, torch.Tensor) for m in (H, r, Q))
+        ident = tuple((id(m), m._version, m.data_ptr()) for m in (H, r, Q)) if tensors else None
+        cache = getattr(self, "_ekf_m", None)
+        if ident is not None and cache is not None and cache[2] == ident:
+            return cache[1]
+
+        def host(m, name):
+            a = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m)
+            if a.dtype.kind not in "fiu":
+                raise ValueError("%s must be a real floating-point array, got dtype %s" % (name, a.dtype))
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if not np.isfinite(a).all():
+                raise ValueError("%s must be finite" % name)
+            return a
+        h = host(H, "H")
+        if h.ndim != 2 or h.shape[1] != 12 or not 1 <= h.shape[0] <= _lib.EKF_MAX_MEAS:
+            raise ValueError("H must have shape (M, 12) with 1 <= M <= %d, got %s" % (_lib.EKF_MAX_MEAS, h.shape))
+        rv = host(r, "r")
+        if rv.shape != (h.shape[0],):
+            raise ValueError("r must have shape (%d,) (one variance per row of H), got %s" % (h.shape[0], rv.shape))
+        if not (rv > 0).all():
+            raise ValueError("r must be positive: the measurement variances")
+        q = host(Q, "Q")
+        if q.shape != (12, 12):
+            raise ValueError("Q must have shape (12, 12), got %s" % (q.shape,))
+        if not np.array_equal(q, q.T):
+            raise ValueError("Q must be symmetric")
+        key = (h.tobytes(), rv.tobytes(), q.tobytes())
+        if cache is None or cache[0] != key:
+            cache = (key, [torch.from_numpy(m).to(self.device) for m in (h, rv, q)])
+        # (the caller's tensors are kept alive with their identity, so that an id cannot be reused by another tensor)
+        cache = self._ekf_m = (cache[0], cache[1], ident, (H, r, Q) if tensors else None)
+        return cache[1]
+
+    def _ekf_input(self, v, shape, name, keep):
+        """A per-env input of rollout_ekf as a contiguous float64 device tensor, kept alive in `keep`: a floating-point
+        tensor on this env's device, or a host array."""
+        torch = _torch()
+        if isinstance(v, torch.Tensor):
+            if tuple(v.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(v.shape)))
+            if not v.dtype.is_floating_point:
+                raise ValueError("%s must be a floating-point tensor, got %s" % (name, v.dtype))
+            if v.device != self.device:
+                raise ValueError("%s must be on %s, got %s" % (name, self.device, v.device))
+            t = v.detach().to(torch.float64).contiguous()
+        else:
+            a = np.asarray(v)
+            if a.shape != shape:
+                raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
+            if a.dtype.kind != "f":
+                raise ValueError("%s must be a floating-point array, got dtype %s" % (name, a.dtype))
+            t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)
+        keep.append(t)
+        return t
+
+    def rollout_ekf(self, actions, z, H, r, Q, x0, P0, status0=None, tape=False, dtype=None):
+        """An extended Kalman filter over the env step, K predict / update steps per env in one kernel: the mean goes
+        through the step's own physics, the covariance through the step Jacobian of step_jacobian (every branch rule of
+        DESIGN section 9), applied on the fly and never stored.  The filter's state is the caller's: NO env state is read
+        but the configuration and the vehicle, and none changes.
+
+        actions [K,N,A]: step k takes actions[k-1].  z [K,N,M] float64: the measurements z = H x + e, e ~ N(0, diag(r));
+        a NaN entry means "no measurement" and its update is skipped.  H [M,12] (1 <= M <= 12), r [M] > 0 and Q [12,12]
+        symmetric PSD (the process noise added per step) are shared by every env and step.  x0 [12,N] float64 and
+        P0 [N,12,12] (symmetric: its upper triangle is read) are the mean and covariance before step 1; status0 [N] uint8
+        the flight status of that mean (default AIRBORNE).
+
+        Per step: x- = the physics from (xhat, status), P- = A P A^T + Q; then for each row i of H in order, skipping NaN
+        z: p = P h, s = h^T p + r_i, nu = z_i - h^T x, x += (p / s) nu, P -= (p / s) p^T.
+
+        Returns EkfResult(x [K,N,12] the filtered means, x_pred [K,N,12] the priors, P [N,12,12] the last posterior, var
+        [K,N,12] the posteriors' diagonals, nis [K,N] the steps' sums of nu^2 / s, loglik [N] the sum of
+        -1/2 (nu^2 / s + ln(2 pi s)), status [K,N] and branch [K,N] (step_jacobian's bits) of the filter's own mean, ok
+        [N] bool (False where some s was not finite or <= 0), P_tape [K,N,12,12] with tape=True, else None).  dtype:
+        torch.float64 (default) or torch.float32 (P, var, nis, loglik, P_tape: the float64 values rounded).  Not available
+        under action_arith="float32".  Asynchronous on the current stream; the tensors are buffers of this env,
+        overwritten by its next call with the same K, dtype and tape."""
+        self._check_open()
+        torch = _torch()
+        dtype = self._out_dtype(dtype)
+        Hd, rd, Qd = self._ekf_model(H, r, Q)
+        M = int(Hd.shape[0])
+        io, K, keep = self._rollout_io(actions, None)
+        n, dev = self.num_envs, self.device
+        zt = self._ekf_input(z, (K, n, M), "z", keep)
+        xt = self._ekf_input(x0, (12, n), "x0", keep)
+        Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
+        if status0 is None:
+            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=dev)
+            keep.append(st)
+            io.start_status_dev = st.data_ptr()
+        else:
+            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
+        io.start_x_dev = xt.data_ptr()
+        eio = _lib.RolloutEkfIO()
+        eio.struct_size = C.sizeof(_lib.RolloutEkfIO)
+        eio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+        eio.num_meas = M
+        eio.H_dev, eio.r_dev, eio.Q_dev = Hd.data_ptr(), rd.data_ptr(), Qd.data_ptr()
+        eio.P0_dev, eio.z_dev = Pt.data_ptr(), zt.data_ptr()
+        tape = bool(tape)
+        out = self._rollout_cache(("ekf", K, dtype, tape), lambda: EkfResult(
+            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
+            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
+            torch.empty((n, 12, 12), dtype=dtype, device=dev), torch.empty((K, n, 12), dtype=dtype, device=dev),
+            torch.empty((K, n), dtype=dtype, device=dev), torch.empty(n, dtype=dtype, device=dev),
+            torch.empty((K, n), dtype=torch.uint8, device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev),
+            torch.empty(n, dtype=torch.bool, device=dev),
+            torch.empty((K, n, 12, 12), dtype=dtype, device=dev) if tape else None))
+        io.x_dev, io.status_dev = out.x.data_ptr(), out.status.data_ptr()
+        eio.x_pred_dev, eio.P_dev, eio.var_dev = out.x_pred.data_ptr(), out.P.data_ptr(), out.var.data_ptr()
+        eio.nis_dev, eio.loglik_dev = out.nis.data_ptr(), out.loglik.data_ptr()
+        eio.branch_dev, eio.ok_dev = out.branch.data_ptr(), out.ok.data_ptr()
+        if tape:
+            eio.P_tape_dev = out.P_tape.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_ekf(self._ctx, C.byref(io), C.byref(eio), self._stream()))
+        self._keep = keep + [Hd, rd, Qd]
+        return out
 
     # -- MPPI: sampled rollouts, their costs and the weighted update (DESIGN section 14) --------
     def _mppi_small(self, v, name, dtype, nonneg):

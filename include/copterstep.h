@@ -37,6 +37,8 @@
  *                            rollout's tape                      counterpart: a second-order trajectory optimiser)
  *   cs_rollout_feedback_states  cs_rollout_states under the     lander.py:40-65 with a time-varying affine feedback
  *                            feedback that pass returns          in place of the random action
+ *   cs_rollout_ekf           an extended Kalman filter over     the rollout lines above and their Jacobian (no upstream
+ *                            the step, K steps per env           counterpart: a state estimator)
  *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
  *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
  *   cs_rollout_mppi_update   their cost-weighted average         (the same)
@@ -821,6 +823,69 @@ typedef struct cs_rollout_feedback_io {
   float* actions_out_dev;      /* [K,N,A] float32, required */
 } cs_rollout_feedback_io;
 int cs_rollout_feedback_states(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_feedback_io* fio, void* stream);
+
+/* An extended Kalman filter over the env step, on the device: K predict / update steps per env
+ * in one call, the step Jacobian applied on the fly and never stored.  The filter's state -- the mean xhat [12] and the
+ * covariance P [12,12] -- is the CALLER's: no env state is read except the context's constants and vehicle table, and
+ * none is written.  The measurement model is linear and shared, z = H x + e with e ~ N(0, diag(r)); the process noise Q
+ * is additive per step.
+ *
+ * From io: num_steps = K, actions_dev [K,N,A], start_x_dev [12,N] = xhat_0 and start_status_dev [N] (both required);
+ * start_force_dev and start_prev_shaping_dev must be NULL (no perturbation is pending: disturbances are what Q models);
+ * x_dev [K,N,12] (or NULL) receives the filtered means and status_dev [K,N] (or NULL) the flight status the filter's own
+ * mean has after step k; the reward, flag, cotangent and gradient pointers must be NULL.
+ *
+ * From eio:
+ *   num_meas  M, 1 .. CS_EKF_MAX_MEAS
+ *   H_dev     [M,12]    float64  shared by all envs and steps
+ *   r_dev     [M]       float64  the measurement variances, each finite and > 0 (the caller's to guarantee;
+ *                                gym_copter_amd checks them)
+ *   Q_dev     [12,12]   float64  symmetric PSD, shared
+ *   P0_dev    [N,12,12] float64  symmetric: its upper triangle is read
+ *   z_dev     [K,N,M]   float64  a NaN entry means "no measurement": that scalar update is skipped
+ * Per step k = 1..K and env, in float64 without contraction:
+ *   predict   x- = the physics of step k from (xhat, status) under actions[k-1], as cs_rollout_states takes it from that
+ *             explicit point (clip, fan-out, the env's vehicle, the thrust law, the gyro term, `substeps` calls, the
+ *             status machine), without storage rounding; termination and auto-reset do not enter.
+ *             P- = A P A^T + Q with A = cs_step_jacobian's dx at that point under every rule of that call (LANDED:
+ *             identity; contact and CRASHED calls hold; LEVELING zeroes the phi, theta rows); CS_JAC_RESET never
+ *             occurs.  The upper triangle is kept; one add per entry applies Q.
+ *   update    for i = 0 .. M-1 in order, skipping NaN z_i:  h = H[i],  p = P h,  s = h^T p + r_i,  nu = z_i - h^T x,
+ *             g = p / s,  x <- x + g nu,  P <- P - g p^T (upper triangle),  nis += nu^2 / s,
+ *             loglik -= 1/2 (nu^2 / s + ln(2 pi s)).  Sequential scalar updates are exact for a diagonal R, and the sum
+ *             of nu^2 / s over a step is its joint normalised innovation squared.  If s is not finite or <= 0 the
+ *             env's ok is 0; every output is written regardless.
+ * Outputs, each may be NULL; P, P_tape, var, nis and loglik in out_dtype (CS_JAC_F64, or CS_JAC_F32: the float64 values
+ * rounded):
+ *   x_pred_dev [K,N,12] float64  the prior means x-          P_dev      [N,12,12]   the posterior after step K (full,
+ *   P_tape_dev [K,N,12,12]       the posterior of every step                          symmetric)
+ *   var_dev    [K,N,12]          the posterior's diagonal    nis_dev    [K,N]       the step's sum of nu^2 / s
+ *   loglik_dev [N]               the call's log-likelihood   branch_dev [K,N] uint8 the CS_JAC_* bits of the step
+ *   ok_dev     [N] uint8
+ * Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32.  Asynchronous on `stream`; eio->struct_size must be
+ * sizeof(cs_rollout_ekf_io) (else CS_ERR_ABI); both blocks are checked before the context.  H, r and Q are read by the
+ * scalar unit: 8-B aligned (as every float64 array here), never written while a call runs. */
+#define CS_EKF_MAX_MEAS 12
+typedef struct cs_rollout_ekf_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_ekf_io) */
+  uint32_t out_dtype;          /* CS_JAC_F64 / CS_JAC_F32: P_dev, P_tape_dev, var_dev, nis_dev, loglik_dev */
+  int32_t num_meas;            /* M, 1 .. CS_EKF_MAX_MEAS */
+  uint32_t reserved_;          /* 0 */
+  const double* H_dev;         /* [M,12], required */
+  const double* r_dev;         /* [M], required */
+  const double* Q_dev;         /* [12,12], required */
+  const double* P0_dev;        /* [N,12,12], required */
+  const double* z_dev;         /* [K,N,M], required */
+  double* x_pred_dev;          /* [K,N,12] */
+  void* P_dev;                 /* [N,12,12] */
+  void* P_tape_dev;            /* [K,N,12,12] */
+  void* var_dev;               /* [K,N,12] */
+  void* nis_dev;               /* [K,N] */
+  void* loglik_dev;            /* [N] */
+  uint8_t* branch_dev;         /* [K,N] */
+  uint8_t* ok_dev;             /* [N] */
+} cs_rollout_ekf_io;
+int cs_rollout_ekf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_ekf_io* eio, void* stream);
 
 /* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
  * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,

@@ -8,7 +8,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_mppi_smooth > profiles/rollout_mppi_smooth_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_es > profiles/rollout_es_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_ac > profiles/rollout_ac_resources.txt
-    python3 tools/resource_table.py remarks.txt ppo_grad > profiles/ppo_grad_resources.txt"""
+    python3 tools/resource_table.py remarks.txt ppo_grad > profiles/ppo_grad_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_ekf > profiles/rollout_ekf_resources.txt"""
 import re
 import sys
 
@@ -60,7 +61,10 @@ HEADS = {"rollout_mlp": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_ppo_grad.hip: PPO's minibatch loss and gradient
 # ppo_grad_kernel<OBS, A, HP, HEAD> (HP = 0: linear, else the hidden width rounded up to 8, 16, 32 or 64 lanes per row;
 # HEAD 0 = the Gaussian policy, 1 = the value function), the two passes over the advantages ppo_adv_kernel<PASS> and
-# ppo_grad_sum_kernel, the sum of the workgroups' partials and the statistics (DESIGN.md section 18)."""}
+# ppo_grad_sum_kernel, the sum of the workgroups' partials and the statistics (DESIGN.md section 18).""", "rollout_ekf": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_ekf.hip: the extended Kalman filter
+# rollout_ekf_kernel<TASK, MODE, GYRO> (the covariance, W = A P and the means in lane-private LDS columns: one wavefront
+# per CU; DESIGN.md section 19)."""}
 
 
 def main(path, which="rollout_mlp"):
