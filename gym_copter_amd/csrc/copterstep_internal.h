@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "copterstep.h"
+#include "trig_reduce.h"
 
 namespace cs {
 
@@ -141,29 +142,9 @@ struct DevConst {
   // (dynamics/__init__.py:120-132 with `motors` a float32 ndarray): every scalar is the float32
   // rounding of the Python value it multiplies or divides
   float f32_maxrpm, f32_pi, f32_B, f32_LB, f32_D, f32_M, f32_Ix, f32_Iy, f32_Iz, f32_pad;
-  // sin/cos constants: [0] 2/pi, [1..3] pi/2 in three pieces (33+33+53 bits, fdlibm
-  // pio2_1, pio2_2, pio2_2t), [4..9] S1..S6, [10..15] C1..C6 (fdlibm k_sin / k_cos),
-  // [16..19] / [20..24] the shorter minimax polynomials of the float32 state modes
-  double trig[25];
+  // sin/cos constants, filled by trig_constants() (trig_reduce.h, which lists them)
+  double trig[kTrigConstants];
 };
-
-inline void trig_constants(double (&t)[25]) {
-  const double v[25] = {6.36619772367581382433e-01,  1.57079632673412561417e+00,
-                        6.07710050630396597660e-11,  2.02226624879595063154e-21,
-                        -1.66666666666666324348e-01, 8.33333333332248946124e-03,
-                        -1.98412698298579493134e-04, 2.75573137070700676789e-06,
-                        -2.50507602534068634195e-08, 1.58969099521155010221e-10,
-                        4.16666666666666019037e-02,  -1.38888888888741095749e-03,
-                        2.48015872894767294178e-05,  -2.75573143513906633035e-07,
-                        2.08757232129817482790e-09,  -1.13596475577881948265e-11,
-                        // sin(y) = y + y^3 * (s0 + s1 z + s2 z^2 + s3 z^3), z = y^2, |y| <= pi/4: 1.4e-11
-                        -0x1.555555545e43fp-3, 0x1.11110def9bd00p-7, -0x1.a013a80b71025p-13,
-                        0x1.6dbe28b3498d4p-19,
-                        // cos(y) = 1 + z * (c0 + c1 z + c2 z^2 + c3 z^3 + c4 z^4): 2.3e-13
-                        -0x1.fffffffffe699p-2, 0x1.5555555150044p-5, -0x1.6c16bae67d7a6p-10,
-                        0x1.a012993437ed5p-16, -0x1.2474f436b27edp-22};
-  for (int i = 0; i < 25; ++i) t[i] = v[i];
-}
 
 // Compile-time traits of the tasks (include/copterstep.h: CS_TASK_*).
 constexpr bool task_is_lander(int t) {

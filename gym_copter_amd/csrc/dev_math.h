@@ -3,6 +3,8 @@
 // not a stand-alone header.
 #pragma once
 
+#include "trig_reduce.h"
+
 namespace cs {
 namespace {
 
@@ -13,8 +15,19 @@ namespace {
 // |y| <= pi/4: the fdlibm k_sin / k_cos minimax polynomials (<= ~1 ulp) where the state is kept in
 // float64 words (FULL), and two shorter ones (sin 1.4e-11, cos 2.3e-13 absolute) where it is
 // rounded to 29 or 24 significant bits anyway.  Larger angles than 2^19*pi/2 (not reached by a
-// physical trajectory: 8e5 rad) are first folded by multiples of 2^17 * 2pi, which keeps full
-// accuracy up to ~8e11 rad and degrades gracefully beyond.
+// physical trajectory: 8e5 rad) are first folded by multiples of 2^17 * 2pi.  The reduction and the kernels are
+// trig_reduce.h, which a host program compiles too; its table (tests/host/trig_reduce_host.cpp against sinl / cosl,
+// max abs error of sin and cos, 2 M arguments of either sign per magnitude):
+//   |x|              FULL       short      (FULL / short of the fold as it was: all three of its pieces first)
+//   <= 7.9e5         1.8e-16    1.36e-11   (no fold: unchanged, bit for bit)
+//   8e5 +- 5e5 ulps  8.1e-17    6.5e-13    6.1e-13 / 6.5e-13
+//   8.1e5 - 1.0e6    2.1e-16    1.36e-11   3.0e-12 / 1.6e-11
+//   1e8              2.1e-16    1.36e-11   2.9e-11 / 3.4e-11
+//   1e11 - 1e17      2.1e-16    1.38e-11   5.8e-11 / 5.8e-11  (2^-34: the last bit of a folded value of 4e5)
+//   1e18             3.7e-9     3.7e-9
+//   1e20             4.8e-7     4.8e-7
+// Accuracy ends between 1e17 and 1e18: from 2^36 folds on (5.6e16 rad) the fold's second piece times their number no
+// longer fits below the leading remainder's last bit, and the error grows with the angle.
 // (experiment build -DCS_EXP_FULLTRIG: the fdlibm-length polynomials in the float32 storage modes as well -- what the
 // short ones save in time against what they cost in parity)
 #ifdef CS_EXP_FULLTRIG
@@ -22,35 +35,6 @@ constexpr bool kFullTrigInEveryMode = true;
 #else
 constexpr bool kFullTrigInEveryMode = false;
 #endif
-template <bool FULL>
-__device__ __forceinline__ void sincos_kernel(const double* t, double y, double& sy, double& cy) {
-  const double z = y * y;
-  if constexpr (FULL) {
-    double ps = fma(z, t[9], t[8]);
-    ps = fma(z, ps, t[7]);
-    ps = fma(z, ps, t[6]);
-    ps = fma(z, ps, t[5]);
-    ps = fma(z, ps, t[4]);
-    sy = fma(y * z, ps, y);
-    double pc = fma(z, t[15], t[14]);
-    pc = fma(z, pc, t[13]);
-    pc = fma(z, pc, t[12]);
-    pc = fma(z, pc, t[11]);
-    pc = fma(z, pc, t[10]);
-    cy = 1.0 - fma(0.5, z, -(z * z) * pc);
-  } else {
-    double ps = fma(z, t[19], t[18]);
-    ps = fma(z, ps, t[17]);
-    ps = fma(z, ps, t[16]);
-    sy = fma(y * z, ps, y);
-    double pc = fma(z, t[24], t[23]);
-    pc = fma(z, pc, t[22]);
-    pc = fma(z, pc, t[21]);
-    pc = fma(z, pc, t[20]);
-    cy = fma(z, pc, 1.0);
-  }
-}
-
 // The three kernels above in LOCK-STEP: one Horner step of all six chains, then the next -- the same operations on the
 // same values as three sincos_kernel calls (bit-identical), in an order the compiler may not undo: an empty asm
 // statement that names the six accumulators after every step (each next step depends on its outputs; asm volatile
@@ -107,29 +91,11 @@ __device__ __forceinline__ void sincos3_lockstep(const double* t, double a, doub
   }
 }
 
+// the constants come from the kernel-argument block (DevConst::trig, filled by
+// trig_constants()): wide scalar loads instead of literal moves per wavefront
 template <bool FULL>
 __device__ __forceinline__ void sincos_f64(const DevConst& k, double x, double& s, double& c) {
-  if (__builtin_expect(fabs(x) >= 8.0e5, 0)) {
-    const double n1 = rint(x * (1.0 / (6.283185307179586476925 * 131072.0)));
-    // 2pi * 2^17 in the same three pieces as pi/2 below (power-of-two scalings are exact)
-    x = fma(-n1, 1.57079632673412561417e+00 * 524288.0, x);
-    x = fma(-n1, 6.07710050630396597660e-11 * 524288.0, x);
-    x = fma(-n1, 2.02226624879595063154e-21 * 524288.0, x);
-  }
-  // the constants come from the kernel-argument block (DevConst::trig, filled by
-  // trig_constants()): wide scalar loads instead of literal moves per wavefront
-  const double* t = k.trig;
-  const double fn = rint(x * t[0]);
-  double y = fma(-fn, t[1], x);
-  y = fma(-fn, t[2], y);
-  y = fma(-fn, t[3], y);
-  const int q = (int)fn;
-  double sy, cy;
-  sincos_kernel<FULL>(t, y, sy, cy);
-  const double s0 = (q & 1) ? cy : sy;
-  const double c0 = (q & 1) ? sy : cy;
-  s = (q & 2) ? -s0 : s0;
-  c = ((q + 1) & 2) ? -c0 : c0;
+  sincos_reduced<FULL>(k.trig, x, s, c);
 }
 
 // sin and cos of the three Euler angles.  Roll and pitch of a live env are inside +-pi/4 (the task
