@@ -136,6 +136,15 @@ class RolloutEkfIO(C.Structure):
                 ("loglik_dev", C.c_void_p), ("branch_dev", C.c_void_p), ("ok_dev", C.c_void_p)]
 
 
+class RolloutRtsIO(C.Structure):
+    """Mirror of `struct cs_rollout_rts_io` (cs_rollout_rts)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("x_f_dev", C.c_void_p),
+                ("x_pred_dev", C.c_void_p), ("status_f_dev", C.c_void_p), ("P_f_dev", C.c_void_p),
+                ("Q_dev", C.c_void_p), ("P0_dev", C.c_void_p), ("end_x_dev", C.c_void_p), ("end_P_dev", C.c_void_p),
+                ("P_tape_dev", C.c_void_p), ("var_dev", C.c_void_p), ("x0_dev", C.c_void_p), ("P0_s_dev", C.c_void_p),
+                ("ok_dev", C.c_void_p)]
+
+
 class RolloutMppiIO(C.Structure):
     """Mirror of `struct cs_rollout_mppi_io` (cs_rollout_mppi_costs / cs_rollout_mppi_update)."""
     _fields_ = [("struct_size", C.c_uint32), ("num_samples", C.c_int32), ("noise_stream", C.c_uint32),
@@ -273,6 +282,7 @@ SYMBOLS = {
     "cs_rollout_lqr": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqrIO), _P]),
     "cs_rollout_feedback_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO), _P]),
     "cs_rollout_ekf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutEkfIO), _P]),
+    "cs_rollout_rts": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutRtsIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),

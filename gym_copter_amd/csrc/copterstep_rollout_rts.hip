@@ -1,0 +1,347 @@
+// copterstep_rollout_rts.hip -- a Rauch-Tung-Striebel fixed-interval smoother over the tapes of cs_rollout_ekf on gfx950
+// (cs_rollout_rts, include/copterstep.h): K backward steps per env in one launch, each the filter's covariance
+// prediction made again from the filter's own tapes -- the step Jacobian applied on the fly, never stored -- followed by
+// one 12 x 12 symmetric positive definite solve.  Every input is a tape or the caller's: nothing of the env state is
+// read but the constants and the vehicle table, and nothing is written.  DESIGN.md section 20.
+//
+// Upstream lines differentiated: those of copterstep_jacobian.hip (setMotors, the state derivative, step).
+//
+// One lane per env on the tile layout of the step kernels (tile t -> workgroup t).  Per backward step j = K-2 .. -1
+// (row -1 is the filter's starting point):
+//   prediction  P- = A P_f[j] A^T + Q through jacobian_block (jacobian_tangents.h) at (x_f[j], status_f[j]) under
+//               actions[j+1] with zero wrench tangents, in copterstep_rollout_ekf.hip's two passes of 6 blocks of 2
+//               directions, restated here: in float64 P- is the filter's own prior of that step bit for bit.  W = A P_f[j]
+//               is kept.
+//   solve       D = P_s[j+1] - P-, then P- = U^T U in place and G = P-^-1 W column by column in place (rts_solve.h)
+//   smoothing   x_s[j] = x_f[j] + G^T (x_s[j+1] - x_pred[j+1]);  P_s[j] = P_f[j] + G^T D G, column by column into the
+//               rows of the factor, which is dead once G is solved
+// In lane-private LDS columns (element k of a lane at [k * 64 + lane], as section 13's): two packed triangles of 78
+// rows that swap roles from step to step -- one is P_f[j], P-, U, P_s[j] in turn, the other P_s[j+1] and then D --, W / G
+// (144 rows and one row of stage padding behind it) and x_s[j+1] (12 rows): 313 rows x 512 B = 156.5 KiB of the CU's
+// 160, one wavefront per CU (profiles/rollout_rts_resources.txt).  What does not fit is read from the input tapes where
+// it is needed: the Jacobian's point x_f[j] once per block (L2 hits beside a jacobian_block) and P_f[j] a second time
+// for the smoothed covariance.  Once G is dead the wavefront's 12 x 12 outputs and its mean rows are staged in its rows
+// and leave as linear runs.  No output of this launch is read back.
+#include <cmath>
+#include <string>
+
+#include "copterstep_jacobian.h"
+
+// P- must round as the filter's did (the no-measurement identities of section 20 rest on it), and the solve's float64
+// arithmetic is fixed (one multiply and one add or subtract per term, no fma)
+#pragma clang fp contract(off)
+
+#include "dev_tile.h"
+#include "dev_codec.h"
+#include "dev_math.h"
+#include "dev_physics.h"
+#include "dev_task.h"
+#include "jacobian_tangents.h"
+#include "rollout_adjoint.h"
+#include "rollout_step.h"
+#include "rollout_sweep.h"
+#include "rts_solve.h"
+#include "dev_launch.h"
+
+namespace cs {
+namespace {
+
+// the lane's LDS rows (row k at [k * kBlock]): triangle 0, W = A P_f (W[i][c] at i * 12 + c) with one row of padding
+// behind it (the stage of the 12 x 12 stores: a lane's matrix row-major at stride 145), triangle 1, x_s[j+1]
+constexpr int kRowW = kEkfSym;
+constexpr int kStageStride = 145;  // (odd: the lanes' stage writes fall into different banks)
+constexpr int kRowT1 = kRowW + kStageStride;
+constexpr int kRowXs = kRowT1 + kEkfSym;
+constexpr int kRtsRows = kRowXs + 12;
+static_assert(kStageStride * kWave <= (kRowT1 - kRowW) * kBlock, "the stage fits W and its padding row");
+static_assert(kRtsRows * kBlock * sizeof(double) <= 160 * 1024, "the LDS of one CU");
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ void store_out(void* dst, size_t at, double v, uint32_t f32) {
+  if (f32)
+    reinterpret_cast<float*>(dst)[at] = (float)v;
+  else
+    reinterpret_cast<double*>(dst)[at] = v;
+}
+
+// The wavefront's staged matrices (lane l's at stage[l * kStageStride ..], row-major) to rows `at` .. of an [.., N, 144]
+// output: a whole wavefront's 64 x 144 values are one contiguous run, read back linearly so that every store instruction
+// writes whole lines; a partial wavefront lane by lane.
+__device__ __forceinline__ void store_matrix(void* dst, size_t at, const double* stage, const RowOut& ro, uint32_t f32) {
+  if (ro.whole) {
+    const size_t base = (at + ro.env0) * 144;
+#pragma clang loop unroll(disable)
+    for (int v = 0; v < 144; ++v) {
+      const int el = v * kWave + ro.lane;
+      const int ln = el / 144, idx = el - ln * 144;
+      store_out(dst, base + el, stage[ln * kStageStride + idx], f32);
+    }
+  } else if (ro.valid) {
+    const size_t base = (at + ro.i) * 144;
+    const double* mine = stage + ro.lane * kStageStride;
+#pragma clang loop unroll(disable)
+    for (int v = 0; v < 144; ++v) store_out(dst, base + v, mine[v], f32);
+  }
+}
+
+// the upper triangle of a row-major 12 x 12 matrix in global memory -> a packed triangle in the lane's LDS column
+// (unrolled: the 78 loads are independent and in flight together; one at a time they would cost 78 L2 latencies a step)
+__device__ __forceinline__ void load_triangle(double* T, const double* p) {
+#pragma unroll
+  for (int a = 0; a < 12; ++a) {
+#pragma unroll
+    for (int j = a; j < 12; ++j) T[(j * (j + 1) / 2 + a) * kBlock] = p[a * 12 + j];
+  }
+}
+
+// a packed triangle -> the lane's stage, full and symmetric (the caller syncs the wavefront before the stage is stored)
+__device__ __forceinline__ void stage_triangle(double* mine, const double* T) {
+#pragma clang loop unroll(disable)
+  for (int a = 0; a < 12; ++a) {
+#pragma unroll
+    for (int b = 0; b < 12; ++b) mine[a * 12 + b] = T[ekf_sym_at(a, b) * kBlock];
+  }
+}
+
+template <int TASK, int MODE, bool GYRO>
+__global__ __launch_bounds__(kBlock) void rollout_rts_kernel(const DevConst c, const DevState s, const cs_rollout_io io,
+                                                             const cs_rollout_rts_io r) {
+  constexpr int A = task_act_dim(TASK);
+  constexpr bool FULL = MODE == CS_STATE_F64 || kFullTrigInEveryMode;
+  __shared__ __attribute__((aligned(16))) double lds[kRtsRows * kBlock];
+  const int lane = threadIdx.x;
+  const uint32_t tile_index = blockIdx.x;
+  const uint32_t i = tile_index * kBlock + threadIdx.x;
+  const uint32_t n = s.n;
+  const uint32_t env0 = i - lane;
+  const RowOut ro{lane, i, env0, i < n, env0 + (uint32_t)kWave <= n};
+  const uint32_t ii = ro.valid ? i : 0u;  // (padding lanes smooth env 0 and store nothing)
+  const int K = io.num_steps;
+  const uint32_t f32 = r.out_dtype == CS_JAC_F32 ? 1u : 0u;
+
+  Coef q = uniform_coef(c);
+  if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
+  double* const W = lds + lane + kRowW * kBlock;
+  double* const XS = lds + lane + kRowXs * kBlock;
+  double* const stage = lds + kRowW * kBlock;
+  double* const mine = stage + lane * kStageStride;
+  // the two triangles by their offsets, which swap after every step: `ta` takes P_f[j] and ends as P_s[j], `tb` holds
+  // P_s[j+1]
+  int ta = 0, tb = kRowT1 * kBlock;
+  bool ok = true;
+
+  // ---- row K-1 is given: the filter's own, or the caller's (end_x, end_P) ----
+  {
+    const size_t row = (size_t)(K - 1) * n;  // 64-bit: K x N x 144 doubles pass 4 GiB at 1 M envs
+    double x[12];
+    if (r.end_x_dev != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) x[k] = r.end_x_dev[(size_t)k * n + ii];
+    } else {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) x[k] = r.x_f_dev[(row + ii) * 12 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) XS[k * kBlock] = x[k];
+    double* const Tb = lds + lane + tb;
+    load_triangle(Tb, r.end_P_dev != nullptr ? r.end_P_dev + (size_t)ii * 144 : r.P_f_dev + (row + ii) * 144);
+    if (io.x_dev != nullptr) store_x_row(stage, io.x_dev, row, ro, x);
+    if (r.P_tape_dev != nullptr) {
+      stage_triangle(mine, Tb);
+      wave_sync();
+      store_matrix(r.P_tape_dev, row, stage, ro, f32);
+      wave_sync();  // (the first step's W is written over the stage)
+    }
+    if (ro.valid && r.var_dev != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) store_out(r.var_dev, (row + i) * 12 + k, Tb[(k * (k + 1) / 2 + k) * kBlock], f32);
+    }
+  }
+
+#pragma clang loop unroll(disable)
+  for (int j = K - 2; j >= -1; --j) {
+    const bool first = j < 0;  // the filter's starting point: x0 [12,N], P0, status0
+    const size_t row = first ? 0 : (size_t)j * n;
+    const size_t next = (size_t)(j + 1) * n;
+    const double* const xf = first ? io.start_x_dev + ii : r.x_f_dev + (row + ii) * 12;
+    const size_t xf_stride = first ? (size_t)n : (size_t)1;
+    const double* const pf = first ? r.P0_dev + (size_t)ii * 144 : r.P_f_dev + (row + ii) * 144;
+    const int fs0 = first ? (int)io.start_status_dev[ii] : (int)r.status_f_dev[row + ii];
+    double* const Ta = lds + lane + ta;
+    double* const Tb = lds + lane + tb;
+
+    // ---- the step's wrench, as the filter made it for step j+2 ----
+    const float4 act = load_action_at<TASK>(io.actions_dev + (next + ii) * A);
+    const float araw[4] = {act.x, act.y, act.z, act.w};
+    float mf[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) mf[k] = clip01(araw[k]);
+    Wrench w;
+    w.bz = thrust_model(q, mf[0], mf[1], mf[2], mf[3]);
+    torque_model(q, mf[0], mf[1], mf[2], mf[3], w);
+
+    load_triangle(Ta, pf);
+
+    // ---- the prediction: 12 blocks of 2 directions through the tangents of the step, the actions known ----
+    const Wrench zero{0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma clang loop unroll(disable)
+    for (int b = 0; b < 12; ++b) {
+      const bool second = b >= 6;  // pass 1: columns 2 b', 2 b' + 1 of P_f -> those of W; pass 2: rows of W -> columns of P-
+      const int c0 = (second ? b - 6 : b) * kJacDirs;
+      JacPoint pt;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) pt.x[k] = xf[k * xf_stride];
+      pt.fs = fs0;
+      pt.active = fs0 != CS_STATUS_LANDED;
+      pt.px = pt.py = pt.pz = -0.0;
+      double v[kJacDirs][12];
+      const Wrench dw[kJacDirs] = {zero, zero};
+#pragma unroll
+      for (int d = 0; d < kJacDirs; ++d) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+          v[d][k] = second ? W[((c0 + d) * 12 + k) * kBlock] : Ta[ekf_sym_at(k, c0 + d) * kBlock];
+      }
+      double xn[12];
+      jacobian_block<FULL, GYRO>(c, q, w, dw, pt, xn, v);
+      if (!second) {
+#pragma unroll
+        for (int d = 0; d < kJacDirs; ++d) {
+#pragma unroll
+          for (int k = 0; k < 12; ++k) W[(k * 12 + c0 + d) * kBlock] = v[d][k];
+        }
+      } else {  // column c0 + d of P- above its diagonal (every column of P_f was read in pass 1), plus Q
+#pragma unroll
+        for (int d = 0; d < kJacDirs; ++d) {
+          const int col = c0 + d;
+#pragma unroll
+          for (int k = 0; k < 12; ++k) {
+            if (k <= col) Ta[(col * (col + 1) / 2 + k) * kBlock] = v[d][k] + r.Q_dev[k * 12 + col];
+          }
+        }
+      }
+    }
+
+    // ---- D = P_s[j+1] - P-, the factor of P-, G = P-^-1 W ----
+#pragma unroll 13
+    for (int k = 0; k < kEkfSym; ++k) Tb[k * kBlock] -= Ta[k * kBlock];
+    ok = rts_cholesky(Ta, kBlock) && ok;
+#pragma clang loop unroll(disable)
+    for (int col = 0; col < 12; ++col) rts_solve_column(Ta, W, col, kBlock);
+
+    // ---- the smoothed mean, kept for the next step ----
+    double x[12];
+    {
+      double xp[12], dx[12];
+      const double* const pred = r.x_pred_dev + (next + ii) * 12;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        xp[k] = xf[k * xf_stride];
+        dx[k] = XS[k * kBlock] - pred[k];
+      }
+      rts_mean(W, kBlock, xp, dx, XS);
+#pragma unroll
+      for (int k = 0; k < 12; ++k) x[k] = XS[k * kBlock];
+    }
+
+    // ---- the smoothed covariance, over the factor ----
+#pragma clang loop unroll(disable)
+    for (int col = 0; col < 12; ++col) rts_ps_column(Tb, W, col, kBlock, pf + col, Ta);
+
+    // ---- row j out (G is dead: its rows are the stage) ----
+    wave_sync();
+    if (!first) {
+      if (io.x_dev != nullptr) store_x_row(stage, io.x_dev, row, ro, x);
+    } else if (ro.valid && r.x0_dev != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) r.x0_dev[(size_t)k * n + i] = x[k];
+    }
+    void* const pdst = first ? r.P0_s_dev : r.P_tape_dev;
+    if (pdst != nullptr) {
+      stage_triangle(mine, Ta);
+      wave_sync();
+      store_matrix(pdst, row, stage, ro, f32);
+    }
+    wave_sync();  // (the next step's W is written over the stage)
+    if (!first && ro.valid && r.var_dev != nullptr) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) store_out(r.var_dev, (row + i) * 12 + k, Ta[(k * (k + 1) / 2 + k) * kBlock], f32);
+    }
+    const int t = ta;
+    ta = tb;
+    tb = t;
+  }
+
+  if (ro.valid && r.ok_dev != nullptr) r.ok_dev[i] = ok ? 1 : 0;
+}
+
+template <int TASK, int MODE>
+hipError_t rts_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const cs_rollout_rts_io& r,
+                 hipStream_t stream) {
+  const dim3 grid(grid_for(s.n)), block(kBlock);
+  if (c.gyro)
+    hipLaunchKernelGGL((rollout_rts_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, r);
+  else
+    hipLaunchKernelGGL((rollout_rts_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, r);
+  return hipGetLastError();
+}
+
+hipError_t launch_rollout_rts(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
+                              const cs_rollout_rts_io& r, hipStream_t stream) {
+  CS_DISPATCH(rts_t, c, s, io, r, stream)
+}
+
+bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+}  // namespace
+}  // namespace cs
+
+extern "C" int cs_rollout_rts(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_rts_io* rio, void* stream) {
+  using cs::report_error;
+  const char* who = "cs_rollout_rts";
+  if (int rc_ = cs::check_rollout_io(io, who, false)) return rc_;
+  if (rio == nullptr) return report_error(CS_ERR_ARG, "cs_rollout_rts: null rio");
+  if (rio->struct_size != sizeof(cs_rollout_rts_io))
+    return report_error(CS_ERR_ABI, ("cs_rollout_rts: rio->struct_size " + std::to_string(rio->struct_size) + " != " +
+                                     std::to_string(sizeof(cs_rollout_rts_io)) + " (sizeof(cs_rollout_rts_io))").c_str());
+  if (io->start_x_dev == nullptr || io->start_status_dev == nullptr)
+    return report_error(CS_ERR_ARG, "cs_rollout_rts: start_x_dev (the filter's x0) and start_status_dev are required");
+  if (io->start_force_dev != nullptr || io->start_prev_shaping_dev != nullptr)
+    return report_error(CS_ERR_ARG, "cs_rollout_rts: start_force_dev and start_prev_shaping_dev must be NULL");
+  if (io->reward_dev != nullptr || io->terminated_dev != nullptr || io->truncated_dev != nullptr ||
+      io->status_dev != nullptr || io->gx_dev != nullptr || io->gr_dev != nullptr || io->g_actions_dev != nullptr ||
+      io->g_x0_dev != nullptr)
+    return report_error(CS_ERR_ARG,
+                        "cs_rollout_rts: the reward, flag, status, cotangent and gradient pointers must be NULL");
+  if (rio->out_dtype != CS_JAC_F64 && rio->out_dtype != CS_JAC_F32)
+    return report_error(CS_ERR_ARG, "cs_rollout_rts: unknown rio->out_dtype (CS_JAC_F64 or CS_JAC_F32)");
+  if (rio->x_f_dev == nullptr || rio->x_pred_dev == nullptr || rio->status_f_dev == nullptr ||
+      rio->P_f_dev == nullptr || rio->Q_dev == nullptr || rio->P0_dev == nullptr)
+    return report_error(CS_ERR_ARG,
+                        "cs_rollout_rts: x_f_dev, x_pred_dev, status_f_dev, P_f_dev, Q_dev and P0_dev are required");
+  if ((rio->end_x_dev == nullptr) != (rio->end_P_dev == nullptr))
+    return report_error(CS_ERR_ARG, "cs_rollout_rts: end_x_dev and end_P_dev are given both or neither");
+  const void* f64s[] = {io->start_x_dev, io->x_dev, rio->x_f_dev, rio->x_pred_dev, rio->P_f_dev, rio->Q_dev,
+                        rio->P0_dev, rio->end_x_dev, rio->end_P_dev, rio->x0_dev};
+  for (const void* p : f64s)
+    if (!cs::aligned8(p)) return report_error(CS_ERR_ARG, "cs_rollout_rts: a float64 array is not 8-B aligned");
+  const uintptr_t out_mask = rio->out_dtype == CS_JAC_F32 ? 3u : 7u;
+  const void* outs[] = {rio->P_tape_dev, rio->var_dev, rio->P0_s_dev};
+  for (const void* p : outs)
+    if ((reinterpret_cast<uintptr_t>(p) & out_mask) != 0)
+      return report_error(CS_ERR_ARG, "cs_rollout_rts: an output array is not aligned to its element size");
+  if ((reinterpret_cast<uintptr_t>(io->actions_dev) & 3u) != 0)
+    return report_error(CS_ERR_ARG, "cs_rollout_rts: actions_dev is not 4-B aligned");
+  cs::ContextView v;
+  if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
+  if (v.c->act_f32)
+    return report_error(CS_ERR_ARG, "cs_rollout_rts: not available with the float32 motor model (action_arith)");
+  const hipError_t e = cs::launch_rollout_rts(v.task, v.mode, *v.c, *v.s, *io, *rio, (hipStream_t)stream);
+  if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_rts: kernel launch");
+  return CS_OK;
+}

@@ -1,11 +1,12 @@
 """A small streaming driver on CopterVecEnv.rollout_ekf: an extended Kalman filter per env whose
-measurements arrive a chunk of steps at a time, and the synthetic measurements to try it on.
+measurements arrive a chunk of steps at a time, the synthetic measurements to try it on, and the chunked driver of the
+smoother over its tapes, CopterVecEnv.rollout_rts.
 
     z = H x + e,  e ~ N(0, diag(r));     x- = step(xhat, a),  P- = A P A^T + Q;     sequential scalar updates
 
 The filter's state (mean, covariance, flight status) is carried from call to call on the device; nothing is read by the
 host."""
-from .vecenv import EkfResult
+from .vecenv import EkfResult, RtsResult
 
 
 def _torch():
@@ -65,3 +66,38 @@ def ekf(env, actions, z, H, r, Q, x0, P0, status0=None, chunk=None):
         ok = res.ok.clone() if ok is None else ok & res.ok
     xs, xp, var, nis, st, br, pt = (torch.cat([p[j] for p in parts]) for j in range(7))
     return EkfResult(xs, xp, P, var, nis, loglik, st, br, ok, pt)
+
+
+def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None):
+    """Run env.rollout_rts over the K steps of a filter's tapes in chunks of `chunk` steps (None: one call), last chunk
+    first: a chunk starts from the filter's row before it (the caller's x0, P0, status0 for the first chunk) and ends in
+    the smoothed starting point the chunk after it returned.  Returns RtsResult with the tapes of all K steps
+    concatenated (P_tape included), x0 and P0 the smoothed starting point and ok the chunks' conjunction -- tensors of
+    their own, not the env's buffers.  Every tape, x0, P0 and ok are bit-identical to the single call's: a chunk boundary
+    rounds nothing (float64 throughout).  filt is the EkfResult of the whole filter with its float64 P_tape
+    (rollout_ekf(..., tape=True) or ekf()); the other arguments are rollout_rts'."""
+    torch = _torch()
+    K = int(actions.shape[0])
+    chunk = K if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1, got %r" % (chunk,))
+    if not isinstance(filt, EkfResult) or filt.P_tape is None:
+        raise ValueError("filt must be an EkfResult with its P_tape (rollout_ekf(..., tape=True))")
+    for t, name in ((filt.x, "x"), (filt.x_pred, "x_pred"), (filt.status, "status"), (filt.P_tape, "P_tape")):
+        if not isinstance(t, torch.Tensor) or t.shape[0] != K:
+            raise ValueError("filt.%s must be a tensor of K = %d rows" % (name, K))
+    parts, end, ok, res = [], None, None, None
+    for k0 in reversed(range(0, K, chunk)):
+        k1 = min(k0 + chunk, K)
+        if k0 == 0:
+            start = (x0, P0, status0)
+        else:
+            start = (filt.x[k0 - 1].T.contiguous(), filt.P_tape[k0 - 1], filt.status[k0 - 1])
+        sub = EkfResult(filt.x[k0:k1], filt.x_pred[k0:k1], None, None, None, None, filt.status[k0:k1], None, None,
+                        filt.P_tape[k0:k1])
+        res = env.rollout_rts(actions[k0:k1], sub, Q, start[0], start[1], status0=start[2], end=end, tape=True)
+        parts.append([t.clone() for t in (res.x, res.P_tape, res.var)])
+        end = (res.x0.clone(), res.P0.clone())
+        ok = res.ok.clone() if ok is None else ok & res.ok
+    xs, pt, var = (torch.cat([p[j] for p in reversed(parts)]) for j in range(3))
+    return RtsResult(xs, pt, var, end[0], end[1], ok)

@@ -221,6 +221,11 @@ class ShardedCopterVecEnv:
         return self.local.rollout_ekf(self._local_rollout_actions(actions), z, H, r, Q, x0, P0, status0=status0,
                                       tape=tape, dtype=dtype)
 
+    def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):
+        """CopterVecEnv.rollout_rts of this rank's envs: shard-local (filt, x0, P0, status0, end: the local envs')."""
+        return self.local.rollout_rts(self._local_rollout_actions(actions), filt, Q, x0, P0, status0=status0, end=end,
+                                      tape=tape, dtype=dtype)
+
     def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
                            stream=0, state=None, knots=None):
         """CopterVecEnv.rollout_mppi_costs of this rank's envs: shard-local (x_ref, state: the local envs').  The noise

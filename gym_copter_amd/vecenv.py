@@ -101,6 +101,10 @@ LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
 # last posterior covariance P [N,12,12], its diagonal per step var [K,N,12], nis [K,N], loglik [N], the status [K,N] and
 # step_jacobian branch bits [K,N] of the filter's own mean, ok [N] bool, and P_tape [K,N,12,12] (None without tape=True)
 EkfResult = collections.namedtuple("EkfResult", "x x_pred P var nis loglik status branch ok P_tape")
+# CopterVecEnv.rollout_rts' result: the smoothed means x [K,N,12], their covariances P_tape
+# [K,N,12,12] (None with tape=False) and diagonals var [K,N,12], the smoothed starting point x0 [12,N], P0 [N,12,12], and
+# ok [N] bool (every Cholesky pivot positive and finite)
+RtsResult = collections.namedtuple("RtsResult", "x P_tape var x0 P0 ok")
 # CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
 MppiCosts = collections.namedtuple("MppiCosts", "costs best")
 MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
@@ -1616,6 +1620,121 @@ class CopterVecEnv(_VectorEnvBase):
         with torch.cuda.device(self.device):
             _lib.check(self._lib.cs_rollout_ekf(self._ctx, C.byref(io), C.byref(eio), self._stream()))
         self._keep = keep + [Hd, rd, Qd]
+        return out
+
+    # -- the Rauch-Tung-Striebel smoother over the filter's tapes --------
+    def _rts_Q(self, Q):
+        """Q [12,12], checked on the host (finite, symmetric) and kept on the device: the same values are uploaded once
+        (a chunked smoother passes them with every chunk); a device tensor is recognised by identity and version."""
+        torch = _torch()
+        ident = (id(Q), Q._version, Q.data_ptr()) if isinstance(Q, torch.Tensor) else None
+        cache = getattr(self, "_rts_q", None)
+        if ident is not None and cache is not None and cache[2] == ident:
+            return cache[1]
+        q = np.asarray(Q.detach().cpu() if isinstance(Q, torch.Tensor) else Q)
+        if q.dtype.kind not in "fiu":
+            raise ValueError("Q must be a real floating-point array, got dtype %s" % q.dtype)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.shape != (12, 12):
+            raise ValueError("Q must have shape (12, 12), got %s" % (q.shape,))
+        if not np.isfinite(q).all():
+            raise ValueError("Q must be finite")
+        if not np.array_equal(q, q.T):
+            raise ValueError("Q must be symmetric")
+        key = q.tobytes()
+        if cache is None or cache[0] != key:
+            cache = (key, torch.from_numpy(q).to(self.device))
+        # (the caller's tensor is kept alive with its identity, so that an id cannot be reused by another tensor)
+        cache = self._rts_q = (cache[0], cache[1], ident, Q if ident is not None else None)
+        return cache[1]
+
+    def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):
+        """A Rauch-Tung-Striebel fixed-interval smoother over the tapes of rollout_ekf, K backward steps per env in one
+        kernel: the estimate of every step given the measurements of all K steps, and that of the starting point.  The
+        step Jacobian is applied on the fly at the filter's own points and never stored.  NO env state is read but the
+        configuration and the vehicle, and none changes.
+
+        actions [K,N,A], Q, x0 [12,N], P0 [N,12,12] and status0 are what the filter was given; filt is its EkfResult
+        from rollout_ekf(..., tape=True) in float64 (x, x_pred, status and P_tape are read).  Q should be positive
+        definite: a merely PSD Q can make a prior singular, which clears ok.  end = (x_end [12,N], P_end [N,12,12])
+        gives the smoothed last row (default: the filter's own last row) -- the smoothed starting point of the chunk that
+        follows, for a tape smoothed in chunks (gym_copter_amd.smooth).
+
+        Row K-1 is the given one; then for j = K-2 down to -1 (row -1 is the starting point), with A the step Jacobian at
+        (x_f[j], status_f[j]) under actions[j+1]:  P- = A P_f[j] A^T + Q (the filter's prior, bit for bit),
+        G = P-^-1 A P_f[j] by Cholesky,  x_s[j] = x_f[j] + G^T (x_s[j+1] - x_pred[j+1]),
+        P_s[j] = P_f[j] + G^T (P_s[j+1] - P-) G.
+
+        Returns RtsResult(x [K,N,12] the smoothed means, P_tape [K,N,12,12] their covariances (None with tape=False),
+        var [K,N,12] the covariances' diagonals, x0 [12,N] and P0 [N,12,12] the smoothed starting point, ok [N] bool
+        (False where a Cholesky pivot was <= 0 or not finite; the outputs are written regardless)).  dtype: torch.float64
+        (default) or torch.float32 (P_tape, var, P0: the float64 values rounded).  Not available under
+        action_arith="float32".  Asynchronous on the current stream; the tensors are buffers of this env, overwritten by
+        its next call with the same K, dtype and tape."""
+        self._check_open()
+        torch = _torch()
+        dtype = self._out_dtype(dtype)
+        if self.config.action_arith != _ARITH["float64"]:
+            raise ValueError('rollout_rts is not available under action_arith="float32"')
+        Qd = self._rts_Q(Q)
+        io, K, keep = self._rollout_io(actions, None)
+        n, dev = self.num_envs, self.device
+        if not isinstance(filt, EkfResult):
+            raise ValueError("filt must be the EkfResult of rollout_ekf(..., tape=True)")
+        if filt.P_tape is None:
+            raise ValueError("filt has no P_tape: filter with rollout_ekf(..., tape=True)")
+        if isinstance(filt.P_tape, torch.Tensor) and filt.P_tape.dtype != torch.float64:
+            raise ValueError("filt.P_tape must be float64 (rollout_ekf's default dtype), got %s" % filt.P_tape.dtype)
+        self._check_tape("rollout_ekf", (filt.x, "filt.x", (K, n, 12), torch.float64),
+                         (filt.x_pred, "filt.x_pred", (K, n, 12), torch.float64),
+                         (filt.status, "filt.status", (K, n), torch.uint8),
+                         (filt.P_tape, "filt.P_tape", (K, n, 12, 12), torch.float64))
+        xt = self._ekf_input(x0, (12, n), "x0", keep)
+        Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
+        if status0 is None:
+            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=dev)
+            keep.append(st)
+            io.start_status_dev = st.data_ptr()
+        else:
+            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
+        io.start_x_dev = xt.data_ptr()
+        rio = _lib.RolloutRtsIO()
+        rio.struct_size = C.sizeof(_lib.RolloutRtsIO)
+        rio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+        if end is not None:
+            if not isinstance(end, (tuple, list)) or len(end) != 2 or end[0] is None or end[1] is None:
+                raise ValueError("end must be the pair (x_end [12,N], P_end [N,12,12]): both or neither")
+            rio.end_x_dev = self._ekf_input(end[0], (12, n), "end[0]", keep).data_ptr()
+            rio.end_P_dev = self._ekf_input(end[1], (n, 12, 12), "end[1]", keep).data_ptr()
+        rio.x_f_dev, rio.x_pred_dev = filt.x.data_ptr(), filt.x_pred.data_ptr()
+        rio.status_f_dev, rio.P_f_dev = filt.status.data_ptr(), filt.P_tape.data_ptr()
+        rio.Q_dev, rio.P0_dev = Qd.data_ptr(), Pt.data_ptr()
+        tape = bool(tape)
+        out = self._rollout_cache(("rts", K, dtype, tape), lambda: RtsResult(
+            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
+            torch.empty((K, n, 12, 12), dtype=dtype, device=dev) if tape else None,
+            torch.empty((K, n, 12), dtype=dtype, device=dev), torch.empty((12, n), dtype=torch.float64, device=dev),
+            torch.empty((n, 12, 12), dtype=dtype, device=dev), torch.empty(n, dtype=torch.bool, device=dev)))
+        # (no output may overlap an input: the caller's tensors that are this call's own buffers are copied first)
+        mine = {t.data_ptr() for t in out if t is not None}
+        for name in ("end_x_dev", "end_P_dev", "P0_dev"):
+            if getattr(rio, name) in mine:
+                src = next(t for t in keep if t.data_ptr() == getattr(rio, name))
+                cp = src.clone()
+                keep.append(cp)
+                setattr(rio, name, cp.data_ptr())
+        if io.start_x_dev in mine:
+            cp = xt.clone()
+            keep.append(cp)
+            io.start_x_dev = cp.data_ptr()
+        io.x_dev = out.x.data_ptr()
+        rio.var_dev, rio.x0_dev, rio.P0_s_dev = out.var.data_ptr(), out.x0.data_ptr(), out.P0.data_ptr()
+        rio.ok_dev = out.ok.data_ptr()
+        if tape:
+            rio.P_tape_dev = out.P_tape.data_ptr()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.cs_rollout_rts(self._ctx, C.byref(io), C.byref(rio), self._stream()))
+        self._keep = keep + [Qd, filt.x, filt.x_pred, filt.status, filt.P_tape]
         return out
 
     # -- MPPI: sampled rollouts, their costs and the weighted update (DESIGN section 14) --------

@@ -39,6 +39,8 @@
  *                            feedback that pass returns          in place of the random action
  *   cs_rollout_ekf           an extended Kalman filter over     the rollout lines above and their Jacobian (no upstream
  *                            the step, K steps per env           counterpart: a state estimator)
+ *   cs_rollout_rts           a Rauch-Tung-Striebel smoother     the same Jacobian at the filter's points (no upstream
+ *                            over that filter's tapes            counterpart: a fixed-interval smoother)
  *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
  *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
  *   cs_rollout_mppi_update   their cost-weighted average         (the same)
@@ -886,6 +888,61 @@ typedef struct cs_rollout_ekf_io {
   uint8_t* ok_dev;             /* [N] */
 } cs_rollout_ekf_io;
 int cs_rollout_ekf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_ekf_io* eio, void* stream);
+
+/* A Rauch-Tung-Striebel fixed-interval smoother over the tapes of cs_rollout_ekf, on the device:
+ * the estimate of every step given the measurements of all K steps, in one call of K backward steps per env.  The step
+ * Jacobian is applied on the fly, at the filter's own points, and never stored.  No env state is read except the
+ * context's constants and vehicle table, and none is written.
+ *
+ * Row k = 0 .. K-1 of a tape is the state after step k+1; "row -1" is the filter's starting point (x0, P0, status0).
+ *
+ * From io: num_steps = K, actions_dev [K,N,A] (the filter's), start_x_dev [12,N] = x0 and start_status_dev [N] = status0
+ * (both required); x_dev [K,N,12] (or NULL) receives the smoothed means; every other pointer of io must be NULL.
+ *
+ * From rio, the inputs (float64; the four tapes are cs_rollout_ekf's x_dev, x_pred_dev, status_dev and, with CS_JAC_F64,
+ * P_tape_dev of the call that filtered these K steps from this starting point with this Q):
+ *   x_f_dev      [K,N,12]     the filtered means        x_pred_dev [K,N,12]  the prior means
+ *   status_f_dev [K,N] uint8  the filter's status       P_f_dev    [K,N,12,12]  the posteriors: upper triangles are read
+ *   Q_dev        [12,12]      symmetric positive definite, shared (a merely PSD Q can make a prior singular: ok = 0)
+ *   P0_dev       [N,12,12]    symmetric: its upper triangle is read
+ *   end_x_dev [12,N], end_P_dev [N,12,12]   both or neither (NULL): the smoothed row K-1, for a caller that smooths a
+ *                             long tape in chunks, last chunk first: the smoothed starting point of the following chunk
+ * The smoothed row K-1 is given: the filter's own row K-1, or (end_x, the upper triangle of end_P, mirrored); it is
+ * written out as it is.  Then for j = K-2 down to -1 and every env, in float64 without contraction:
+ *   predict   A = cs_step_jacobian's dx at (x_f[j], status_f[j]) under actions[j+1], with every rule of that call and a
+ *             zero wrench tangent: the point and the wrench cs_rollout_ekf used for step j+2.  W = A P_f[j];
+ *             P- = W A^T + Q, the upper triangle kept, one add per entry for Q: the filter's own prior, bit for bit.
+ *   solve     P- = L L^T by Cholesky.  If a pivot is <= 0 or not finite the env's ok is 0; the arithmetic is carried
+ *             through and every output is written regardless.  G = P-^-1 W by a forward and a backward substitution per
+ *             column (the smoother gain is G^T).
+ *   smooth    x_s[j] = x_f[j] + G^T (x_s[j+1] - x_pred[j+1]);  P_s[j] = P_f[j] + G^T (P_s[j+1] - P-) G, its upper
+ *             triangle computed and mirrored on store.
+ * The order of every sum is fixed (gym_copter_amd/csrc/rts_solve.h).
+ * Outputs, each may be NULL; P_tape, var and P0_s in out_dtype (CS_JAC_F64, or CS_JAC_F32: the float64 values rounded):
+ *   io->x_dev  [K,N,12] float64  the smoothed means           P_tape_dev [K,N,12,12]  the smoothed covariances
+ *   var_dev    [K,N,12]          their diagonals              x0_dev     [12,N] float64  the smoothed starting point
+ *   P0_s_dev   [N,12,12]         its covariance               ok_dev     [N] uint8
+ * No output may overlap an input.  Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32.  Asynchronous on `stream`;
+ * rio->struct_size must be sizeof(cs_rollout_rts_io) (else CS_ERR_ABI); both blocks are checked before the context.  Q
+ * is read by the scalar unit: 8-B aligned (as every float64 array here), never written while a call runs. */
+typedef struct cs_rollout_rts_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_rts_io) */
+  uint32_t out_dtype;          /* CS_JAC_F64 / CS_JAC_F32: P_tape_dev, var_dev, P0_s_dev */
+  const double* x_f_dev;       /* [K,N,12], required */
+  const double* x_pred_dev;    /* [K,N,12], required */
+  const uint8_t* status_f_dev; /* [K,N], required */
+  const double* P_f_dev;       /* [K,N,12,12], required */
+  const double* Q_dev;         /* [12,12], required */
+  const double* P0_dev;        /* [N,12,12], required */
+  const double* end_x_dev;     /* [12,N] or NULL */
+  const double* end_P_dev;     /* [N,12,12] or NULL (with end_x_dev: both or neither) */
+  void* P_tape_dev;            /* [K,N,12,12] */
+  void* var_dev;               /* [K,N,12] */
+  double* x0_dev;              /* [12,N] */
+  void* P0_s_dev;              /* [N,12,12] */
+  uint8_t* ok_dev;             /* [N] */
+} cs_rollout_rts_io;
+int cs_rollout_rts(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_rts_io* rio, void* stream);
 
 /* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
  * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,

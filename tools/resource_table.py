@@ -9,7 +9,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_es > profiles/rollout_es_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_ac > profiles/rollout_ac_resources.txt
     python3 tools/resource_table.py remarks.txt ppo_grad > profiles/ppo_grad_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_ekf > profiles/rollout_ekf_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_ekf > profiles/rollout_ekf_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_rts > profiles/rollout_rts_resources.txt"""
 import re
 import sys
 
@@ -64,7 +65,10 @@ HEADS = {"rollout_mlp": """\
 # ppo_grad_sum_kernel, the sum of the workgroups' partials and the statistics (DESIGN.md section 18).""", "rollout_ekf": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_ekf.hip: the extended Kalman filter
 # rollout_ekf_kernel<TASK, MODE, GYRO> (the covariance, W = A P and the means in lane-private LDS columns: one wavefront
-# per CU; DESIGN.md section 19)."""}
+# per CU; DESIGN.md section 19).""", "rollout_rts": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_rts.hip: the Rauch-Tung-Striebel smoother
+# rollout_rts_kernel<TASK, MODE, GYRO> (two packed covariances, W = A P / the gain and the smoothed mean in lane-private
+# LDS columns: one wavefront per CU; DESIGN.md section 20)."""}
 
 
 def main(path, which="rollout_mlp"):
