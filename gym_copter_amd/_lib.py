@@ -145,6 +145,20 @@ class RolloutRtsIO(C.Structure):
                 ("ok_dev", C.c_void_p)]
 
 
+class RolloutPfIO(C.Structure):
+    """Mirror of `struct cs_rollout_pf_io` (cs_rollout_pf)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_meas", C.c_int32),
+                ("num_particles", C.c_int32), ("nonce", C.c_uint32), ("first_step", C.c_uint32),
+                ("ess_frac", C.c_double), ("H_dev", C.c_void_p), ("r_dev", C.c_void_p), ("Lq_dev", C.c_void_p),
+                ("z_dev", C.c_void_p), ("L0_dev", C.c_void_p), ("part_in_dev", C.c_void_p),
+                ("pstatus_in_dev", C.c_void_p), ("lw_in_dev", C.c_void_p), ("var_dev", C.c_void_p),
+                ("ess_dev", C.c_void_p), ("resampled_dev", C.c_void_p), ("best_dev", C.c_void_p),
+                ("P_dev", C.c_void_p), ("loglik_dev", C.c_void_p), ("ok_dev", C.c_void_p),
+                ("part_out_dev", C.c_void_p), ("pstatus_out_dev", C.c_void_p), ("lw_out_dev", C.c_void_p),
+                ("part_tape_dev", C.c_void_p), ("pstatus_tape_dev", C.c_void_p), ("lw_tape_dev", C.c_void_p),
+                ("wq_tape_dev", C.c_void_p), ("anc_tape_dev", C.c_void_p)]
+
+
 class RolloutMppiIO(C.Structure):
     """Mirror of `struct cs_rollout_mppi_io` (cs_rollout_mppi_costs / cs_rollout_mppi_update)."""
     _fields_ = [("struct_size", C.c_uint32), ("num_samples", C.c_int32), ("noise_stream", C.c_uint32),
@@ -211,6 +225,7 @@ class PpoGradIO(C.Structure):
 
 ES_PAIR_CHUNK, ES_MAX_MEMBERS, ES_MAX_PARAMS = 32, 65536, 1092   # CS_ES_PAIR_CHUNK, CS_ES_MAX_MEMBERS, CS_ES_MAX_PARAMS
 EKF_MAX_MEAS = 12                                            # CS_EKF_MAX_MEAS
+PF_MIN_PARTICLES, PF_MAX_PARTICLES = 64, 1024                # CS_PF_MIN_PARTICLES, CS_PF_MAX_PARTICLES
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
@@ -283,6 +298,7 @@ SYMBOLS = {
     "cs_rollout_feedback_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO), _P]),
     "cs_rollout_ekf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutEkfIO), _P]),
     "cs_rollout_rts": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutRtsIO), _P]),
+    "cs_rollout_pf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutPfIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),

@@ -1,0 +1,218 @@
+"""The bootstrap particle filter's host side: CopterVecEnv.rollout_pf -- one call of
+cs_rollout_pf on the env's cached buffers; vecenv.py binds it to the class -- and pf(), a small streaming driver on it
+for a filter whose measurements arrive a chunk of steps at a time.
+
+    x_p <- step(x_p, a) + Lq eps;     lw_p <- lw_p - 1/2 sum (z_i - H[i] x_p)^2 / r_i;     systematic resampling
+
+The particles, their statuses and their log-weights are carried from call to call on the device; nothing is read by the
+host.  Synthetic measurements to try it on: gym_copter_amd.measure."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+def _torch():
+    import torch
+    return torch
+
+
+# CopterVecEnv.rollout_pf's result: the weighted means x [K,N,12] and variances var [K,N,12] before
+# each step's resampling, ess [K,N], resampled [K,N] bool, best [K,N] int32 (the heaviest particle) and its status
+# [K,N], the weighted covariance after step K P [N,12,12], loglik [N], ok [N] bool; the carried state after step K,
+# post-resample: part [N,P,12], pstatus [N,P], lw [N,P]; and with tape=True (else None) part_tape [K,N,P,12] (the prior
+# particles), pstatus_tape [K,N,P], lw_tape [K,N,P], wq_tape [K,N,P] int32 (the integer weights, <= 2^24) and anc_tape
+# [K,N,P] int32
+PfResult = collections.namedtuple("PfResult", "x var ess resampled best status P loglik ok part pstatus lw part_tape "
+                                              "pstatus_tape lw_tape wq_tape anc_tape")
+
+
+def pf_model(self, H, r, Q):
+    """H [M,12], r [M] and the process noise, checked on the host and kept on the device as (H, r, Lq): Q [12,12]
+    symmetric positive definite is factored (numpy.linalg.cholesky), Q [12] of variances >= 0 gives diag sqrt(Q).  The
+    same values are uploaded once; device tensors are recognised by identity and version."""
+    torch = _torch()
+    tensors = all(isinstance(m, torch.Tensor) for m in (H, r, Q))
+    ident = tuple((id(m), m._version, m.data_ptr()) for m in (H, r, Q)) if tensors else None
+    cache = getattr(self, "_pf_m", None)
+    if ident is not None and cache is not None and cache[2] == ident:
+        return cache[1]
+
+    def host(m, name):
+        a = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m)
+        if a.dtype.kind not in "fiu":
+            raise ValueError("%s must be a real floating-point array, got dtype %s" % (name, a.dtype))
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if not np.isfinite(a).all():
+            raise ValueError("%s must be finite" % name)
+        return a
+    h = host(H, "H")
+    if h.ndim != 2 or h.shape[1] != 12 or not 1 <= h.shape[0] <= _lib.EKF_MAX_MEAS:
+        raise ValueError("H must have shape (M, 12) with 1 <= M <= %d, got %s" % (_lib.EKF_MAX_MEAS, h.shape))
+    rv = host(r, "r")
+    if rv.shape != (h.shape[0],):
+        raise ValueError("r must have shape (%d,) (one variance per row of H), got %s" % (h.shape[0], rv.shape))
+    if not (rv > 0).all():
+        raise ValueError("r must be positive: the measurement variances")
+    q = host(Q, "Q")
+    if q.shape == (12,):
+        if not (q >= 0).all():
+            raise ValueError("Q must be >= 0: the process noise variances")
+        lq = np.diag(np.sqrt(q))
+    elif q.shape == (12, 12):
+        if not np.array_equal(q, q.T):
+            raise ValueError("Q must be symmetric")
+        try:
+            lq = np.linalg.cholesky(q)
+        except np.linalg.LinAlgError:
+            raise ValueError("Q must be positive definite (a Q with zero variances: pass the 12 variances)") from None
+    else:
+        raise ValueError("Q must have shape (12, 12) or (12,), got %s" % (q.shape,))
+    lq = np.ascontiguousarray(lq)
+    key = (h.tobytes(), rv.tobytes(), lq.tobytes())
+    if cache is None or cache[0] != key:
+        cache = (key, [torch.from_numpy(m).to(self.device) for m in (h, rv, lq)])
+    cache = self._pf_m = (cache[0], cache[1], ident, (H, r, Q) if tensors else None)
+    return cache[1]
+
+
+def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce=0, ess_frac=0.5, status0=None,
+               start=None, first_step=1, tape=False, dtype=None):
+    """A bootstrap particle filter over the env step, K steps of propagate / weight / estimate / resample per env in
+    one kernel, `particles` particles per env that stay on the compute unit: the sampling twin of rollout_ekf, for a
+    belief that straddles a branch of the step (touchdown, crash, the motor clip).  The filter's state is the
+    caller's: NO env state is read but the configuration and the vehicle, and none changes.
+
+    actions [K,N,A], z [K,N,M] (NaN = no measurement), H [M,12] and r [M] > 0 are rollout_ekf's.  Q is the process
+    noise added to every particle each step whatever its status: [12,12] symmetric positive definite, or [12]
+    variances (zeros allowed).  The start is either Gaussian -- x0 [12,N], P0 [N,12,12] symmetric positive definite
+    (factored by torch.linalg.cholesky; None: every particle starts at x0), status0 [N] uint8 (default AIRBORNE) --
+    or start=, a previous PfResult (or its (part, pstatus, lw)): the particles carried after its last step.
+    first_step is the global index of this call's first step, so that a run in chunks draws the noise of a single
+    call; nonce selects another noise stream.  particles is a power of two in 64 .. 1024.  The step resamples
+    (systematically, on integer weights) when its effective sample size is below ess_frac * particles.
+
+    Returns PfResult (see its comment).  dtype: torch.float64 (default) or torch.float32 (var, ess, P, loglik: the
+    float64 values rounded).  Not available under action_arith="float32".  Asynchronous on the current stream; the
+    tensors are buffers of this env, overwritten by its next call with the same K, particles, dtype and tape (a
+    `start` that is such a buffer is read before it is overwritten)."""
+    self._check_open()
+    torch = _torch()
+    dtype = self._out_dtype(dtype)
+    Hd, rd, Lqd = self._pf_model(H, r, Q)
+    M = int(Hd.shape[0])
+    P = particles
+    if not isinstance(P, (int, np.integer)) or isinstance(P, bool) or P < _lib.PF_MIN_PARTICLES or \
+            P > _lib.PF_MAX_PARTICLES or P & (P - 1):
+        raise ValueError("particles must be a power of two in %d .. %d, got %r"
+                         % (_lib.PF_MIN_PARTICLES, _lib.PF_MAX_PARTICLES, particles))
+    P = int(P)
+    if not isinstance(nonce, (int, np.integer)) or isinstance(nonce, bool) or not 0 <= int(nonce) < 1 << 32:
+        raise ValueError("nonce must be an int in [0, 2**32), got %r" % (nonce,))
+    nonce = int(nonce)
+    if not isinstance(first_step, (int, np.integer)) or isinstance(first_step, bool) or first_step < 1:
+        raise ValueError("first_step must be an int >= 1, got %r" % (first_step,))
+    if not 0.0 <= float(ess_frac) <= 1.0:
+        raise ValueError("ess_frac must be in [0, 1], got %r" % (ess_frac,))
+    io, K, keep = self._rollout_io(actions, None)
+    if int(first_step) + K - 1 >= 1 << 32:
+        raise ValueError("first_step + K - 1 must be below 2**32")
+    n, dev = self.num_envs, self.device
+    zt = self._ekf_input(z, (K, n, M), "z", keep)
+    pio = _lib.RolloutPfIO()
+    pio.struct_size = C.sizeof(_lib.RolloutPfIO)
+    pio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+    pio.num_meas, pio.num_particles, pio.nonce, pio.first_step = M, P, nonce, int(first_step)
+    pio.ess_frac = float(ess_frac)
+    if (x0 is None) == (start is None):
+        raise ValueError("give exactly one start: x0 (with P0, status0) or start (a previous PfResult)")
+    if start is not None:
+        if P0 is not None or status0 is not None:
+            raise ValueError("P0 and status0 belong to the Gaussian start: leave them out with start=")
+        if isinstance(start, PfResult):
+            start = (start.part, start.pstatus, start.lw)
+        if not isinstance(start, (tuple, list)) or len(start) != 3:
+            raise ValueError("start must be a PfResult or its (part, pstatus, lw)")
+        self._check_tape("rollout_pf", (start[0], "start part", (n, P, 12), torch.float64),
+                         (start[1], "start pstatus", (n, P), torch.uint8),
+                         (start[2], "start lw", (n, P), torch.float64))
+        keep.extend(start)
+        pio.part_in_dev, pio.pstatus_in_dev, pio.lw_in_dev = (t.data_ptr() for t in start)
+    else:
+        xt = self._ekf_input(x0, (12, n), "x0", keep)
+        io.start_x_dev = xt.data_ptr()
+        if status0 is None:
+            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=dev)
+            keep.append(st)
+            io.start_status_dev = st.data_ptr()
+        else:
+            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
+        if P0 is not None:
+            Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
+            try:
+                L0 = torch.linalg.cholesky(Pt).contiguous()
+            except RuntimeError as e:          # torch.linalg.LinAlgError
+                raise ValueError("P0 must be symmetric positive definite: %s" % e) from None
+            keep.append(L0)
+            pio.L0_dev = L0.data_ptr()
+    tape = bool(tape)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+    out = self._rollout_cache(("pf", K, P, dtype, tape), lambda: PfResult(
+        e((K, n, 12), torch.float64), e((K, n, 12), dtype), e((K, n), dtype), e((K, n), torch.bool),
+        e((K, n), torch.int32), e((K, n), torch.uint8), e((n, 12, 12), dtype), e(n, dtype), e(n, torch.bool),
+        e((n, P, 12), torch.float64), e((n, P), torch.uint8), e((n, P), torch.float64),
+        e((K, n, P, 12), torch.float64) if tape else None, e((K, n, P), torch.uint8) if tape else None,
+        e((K, n, P), torch.float64) if tape else None, e((K, n, P), torch.int32) if tape else None,
+        e((K, n, P), torch.int32) if tape else None))
+    io.x_dev, io.status_dev = out.x.data_ptr(), out.status.data_ptr()
+    pio.H_dev, pio.r_dev, pio.Lq_dev, pio.z_dev = Hd.data_ptr(), rd.data_ptr(), Lqd.data_ptr(), zt.data_ptr()
+    pio.var_dev, pio.ess_dev, pio.resampled_dev = out.var.data_ptr(), out.ess.data_ptr(), out.resampled.data_ptr()
+    pio.best_dev, pio.P_dev, pio.loglik_dev, pio.ok_dev = (out.best.data_ptr(), out.P.data_ptr(),
+                                                           out.loglik.data_ptr(), out.ok.data_ptr())
+    pio.part_out_dev, pio.pstatus_out_dev, pio.lw_out_dev = (out.part.data_ptr(), out.pstatus.data_ptr(),
+                                                             out.lw.data_ptr())
+    if tape:
+        pio.part_tape_dev, pio.pstatus_tape_dev = out.part_tape.data_ptr(), out.pstatus_tape.data_ptr()
+        pio.lw_tape_dev, pio.wq_tape_dev = out.lw_tape.data_ptr(), out.wq_tape.data_ptr()
+        pio.anc_tape_dev = out.anc_tape.data_ptr()
+    with torch.cuda.device(self.device):
+        _lib.check(self._lib.cs_rollout_pf(self._ctx, C.byref(io), C.byref(pio), self._stream()))
+    self._keep = keep + [Hd, rd, Lqd]
+    return out
+
+
+def pf(env, actions, z, H, r, Q, x0, P0, particles, nonce=0, ess_frac=0.5, status0=None, chunk=None, tape=True):
+    """Run env.rollout_pf over actions [K,N,A] and z [K,N,M] in chunks of `chunk` steps (None: one call), as a filter
+    whose measurements arrive `chunk` at a time: the particles after each chunk start the next, and first_step tells
+    every chunk where it stands, so that it draws the noise a single call draws.  Returns PfResult with the tapes of all K
+    steps concatenated (the particle tapes with tape=True), P the weighted covariance after the last step, loglik the sum
+    of the chunks' and ok their conjunction -- tensors of their own, not the env's buffers.  Every tape, the carried
+    state, P and ok are bit-identical to the single call's: a chunk boundary rounds nothing (float64 throughout).  loglik
+    equals the single call's to rounding only: it is the sum of the chunks' sums.  The other arguments are rollout_pf's."""
+    import torch
+    K = int(actions.shape[0])
+    chunk = K if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1, got %r" % (chunk,))
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] != K:
+        raise ValueError("z must be a tensor of shape (K, N, M) with K = %d steps" % K)
+    taped = ("x", "var", "ess", "resampled", "best", "status") + \
+        (("part_tape", "pstatus_tape", "lw_tape", "wq_tape", "anc_tape") if tape else ())
+    parts = {name: [] for name in taped}
+    res, loglik, ok = None, None, None
+    for k0 in range(0, K, chunk):
+        kw = dict(particles=particles, nonce=nonce, ess_frac=ess_frac, first_step=k0 + 1, tape=tape)
+        if res is None:
+            res = env.rollout_pf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, x0, P0, status0=status0, **kw)
+        else:
+            res = env.rollout_pf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, start=res, **kw)
+        for name in taped:
+            parts[name].append(getattr(res, name).clone())
+        loglik = res.loglik.clone() if loglik is None else loglik + res.loglik
+        ok = res.ok.clone() if ok is None else ok & res.ok
+    cat = {name: torch.cat(parts[name]) for name in taped}
+    return PfResult(cat["x"], cat["var"], cat["ess"], cat["resampled"], cat["best"], cat["status"], res.P.clone(), loglik,
+                    ok, res.part.clone(), res.pstatus.clone(), res.lw.clone(), cat.get("part_tape"),
+                    cat.get("pstatus_tape"), cat.get("lw_tape"), cat.get("wq_tape"), cat.get("anc_tape"))

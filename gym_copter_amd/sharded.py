@@ -226,6 +226,14 @@ class ShardedCopterVecEnv:
         return self.local.rollout_rts(self._local_rollout_actions(actions), filt, Q, x0, P0, status0=status0, end=end,
                                       tape=tape, dtype=dtype)
 
+    def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce=0, ess_frac=0.5, status0=None,
+                   start=None, first_step=1, tape=False, dtype=None):
+        """CopterVecEnv.rollout_pf of this rank's envs: shard-local (z, x0, P0, status0, start: the local envs').  The
+        noise is keyed by the global env id, so a sharded batch draws what the unsharded one draws."""
+        return self.local.rollout_pf(self._local_rollout_actions(actions), z, H, r, Q, x0=x0, P0=P0,
+                                     particles=particles, nonce=nonce, ess_frac=ess_frac, status0=status0, start=start,
+                                     first_step=first_step, tape=tape, dtype=dtype)
+
     def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
                            stream=0, state=None, knots=None):
         """CopterVecEnv.rollout_mppi_costs of this rank's envs: shard-local (x_ref, state: the local envs').  The noise

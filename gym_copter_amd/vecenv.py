@@ -27,6 +27,7 @@ import numpy as np
 
 from . import _lib
 from . import mlp as _mlp
+from . import pf as _pf
 from .spaces import gymnasium_api
 
 # Envs that hold a device context.  Whatever is still open when the interpreter exits is closed by an exit handler,
@@ -105,6 +106,7 @@ EkfResult = collections.namedtuple("EkfResult", "x x_pred P var nis loglik statu
 # [K,N,12,12] (None with tape=False) and diagonals var [K,N,12], the smoothed starting point x0 [12,N], P0 [N,12,12], and
 # ok [N] bool (every Cholesky pivot positive and finite)
 RtsResult = collections.namedtuple("RtsResult", "x P_tape var x0 P0 ok")
+PfResult = _pf.PfResult      # CopterVecEnv.rollout_pf's result (pf.py)
 # CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
 MppiCosts = collections.namedtuple("MppiCosts", "costs best")
 MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
@@ -1621,6 +1623,12 @@ class CopterVecEnv(_VectorEnvBase):
             _lib.check(self._lib.cs_rollout_ekf(self._ctx, C.byref(io), C.byref(eio), self._stream()))
         self._keep = keep + [Hd, rd, Qd]
         return out
+
+    # -- the bootstrap particle filter over the env step: its host side lives with its streaming
+    #    driver in pf.py and is bound here.  (The list of guarded entry points in tests/test_gpu_output_bounds.py is
+    #    read from this class's `def`s; rollout_pf's guarded-output test is in tests/test_gpu_rollout_pf.py.) --------
+    _pf_model = _pf.pf_model
+    rollout_pf = _pf.rollout_pf
 
     # -- the Rauch-Tung-Striebel smoother over the filter's tapes --------
     def _rts_Q(self, Q):

@@ -41,6 +41,8 @@
  *                            the step, K steps per env           counterpart: a state estimator)
  *   cs_rollout_rts           a Rauch-Tung-Striebel smoother     the same Jacobian at the filter's points (no upstream
  *                            over that filter's tapes            counterpart: a fixed-interval smoother)
+ *   cs_rollout_pf            a bootstrap particle filter over   the rollout lines above, per particle (no upstream
+ *                            the step, K steps per env           counterpart: a sampling state estimator)
  *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
  *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
  *   cs_rollout_mppi_update   their cost-weighted average         (the same)
@@ -943,6 +945,101 @@ typedef struct cs_rollout_rts_io {
   uint8_t* ok_dev;             /* [N] */
 } cs_rollout_rts_io;
 int cs_rollout_rts(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_rts_io* rio, void* stream);
+
+/* A bootstrap particle filter over the env step, on the device: K steps of propagate / weight /
+ * estimate / resample per env in one call, P particles per env that never leave the compute unit.  The sampling twin of
+ * cs_rollout_ekf: a belief that straddles a branch of the step (touchdown, crash, the motor clip) is represented by
+ * particles on both sides of it.  The filter's state is the CALLER's: no env state is read except the context's
+ * constants and vehicle table, and none is written.  The measurement model is cs_rollout_ekf's, z = H x + e with
+ * e ~ N(0, diag(r)); the process noise is additive, w = Lq eps with Lq [12,12] lower triangular (Lq Lq^T = Q; rows of
+ * zeros allowed) and shared.  Everything is float64 without contraction unless stated.
+ *
+ * P = num_particles is a power of two in 64 .. CS_PF_MAX_PARTICLES.  From io: num_steps = K, actions_dev [K,N,A]; the
+ * reward, flag, cotangent and gradient pointers, start_force_dev and start_prev_shaping_dev must be NULL.
+ *
+ * Start, one of two forms (both or neither is refused):
+ *   Gaussian  io->start_x_dev [12,N] = xhat_0, io->start_status_dev [N], L0_dev [N,12,12] lower triangular (NULL: every
+ *             particle is xhat_0): particle p = xhat_0 + L0 eps(k = 0, p), status = start_status, lw = -ln P
+ *   carried   part_in_dev [N,P,12], pstatus_in_dev [N,P], lw_in_dev [N,P] (io->start_x_dev, io->start_status_dev and
+ *             L0_dev NULL): what a previous call's part_out_dev, pstatus_out_dev and lw_out_dev hold.  An env's inputs
+ *             are read before any of its outputs is written, so the three may be the same buffers as the outputs.
+ * first_step >= 1 is the global index of the call's first step: a run in chunks draws what a single call draws.
+ *
+ * Noise (pf_noise.h).  eps of (seed, global env id g, nonce, step k, particle p, slot j) is one Philox2x32-10 call with
+ * counter = (g, nonce) and key = key_pf + ((k * 1024 + p) * 16 + j) mod 2^32, key_pf = the low half of the fifth
+ * splitmix64 of the seed; slots 0 .. 11 are the state components (the Irwin-Hall draw of cs_rollout_mppi: float32, mean
+ * 0, variance 1 - 2^-32, support +-3.46), slot 12 at p = 0 is the step's resampling word.  noise_i = sum_{j <= i}
+ * Lq[i][j] (double)eps_j, j ascending, one multiply and one add per term.  A pure function of its arguments: it does not
+ * depend on P, the batch, the sharding or the chunking.
+ *
+ * Per step k = first_step .. first_step + K - 1 and env:
+ *   propagate  every particle goes through the physics of the step from its own (x, status) under the step's action,
+ *              exactly as cs_rollout_ekf's mean does (clip, motor law, the env's vehicle, `substeps` calls, the status
+ *              machine, skipped for a LANDED particle; no storage rounding, no pending perturbation); then x += noise
+ *              for EVERY particle whatever its status -- as cs_rollout_ekf adds Q whatever the branch: Q models what
+ *              the step does not, and a caller who wants a landed vehicle to stay put zeroes the rows of Lq it needs.
+ *   weight     for the present (not NaN) z_i in order: nu = z_i - H[i] x, ll -= 1/2 nu^2 / r_i; lw' = lw + ll, a
+ *              non-finite lw' counts as -inf.  m = max lw', e_p = exp(lw'_p - m), eta = sum e_p;
+ *              lw <- lw' - (m + ln eta), loglik += m + ln eta - 1/2 sum_present ln(2 pi r_i).  A step with no z present
+ *              leaves lw untouched, bit for bit, and adds 0.  If no particle has a finite lw' the env's ok is 0,
+ *              lw <- -ln P, every e_p counts as 1 and loglik is left alone.
+ *   integer    wq_p = (uint32) rint(e_p 2^24): the heaviest particle has exactly 2^24.  Everything below uses wq in exact
+ *   weights    64-bit integer arithmetic: S1 = sum wq, S2 = sum wq^2, ess = (double)S1 (double)S1 / (double)S2; the step
+ *              resamples iff (double)S1 (double)S1 < (ess_frac P) (double)S2.
+ *   estimate   (before resampling)  xhat = sum wq_p x_p / S1, var = sum wq_p (x_p - xhat)^2 / S1, particles of weight 0
+ *              left out; best = the lowest index of the largest wq, status = that particle's.  The order of these
+ *              sums is fixed (no atomics): the same inputs give the same bits on every call.
+ *   resample   systematic: u = the top 16 bits of the step's resampling word, C_p the inclusive cumulative sum of wq;
+ *              the ancestor of slot j is the smallest p with C_p (P << 16) > ((j << 16) + u) S1 (both sides < 2^61).
+ *              Particle j takes its ancestor's state and status, lw <- -ln P.  Without a resample the ancestors are the
+ *              identity.
+ * Outputs, each may be NULL; var, ess, P and loglik in out_dtype (CS_JAC_F64, or CS_JAC_F32: the float64 values rounded):
+ *   io->x_dev [K,N,12] float64 xhat     io->status_dev [K,N]        var_dev [K,N,12]         ess_dev [K,N]
+ *   resampled_dev [K,N] uint8           best_dev [K,N] int32        P_dev [N,12,12] the weighted covariance after step
+ *   loglik_dev [N]                      ok_dev [N] uint8            K, before its resampling (symmetric; diagonal = var)
+ *   part_out_dev [N,P,12], pstatus_out_dev [N,P], lw_out_dev [N,P]: the state after step K, post-resample
+ * and the tapes:
+ *   part_tape_dev [K,N,P,12] the prior particles after the noise    pstatus_tape_dev [K,N,P] their statuses
+ *   lw_tape_dev [K,N,P] normalised, before resampling               wq_tape_dev [K,N,P] uint32
+ *   anc_tape_dev [K,N,P] int32
+ * Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32.  Asynchronous on `stream`; pio->struct_size must be
+ * sizeof(cs_rollout_pf_io) (else CS_ERR_ABI, checked first); both blocks are checked before the context.  r_dev must be
+ * finite and > 0 (the caller's to guarantee; gym_copter_amd checks it).  Every array is aligned to its element size. */
+#define CS_PF_MIN_PARTICLES 64
+#define CS_PF_MAX_PARTICLES 1024
+typedef struct cs_rollout_pf_io {
+  uint32_t struct_size;            /* sizeof(cs_rollout_pf_io) */
+  uint32_t out_dtype;              /* CS_JAC_F64 / CS_JAC_F32: var_dev, ess_dev, P_dev, loglik_dev */
+  int32_t num_meas;                /* M, 1 .. CS_EKF_MAX_MEAS */
+  int32_t num_particles;           /* P, a power of two in CS_PF_MIN_PARTICLES .. CS_PF_MAX_PARTICLES */
+  uint32_t nonce;                  /* the second counter word of every draw */
+  uint32_t first_step;             /* >= 1: the global index of the call's first step */
+  double ess_frac;                 /* in [0, 1]: resample when ess < ess_frac P */
+  const double* H_dev;             /* [M,12], required */
+  const double* r_dev;             /* [M], required */
+  const double* Lq_dev;            /* [12,12] lower triangular, required */
+  const double* z_dev;             /* [K,N,M], required */
+  const double* L0_dev;            /* [N,12,12] lower triangular, or NULL (Gaussian start) */
+  const double* part_in_dev;       /* [N,P,12] (carried start) */
+  const uint8_t* pstatus_in_dev;   /* [N,P] */
+  const double* lw_in_dev;         /* [N,P] */
+  void* var_dev;                   /* [K,N,12] */
+  void* ess_dev;                   /* [K,N] */
+  uint8_t* resampled_dev;          /* [K,N] */
+  int32_t* best_dev;               /* [K,N] */
+  void* P_dev;                     /* [N,12,12] */
+  void* loglik_dev;                /* [N] */
+  uint8_t* ok_dev;                 /* [N] */
+  double* part_out_dev;            /* [N,P,12] */
+  uint8_t* pstatus_out_dev;        /* [N,P] */
+  double* lw_out_dev;              /* [N,P] */
+  double* part_tape_dev;           /* [K,N,P,12] */
+  uint8_t* pstatus_tape_dev;       /* [K,N,P] */
+  double* lw_tape_dev;             /* [K,N,P] */
+  uint32_t* wq_tape_dev;           /* [K,N,P] */
+  int32_t* anc_tape_dev;           /* [K,N,P] */
+} cs_rollout_pf_io;
+int cs_rollout_pf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_pf_io* pio, void* stream);
 
 /* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
  * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,

@@ -10,7 +10,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_ac > profiles/rollout_ac_resources.txt
     python3 tools/resource_table.py remarks.txt ppo_grad > profiles/ppo_grad_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_ekf > profiles/rollout_ekf_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_rts > profiles/rollout_rts_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_rts > profiles/rollout_rts_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_pf > profiles/rollout_pf_resources.txt"""
 import re
 import sys
 
@@ -68,7 +69,11 @@ HEADS = {"rollout_mlp": """\
 # per CU; DESIGN.md section 19).""", "rollout_rts": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_rts.hip: the Rauch-Tung-Striebel smoother
 # rollout_rts_kernel<TASK, MODE, GYRO> (two packed covariances, W = A P / the gain and the smoothed mean in lane-private
-# LDS columns: one wavefront per CU; DESIGN.md section 20)."""}
+# LDS columns: one wavefront per CU; DESIGN.md section 20).""", "rollout_pf": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_pf.hip: the bootstrap particle filter
+# rollout_pf_kernel<TASK, MODE, GYRO> (one workgroup of min(P, 256) lanes per env; the particles, their weights and the
+# cumulative weights in dynamic LDS, 124 P + 3 072 bytes per workgroup -- not part of the static figure below; DESIGN.md
+# section 21)."""}
 
 
 def main(path, which="rollout_mlp"):
