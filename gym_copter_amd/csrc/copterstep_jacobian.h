@@ -2,6 +2,8 @@
 // copterstep_jacobian.hip (cs_step_jacobian and its kernels).  Not installed; the public ABI is include/copterstep.h.
 #pragma once
 
+#include <initializer_list>
+
 #include "copterstep_internal.h"
 
 namespace cs {
@@ -23,6 +25,25 @@ uint64_t context_seed(const cs_ctx* ctx);
 // (copterstep_rollout_grad.hip) the cs_rollout_io checks of cs_rollout_states / cs_rollout_vjp (vjp: the backward's),
 // made before the context; also those of cs_rollout_mlp_* (copterstep_rollout_mlp.hip)
 int check_rollout_io(const cs_rollout_io* io, const char* who, bool vjp);
+
+// (copterstep_rollout_grad.hip) what cs_rollout_ekf, cs_rollout_rts and cs_rollout_pf check alike, in two calls because
+// their own checks stand between.  Their second block opens with uint32_t struct_size, out_dtype.
+struct FilterExt {
+  const char* name;   // the argument's name ("eio") and its type's, as the messages spell them
+  const char* type;
+  const void* block;
+  size_t size;        // sizeof the type
+};
+// After check_rollout_io: the block is there and of its size; `start_missing` (the entry point's text if a start pointer
+// it requires is NULL, else nullptr); no start force or shaping; `must_be_null` (its text if a pointer of io it forbids
+// is set, else nullptr); out_dtype is known.
+int check_filter_io(const cs_rollout_io* io, const char* who, const FilterExt& ext, const char* start_missing,
+                    const char* must_be_null);
+// After the entry point's own checks: the float64 arrays are 8-B aligned, the out_dtype arrays to their element, the
+// 32-bit ones (`w32_names` in the message) to 4 B; then enter_context, and the float32 motor law is refused.
+int enter_filter_context(cs_ctx* ctx, const char* who, void* stream, uint32_t out_dtype,
+                         std::initializer_list<const void*> f64s, std::initializer_list<const void*> outs,
+                         std::initializer_list<const void*> w32s, const char* w32_names, ContextView* out);
 
 constexpr int kVehicleRows = 12;  // cs_set_vehicle_params' raw rows: B, D, M, L, Ix, Iy, Iz, Jr, maxrpm, G, rho, C_L
 

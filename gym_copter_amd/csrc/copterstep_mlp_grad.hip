@@ -19,6 +19,8 @@
 // the sums are explicit fma chains (the arithmetic include/copterstep.h documents), whatever the compiler would contract
 #pragma clang fp contract(off)
 
+#include "wave_sync.h"
+
 namespace cs {
 namespace {
 
@@ -27,12 +29,6 @@ constexpr int kGradBlock = 64 * kGradWaves;
 constexpr int kGradChunk = 8;                    // accumulators reduced per pass through the LDS
 constexpr uint32_t kGradMaxGroups = 1024;        // workgroups (= partials) at most: 4 per CU
 constexpr uint32_t kGradMaxParams = CS_MLP_MAX_HIDDEN * (12 + 1) + 4 * (CS_MLP_MAX_HIDDEN + 1);  // Hover3D, H = 64
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // HP: 0 = the linear policy (one row per lane), else the hidden width rounded up (8, 16, 32 or 64 lanes per row)
 template <int OBS, int A, int HP>

@@ -22,6 +22,8 @@
 // the sums are explicit fma chains (the arithmetic include/copterstep.h documents), whatever the compiler would contract
 #pragma clang fp contract(off)
 
+#include "wave_sync.h"
+
 namespace cs {
 namespace {
 
@@ -59,12 +61,6 @@ struct PpoArgs {
   uint32_t prep_groups, normalize, tiles_per_group;
   uint32_t stride, offset, ls_offset, scal_offset;  // a partial's length and this head's columns in it
 };
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the row of sample s, or -1: past the minibatch's end, or an index outside [0, R) -- such a sample is never read
 __device__ __forceinline__ int64_t sample_row(const int64_t* __restrict__ index, const int64_t row_base,

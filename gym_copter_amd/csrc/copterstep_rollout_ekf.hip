@@ -7,9 +7,8 @@
 //
 // One lane per env on the tile layout of the step kernels (tile t -> workgroup t).  Per step:
 //   mean        the physics of rollout_step (clip, motor law, physics_substeps) from the filter's own mean and status
-//   covariance  P- = A P A^T + Q through jacobian_block (jacobian_tangents.h) with zero wrench tangents -- the actions
-//               are known -- in two passes of 6 blocks of 2 directions: the columns of P give W = A P, the rows of W give
-//               A W^T = (A P A^T)^T, whose upper triangle is kept
+//   covariance  P- = A P A^T + Q by cov_predict (cov_tile.h: jacobian_block with zero wrench tangents -- the actions are
+//               known -- in two passes of 6 blocks of 2 directions), the function the smoother calls for the same prior
 //   update      M sequential scalar updates (ekf_update.h)
 // P (78 rows, packed upper triangle), W (144 rows and one row of stage padding behind it), the mean at the start of the
 // step (12 rows) and the prior / posterior mean (12 rows) live in lane-private LDS columns (element j of a lane at
@@ -35,54 +34,20 @@
 #include "rollout_step.h"
 #include "rollout_sweep.h"
 #include "ekf_update.h"
+#include "cov_tile.h"
 #include "dev_launch.h"
 
 namespace cs {
 namespace {
 
 // the lane's LDS rows (row j at [j * kBlock]): the packed upper triangle of P, W = A P (W[i][c] at i * 12 + c) with one
-// row of padding behind it (the stage of the 12 x 12 stores: a lane's matrix row-major at stride 145), the mean at the
-// start of the step (the Jacobian's point) and the prior / posterior mean
+// row of padding behind it (the stage of the 12 x 12 stores, cov_tile.h), the mean at the start of the step (the
+// Jacobian's point) and the prior / posterior mean
 constexpr int kRowW = kEkfSym;
-constexpr int kStageStride = 145;  // (odd: the lanes' stage writes fall into different banks)
 constexpr int kRowX0 = kRowW + kStageStride;
 constexpr int kRowX = kRowX0 + 12;
 constexpr int kEkfRows = kRowX + 12;
-static_assert(kStageStride * kWave <= (kRowX0 - kRowW) * kBlock, "the stage fits W and its padding row");
 static_assert(kEkfRows * kBlock * sizeof(double) <= 160 * 1024, "the LDS of one CU");
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void store_out(void* dst, size_t at, double v, uint32_t f32) {
-  if (f32)
-    reinterpret_cast<float*>(dst)[at] = (float)v;
-  else
-    reinterpret_cast<double*>(dst)[at] = v;
-}
-
-// The wavefront's staged matrices (lane l's at stage[l * kStageStride ..], row-major) to rows `at` .. of an [.., N, 144]
-// output: a whole wavefront's 64 x 144 values are one contiguous run, read back linearly so that every store instruction
-// writes whole lines; a partial wavefront lane by lane.
-__device__ __forceinline__ void store_matrix(void* dst, size_t at, const double* stage, const RowOut& ro, uint32_t f32) {
-  if (ro.whole) {
-    const size_t base = (at + ro.env0) * 144;
-#pragma clang loop unroll(disable)
-    for (int v = 0; v < 144; ++v) {
-      const int el = v * kWave + ro.lane;
-      const int ln = el / 144, idx = el - ln * 144;
-      store_out(dst, base + el, stage[ln * kStageStride + idx], f32);
-    }
-  } else if (ro.valid) {
-    const size_t base = (at + ro.i) * 144;
-    const double* mine = stage + ro.lane * kStageStride;
-#pragma clang loop unroll(disable)
-    for (int v = 0; v < 144; ++v) store_out(dst, base + v, mine[v], f32);
-  }
-}
 
 template <int TASK, int MODE, bool GYRO>
 __global__ __launch_bounds__(kBlock) void rollout_ekf_kernel(const DevConst c, const DevState s, const cs_rollout_io io,
@@ -127,17 +92,8 @@ __global__ __launch_bounds__(kBlock) void rollout_ekf_kernel(const DevConst c, c
   for (int k = 0; k < K; ++k) {
     const size_t row = (size_t)k * n;  // 64-bit: K x N x 144 doubles pass 4 GiB at 1 M envs
     const float4 act = load_action_at<TASK>(io.actions_dev + (row + ii) * A);
-    const float araw[4] = {act.x, act.y, act.z, act.w};
-    float mf[4];
-    bool clipped = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      mf[j] = clip01(araw[j]);
-      clipped |= !(araw[j] >= 0.f && araw[j] <= 1.f);
-    }
-    Wrench w;
-    w.bz = thrust_model(q, mf[0], mf[1], mf[2], mf[3]);
-    torque_model(q, mf[0], mf[1], mf[2], mf[3], w);
+    bool clipped;
+    const Wrench w = step_wrench(q, act, &clipped);
     const int fs0 = fs;
     uint32_t bits = (fs0 == CS_STATUS_LANDED ? (uint32_t)kJacLanded : 0u) | (clipped ? (uint32_t)kJacClipped : 0u);
 
@@ -158,45 +114,8 @@ __global__ __launch_bounds__(kBlock) void rollout_ekf_kernel(const DevConst c, c
       for (int j = 0; j < 12; ++j) X[j * kBlock] = x[j];
     }
 
-    // ---- the covariance: 12 blocks of 2 directions through the tangents of the step, the actions known ----
-    const Wrench zero{0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma clang loop unroll(disable)
-    for (int b = 0; b < 12; ++b) {
-      const bool second = b >= 6;  // pass 1: columns 2 b', 2 b' + 1 of P -> those of W; pass 2: rows of W -> columns of P-
-      const int c0 = (second ? b - 6 : b) * kJacDirs;
-      JacPoint pt;
-#pragma unroll
-      for (int j = 0; j < 12; ++j) pt.x[j] = X0[j * kBlock];
-      pt.fs = fs0;
-      pt.active = fs0 != CS_STATUS_LANDED;
-      pt.px = pt.py = pt.pz = -0.0;
-      double v[kJacDirs][12];
-      const Wrench dw[kJacDirs] = {zero, zero};
-#pragma unroll
-      for (int d = 0; d < kJacDirs; ++d) {
-#pragma unroll
-        for (int j = 0; j < 12; ++j)
-          v[d][j] = second ? W[((c0 + d) * 12 + j) * kBlock] : P[ekf_sym_at(j, c0 + d) * kBlock];
-      }
-      double xn[12];
-      bits |= jacobian_block<FULL, GYRO>(c, q, w, dw, pt, xn, v);
-      if (!second) {
-#pragma unroll
-        for (int d = 0; d < kJacDirs; ++d) {
-#pragma unroll
-          for (int j = 0; j < 12; ++j) W[(j * 12 + c0 + d) * kBlock] = v[d][j];
-        }
-      } else {  // column c0 + d of P- above its diagonal (every column of P was read in pass 1), plus Q
-#pragma unroll
-        for (int d = 0; d < kJacDirs; ++d) {
-          const int col = c0 + d;
-#pragma unroll
-          for (int j = 0; j < 12; ++j) {
-            if (j <= col) P[(col * (col + 1) / 2 + j) * kBlock] = v[d][j] + e.Q_dev[j * 12 + col];
-          }
-        }
-      }
-    }
+    // ---- the covariance: P- = A P A^T + Q at the mean the step started from ----
+    bits |= cov_predict<FULL, GYRO>(c, q, w, fs0, X0, kBlock, P, W, e.Q_dev);
 
     // ---- the prior mean out (W is dead: its rows are the stage) ----
     {
@@ -224,12 +143,7 @@ __global__ __launch_bounds__(kBlock) void rollout_ekf_kernel(const DevConst c, c
     }
     const bool last = k == K - 1;
     if (e.P_tape_dev != nullptr || (last && e.P_dev != nullptr)) {
-      double* const mine = stage + lane * kStageStride;
-#pragma clang loop unroll(disable)
-      for (int a = 0; a < 12; ++a) {
-#pragma clang loop unroll(disable)
-        for (int bb = 0; bb < 12; ++bb) mine[a * 12 + bb] = P[ekf_sym_at(a, bb) * kBlock];
-      }
+      stage_triangle(stage + lane * kStageStride, P);
       wave_sync();
       if (e.P_tape_dev != nullptr) store_matrix(e.P_tape_dev, row, stage, ro, f32);
       if (last && e.P_dev != nullptr) store_matrix(e.P_dev, 0, stage, ro, f32);
@@ -268,8 +182,6 @@ hipError_t launch_rollout_ekf(int task, int mode, const DevConst& c, const DevSt
   CS_DISPATCH(ekf_t, c, s, io, e, stream)
 }
 
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 }  // namespace cs
 
@@ -277,39 +189,26 @@ extern "C" int cs_rollout_ekf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rol
   using cs::report_error;
   const char* who = "cs_rollout_ekf";
   if (int rc_ = cs::check_rollout_io(io, who, false)) return rc_;
-  if (eio == nullptr) return report_error(CS_ERR_ARG, "cs_rollout_ekf: null eio");
-  if (eio->struct_size != sizeof(cs_rollout_ekf_io))
-    return report_error(CS_ERR_ABI, ("cs_rollout_ekf: eio->struct_size " + std::to_string(eio->struct_size) + " != " +
-                                     std::to_string(sizeof(cs_rollout_ekf_io)) + " (sizeof(cs_rollout_ekf_io))").c_str());
-  if (io->start_x_dev == nullptr || io->start_status_dev == nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: start_x_dev (the mean) and start_status_dev are required");
-  if (io->start_force_dev != nullptr || io->start_prev_shaping_dev != nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: start_force_dev and start_prev_shaping_dev must be NULL");
-  if (io->reward_dev != nullptr || io->terminated_dev != nullptr || io->truncated_dev != nullptr ||
-      io->gx_dev != nullptr || io->gr_dev != nullptr || io->g_actions_dev != nullptr || io->g_x0_dev != nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: the reward, flag, cotangent and gradient pointers must be NULL");
-  if (eio->out_dtype != CS_JAC_F64 && eio->out_dtype != CS_JAC_F32)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: unknown eio->out_dtype (CS_JAC_F64 or CS_JAC_F32)");
+  const bool no_start = io->start_x_dev == nullptr || io->start_status_dev == nullptr;
+  const bool extra = io->reward_dev != nullptr || io->terminated_dev != nullptr || io->truncated_dev != nullptr ||
+                     io->gx_dev != nullptr || io->gr_dev != nullptr || io->g_actions_dev != nullptr ||
+                     io->g_x0_dev != nullptr;
+  if (int rc_ = cs::check_filter_io(io, who, {"eio", "cs_rollout_ekf_io", eio, sizeof(cs_rollout_ekf_io)},
+                                    no_start ? "start_x_dev (the mean) and start_status_dev are required" : nullptr,
+                                    extra ? "the reward, flag, cotangent and gradient pointers must be NULL" : nullptr))
+    return rc_;
   if (eio->num_meas < 1 || eio->num_meas > CS_EKF_MAX_MEAS)
     return report_error(CS_ERR_ARG, "cs_rollout_ekf: num_meas must be 1 .. CS_EKF_MAX_MEAS");
   if (eio->H_dev == nullptr || eio->r_dev == nullptr || eio->Q_dev == nullptr || eio->P0_dev == nullptr ||
       eio->z_dev == nullptr)
     return report_error(CS_ERR_ARG, "cs_rollout_ekf: H_dev, r_dev, Q_dev, P0_dev and z_dev are required");
-  const void* f64s[] = {io->start_x_dev, io->x_dev, eio->H_dev, eio->r_dev, eio->Q_dev, eio->P0_dev, eio->z_dev,
-                        eio->x_pred_dev};
-  for (const void* p : f64s)
-    if (!cs::aligned8(p)) return report_error(CS_ERR_ARG, "cs_rollout_ekf: a float64 array is not 8-B aligned");
-  const uintptr_t out_mask = eio->out_dtype == CS_JAC_F32 ? 3u : 7u;
-  const void* outs[] = {eio->P_dev, eio->P_tape_dev, eio->var_dev, eio->nis_dev, eio->loglik_dev};
-  for (const void* p : outs)
-    if ((reinterpret_cast<uintptr_t>(p) & out_mask) != 0)
-      return report_error(CS_ERR_ARG, "cs_rollout_ekf: an output array is not aligned to its element size");
-  if ((reinterpret_cast<uintptr_t>(io->actions_dev) & 3u) != 0)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: actions_dev is not 4-B aligned");
   cs::ContextView v;
-  if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
-  if (v.c->act_f32)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: not available with the float32 motor model (action_arith)");
+  if (int rc_ = cs::enter_filter_context(
+          ctx, who, stream, eio->out_dtype,
+          {io->start_x_dev, io->x_dev, eio->H_dev, eio->r_dev, eio->Q_dev, eio->P0_dev, eio->z_dev, eio->x_pred_dev},
+          {eio->P_dev, eio->P_tape_dev, eio->var_dev, eio->nis_dev, eio->loglik_dev}, {io->actions_dev}, "actions_dev",
+          &v))
+    return rc_;
   const hipError_t e = cs::launch_rollout_ekf(v.task, v.mode, *v.c, *v.s, *io, *eio, (hipStream_t)stream);
   if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_ekf: kernel launch");
   return CS_OK;

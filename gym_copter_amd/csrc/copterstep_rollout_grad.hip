@@ -13,6 +13,7 @@
 // step's primal is recomputed from the caller's tape (the forward's x and status rows), the substep start states from
 // the step's start (O(substeps^2) calls).  Both loops are rollout_sweep.h's, shared with the closed-loop rollouts;
 // the kernels here are wrappers that pick the open-loop actions and the sweep's extension.  DESIGN.md sections 10, 11.
+#include <cstring>
 #include <string>
 
 #include "copterstep_jacobian.h"
@@ -264,6 +265,44 @@ int check_rollout_io(const cs_rollout_io* io, const char* who, bool vjp) {
     if (io->x_dev == nullptr || io->status_dev == nullptr)
       return report_error(CS_ERR_ARG, (w + ": the tape (x_dev and status_dev of cs_rollout_states) is required").c_str());
   }
+  return CS_OK;
+}
+
+// the filter family's second block and what its entry points ask of io alike, in the order they always checked it
+int check_filter_io(const cs_rollout_io* io, const char* who, const FilterExt& ext, const char* start_missing,
+                    const char* must_be_null) {
+  const std::string w(who), name(ext.name);
+  if (ext.block == nullptr) return report_error(CS_ERR_ARG, (w + ": null " + name).c_str());
+  uint32_t struct_size, out_dtype;  // the block's first two words (the second is read once the first says it is there)
+  std::memcpy(&struct_size, ext.block, sizeof(uint32_t));
+  if (struct_size != ext.size)
+    return report_error(CS_ERR_ABI, (w + ": " + name + "->struct_size " + std::to_string(struct_size) + " != " +
+                                     std::to_string(ext.size) + " (sizeof(" + ext.type + "))").c_str());
+  if (start_missing != nullptr) return report_error(CS_ERR_ARG, (w + ": " + start_missing).c_str());
+  if (io->start_force_dev != nullptr || io->start_prev_shaping_dev != nullptr)
+    return report_error(CS_ERR_ARG, (w + ": start_force_dev and start_prev_shaping_dev must be NULL").c_str());
+  if (must_be_null != nullptr) return report_error(CS_ERR_ARG, (w + ": " + must_be_null).c_str());
+  std::memcpy(&out_dtype, static_cast<const char*>(ext.block) + sizeof(uint32_t), sizeof(uint32_t));
+  if (out_dtype != CS_JAC_F64 && out_dtype != CS_JAC_F32)
+    return report_error(CS_ERR_ARG, (w + ": unknown " + name + "->out_dtype (CS_JAC_F64 or CS_JAC_F32)").c_str());
+  return CS_OK;
+}
+
+int enter_filter_context(cs_ctx* ctx, const char* who, void* stream, uint32_t out_dtype,
+                         std::initializer_list<const void*> f64s, std::initializer_list<const void*> outs,
+                         std::initializer_list<const void*> w32s, const char* w32_names, ContextView* out) {
+  const std::string w(who);
+  const auto aligned = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; };
+  for (const void* p : f64s)
+    if (!aligned(p, 7u)) return report_error(CS_ERR_ARG, (w + ": a float64 array is not 8-B aligned").c_str());
+  for (const void* p : outs)
+    if (!aligned(p, out_dtype == CS_JAC_F32 ? 3u : 7u))
+      return report_error(CS_ERR_ARG, (w + ": an output array is not aligned to its element size").c_str());
+  for (const void* p : w32s)
+    if (!aligned(p, 3u)) return report_error(CS_ERR_ARG, (w + ": " + w32_names + " is not 4-B aligned").c_str());
+  if (int rc_ = enter_context(ctx, who, stream, out)) return rc_;
+  if (out->c->act_f32)
+    return report_error(CS_ERR_ARG, (w + ": not available with the float32 motor model (action_arith)").c_str());
   return CS_OK;
 }
 

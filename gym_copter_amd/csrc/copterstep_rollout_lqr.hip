@@ -34,6 +34,7 @@
 #include "rollout_step.h"
 #include "rollout_sweep.h"
 #include "lqr_solve.h"
+#include "cov_tile.h"
 #include "dev_launch.h"
 
 namespace cs {
@@ -60,9 +61,8 @@ struct LqrArgs {
 // j (j + 1) / 2 + i), W = A^T V (W[i][c] at i * 12 + c), B^T V then Qux (row a, column c at a * 12 + c), B^T V B, the
 // vector s / v / Qx, and Qu.  After the last call of a step W is dead: the gains (row-major per lane, stride 12 A + 1:
 // what the wavefront then reads linearly for its stores), G = Quu K + Qux and d are staged in its rows.
-constexpr int kSymRows = 78;
-constexpr int lqr_rows(int A) { return kSymRows + 144 + 12 * A + A * A + 12 + A; }
-constexpr int kRowW = kSymRows;
+constexpr int lqr_rows(int A) { return kEkfSym + 144 + 12 * A + A * A + 12 + A; }
+constexpr int kRowW = kEkfSym;
 constexpr int kRowBV = kRowW + 144;
 constexpr int lqr_row_quu(int A) { return kRowBV + 12 * A; }
 constexpr int lqr_row_sv(int A) { return lqr_row_quu(A) + A * A; }
@@ -70,25 +70,6 @@ constexpr int lqr_row_qu(int A) { return lqr_row_sv(A) + 12; }
 constexpr int kRowG = kRowW + 64;    // (the gain stage takes 12 A + 1 <= 49 rows of W's 144)
 constexpr int kRowD = kRowW + 128;   // (A <= 4 doubles per lane: [lane * A + a])
 static_assert(lqr_rows(4) * kBlock * sizeof(double) <= 160 * 1024, "the LDS of one CU");
-
-__device__ __forceinline__ int sym_at(int i, int j) { return i <= j ? j * (j + 1) / 2 + i : i * (i + 1) / 2 + j; }
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-template <class OUT>
-__device__ __forceinline__ void store_out(void* dst, size_t at, double v) {
-  reinterpret_cast<OUT*>(dst)[at] = (OUT)v;
-}
-__device__ __forceinline__ void store_out(void* dst, size_t at, double v, uint32_t f32) {
-  if (f32)
-    store_out<float>(dst, at, v);
-  else
-    store_out<double>(dst, at, v);
-}
 
 // One step of the recursion: on entry the lane's S, s are those after the step (0 beyond the horizon), on exit those
 // before it; its gains go out to row `row` (= step index x N) of K_dev, d_dev.  P = the lane's LDS column, wbase = the
@@ -135,7 +116,7 @@ __device__ __forceinline__ void lqr_step(const DevConst& c, const Coef& q, const
     } else if (call < kEndV) {  // column call - 1 of V
       const int col = call - 1;
 #pragma unroll
-      for (int i = 0; i < 12; ++i) lam[i] = S[sym_at(i, col) * kBlock];
+      for (int i = 0; i < 12; ++i) lam[i] = S[ekf_sym_at(i, col) * kBlock];
     } else if (call < kEndB) {  // column a of V B = row a of B^T V
       const int a = call - kEndV;
 #pragma unroll
@@ -313,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void rollout_lqr_kernel(const DevConst c, c
   double* const P = lds + lane;
   double* const SV = P + lqr_row_sv(A) * kBlock;
 #pragma clang loop unroll(disable)
-  for (int j = 0; j < kSymRows; ++j) P[j * kBlock] = 0.0;
+  for (int j = 0; j < kEkfSym; ++j) P[j * kBlock] = 0.0;
 #pragma unroll
   for (int j = 0; j < 12; ++j) SV[j * kBlock] = 0.0;
   double dv1 = 0.0, dv2 = 0.0;
@@ -377,7 +358,7 @@ __global__ __launch_bounds__(kBlock) void rollout_lqr_kernel(const DevConst c, c
 #pragma clang loop unroll(disable)
       for (int a = 0; a < 12; ++a) {
 #pragma clang loop unroll(disable)
-        for (int b = 0; b < 12; ++b) store_out(l.S0, (size_t)i * 144 + a * 12 + b, P[sym_at(a, b) * kBlock], l.f32);
+        for (int b = 0; b < 12; ++b) store_out(l.S0, (size_t)i * 144 + a * 12 + b, P[ekf_sym_at(a, b) * kBlock], l.f32);
       }
     }
     if (l.s0 != nullptr) {

@@ -34,6 +34,11 @@
 #include "dev_math.h"
 #include "dev_physics.h"
 #include "dev_task.h"
+#include "jacobian_tangents.h"
+#include "rollout_adjoint.h"
+#include "rollout_step.h"
+#include "rollout_sweep.h"
+#include "cov_tile.h"
 #include "pf_noise.h"
 #include "dev_launch.h"
 
@@ -60,13 +65,6 @@ struct PfArgs {
   uint32_t key_pf;   // pf_noise_key(seed)
   double neg_ln_p;   // -ln P, taken on the host
 };
-
-__device__ __forceinline__ void pf_store(void* dst, size_t at, double v, uint32_t f32) {
-  if (f32)
-    reinterpret_cast<float*>(dst)[at] = (float)v;
-  else
-    reinterpret_cast<double*>(dst)[at] = v;
-}
 
 // NV sums over the workgroup, the same bits in every lane: the wavefront's butterfly (a + b = b + a: both partners hold
 // the same value after every round), then the wavefronts' partials in order.  red: 12 x kPfWaves words.
@@ -225,6 +223,8 @@ __global__ __launch_bounds__(kPfBlock) void rollout_pf_kernel(const DevConst c, 
 
     // ---- the step's wrench (uniform) and its z row ----
     const float4 act = load_action_at<TASK>(io.actions_dev + row * A);
+    // (the clip and the motor law as they stood before step_wrench: through it two additions of the sum of squares
+    // came out with swapped operands and one A/B row missed by 0.5 %, profiles/filter_shared_refactor_ab.txt)
     const float araw[4] = {act.x, act.y, act.z, act.w};
     float mf[4];
 #pragma unroll
@@ -392,10 +392,10 @@ __global__ __launch_bounds__(kPfBlock) void rollout_pf_kernel(const DevConst c, 
       }
       if (f.var_dev != nullptr) {
 #pragma unroll
-        for (int j = 0; j < 12; ++j) pf_store(f.var_dev, row * 12 + j, var[j], f32);
+        for (int j = 0; j < 12; ++j) store_out(f.var_dev, row * 12 + j, var[j], f32);
       }
       if (io.status_dev != nullptr) io.status_dev[row] = (uint8_t)ST[best];
-      if (f.ess_dev != nullptr) pf_store(f.ess_dev, row, ess, f32);
+      if (f.ess_dev != nullptr) store_out(f.ess_dev, row, ess, f32);
       if (f.resampled_dev != nullptr) f.resampled_dev[row] = resample ? 1 : 0;
       if (f.best_dev != nullptr) f.best_dev[row] = best;
     }
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(kPfBlock) void rollout_pf_kernel(const DevConst c, 
         for (int j = 0; j < 12; ++j) scr[kScrL + j * 13] = var[j];
       }
       __syncthreads();
-      for (int e = tid; e < 144; e += bd) pf_store(f.P_dev, (size_t)env * 144 + e, scr[kScrL + e], f32);
+      for (int e = tid; e < 144; e += bd) store_out(f.P_dev, (size_t)env * 144 + e, scr[kScrL + e], f32);
     }
 
     // ---- systematic resampling on the integer weights ----
@@ -530,7 +530,7 @@ __global__ __launch_bounds__(kPfBlock) void rollout_pf_kernel(const DevConst c, 
     if (f.lw_out_dev != nullptr) f.lw_out_dev[pbase + p] = LW[p];
   }
   if (tid == 0) {
-    if (f.loglik_dev != nullptr) pf_store(f.loglik_dev, env, loglik, f32);
+    if (f.loglik_dev != nullptr) store_out(f.loglik_dev, env, loglik, f32);
     if (f.ok_dev != nullptr) f.ok_dev[env] = ok ? 1 : 0;
   }
 }
@@ -562,8 +562,6 @@ hipError_t launch_rollout_pf(int task, int mode, const DevConst& c, const DevSta
   CS_DISPATCH(pf_t, c, s, io, f, pa, stream)
 }
 
-bool pf_aligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) == 0; }
-
 }  // namespace
 }  // namespace cs
 
@@ -571,17 +569,12 @@ extern "C" int cs_rollout_pf(cs_ctx* ctx, const cs_rollout_io* io, const cs_roll
   using cs::report_error;
   const char* who = "cs_rollout_pf";
   if (int rc_ = cs::check_rollout_io(io, who, false)) return rc_;
-  if (pio == nullptr) return report_error(CS_ERR_ARG, "cs_rollout_pf: null pio");
-  if (pio->struct_size != sizeof(cs_rollout_pf_io))
-    return report_error(CS_ERR_ABI, ("cs_rollout_pf: pio->struct_size " + std::to_string(pio->struct_size) + " != " +
-                                     std::to_string(sizeof(cs_rollout_pf_io)) + " (sizeof(cs_rollout_pf_io))").c_str());
-  if (io->start_force_dev != nullptr || io->start_prev_shaping_dev != nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_pf: start_force_dev and start_prev_shaping_dev must be NULL");
-  if (io->reward_dev != nullptr || io->terminated_dev != nullptr || io->truncated_dev != nullptr ||
-      io->gx_dev != nullptr || io->gr_dev != nullptr || io->g_actions_dev != nullptr || io->g_x0_dev != nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_pf: the reward, flag, cotangent and gradient pointers must be NULL");
-  if (pio->out_dtype != CS_JAC_F64 && pio->out_dtype != CS_JAC_F32)
-    return report_error(CS_ERR_ARG, "cs_rollout_pf: unknown pio->out_dtype (CS_JAC_F64 or CS_JAC_F32)");
+  const bool extra = io->reward_dev != nullptr || io->terminated_dev != nullptr || io->truncated_dev != nullptr ||
+                     io->gx_dev != nullptr || io->gr_dev != nullptr || io->g_actions_dev != nullptr ||
+                     io->g_x0_dev != nullptr;
+  if (int rc_ = cs::check_filter_io(io, who, {"pio", "cs_rollout_pf_io", pio, sizeof(cs_rollout_pf_io)}, nullptr,
+                                    extra ? "the reward, flag, cotangent and gradient pointers must be NULL" : nullptr))
+    return rc_;
   if (pio->num_meas < 1 || pio->num_meas > CS_EKF_MAX_MEAS)
     return report_error(CS_ERR_ARG, "cs_rollout_pf: num_meas must be 1 .. CS_EKF_MAX_MEAS");
   const int P = pio->num_particles;
@@ -603,23 +596,14 @@ extern "C" int cs_rollout_pf(cs_ctx* ctx, const cs_rollout_io* io, const cs_roll
                         "of part_in_dev, pstatus_in_dev and lw_in_dev");
   if (carried && pio->L0_dev != nullptr)
     return report_error(CS_ERR_ARG, "cs_rollout_pf: L0_dev belongs to the Gaussian start: NULL with a carried start");
-  const void* f64s[] = {io->start_x_dev, io->x_dev, pio->H_dev, pio->r_dev, pio->Lq_dev, pio->z_dev, pio->L0_dev,
-                        pio->part_in_dev, pio->lw_in_dev, pio->part_out_dev, pio->lw_out_dev, pio->part_tape_dev,
-                        pio->lw_tape_dev};
-  for (const void* p : f64s)
-    if (!cs::pf_aligned(p, 7u)) return report_error(CS_ERR_ARG, "cs_rollout_pf: a float64 array is not 8-B aligned");
-  const uintptr_t out_mask = pio->out_dtype == CS_JAC_F32 ? 3u : 7u;
-  const void* outs[] = {pio->var_dev, pio->ess_dev, pio->P_dev, pio->loglik_dev};
-  for (const void* p : outs)
-    if (!cs::pf_aligned(p, out_mask))
-      return report_error(CS_ERR_ARG, "cs_rollout_pf: an output array is not aligned to its element size");
-  if (!cs::pf_aligned(io->actions_dev, 3u) || !cs::pf_aligned(pio->best_dev, 3u) ||
-      !cs::pf_aligned(pio->wq_tape_dev, 3u) || !cs::pf_aligned(pio->anc_tape_dev, 3u))
-    return report_error(CS_ERR_ARG, "cs_rollout_pf: actions_dev or a 32-bit array is not 4-B aligned");
   cs::ContextView v;
-  if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
-  if (v.c->act_f32)
-    return report_error(CS_ERR_ARG, "cs_rollout_pf: not available with the float32 motor model (action_arith)");
+  if (int rc_ = cs::enter_filter_context(
+          ctx, who, stream, pio->out_dtype,
+          {io->start_x_dev, io->x_dev, pio->H_dev, pio->r_dev, pio->Lq_dev, pio->z_dev, pio->L0_dev, pio->part_in_dev,
+           pio->lw_in_dev, pio->part_out_dev, pio->lw_out_dev, pio->part_tape_dev, pio->lw_tape_dev},
+          {pio->var_dev, pio->ess_dev, pio->P_dev, pio->loglik_dev},
+          {io->actions_dev, pio->best_dev, pio->wq_tape_dev, pio->anc_tape_dev}, "actions_dev or a 32-bit array", &v))
+    return rc_;
   const cs::PfArgs pa{cs::pf_noise_key(cs::context_seed(ctx)), -std::log((double)P)};
   const hipError_t e = cs::launch_rollout_pf(v.task, v.mode, *v.c, *v.s, *io, *pio, pa, (hipStream_t)stream);
   if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_pf: kernel launch");

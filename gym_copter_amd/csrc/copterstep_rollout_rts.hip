@@ -8,10 +8,9 @@
 //
 // One lane per env on the tile layout of the step kernels (tile t -> workgroup t).  Per backward step j = K-2 .. -1
 // (row -1 is the filter's starting point):
-//   prediction  P- = A P_f[j] A^T + Q through jacobian_block (jacobian_tangents.h) at (x_f[j], status_f[j]) under
-//               actions[j+1] with zero wrench tangents, in copterstep_rollout_ekf.hip's two passes of 6 blocks of 2
-//               directions, restated here: in float64 P- is the filter's own prior of that step bit for bit.  W = A P_f[j]
-//               is kept.
+//   prediction  P- = A P_f[j] A^T + Q at (x_f[j], status_f[j]) under actions[j+1] by cov_predict (cov_tile.h), the
+//               function copterstep_rollout_ekf.hip calls with the same arguments: in float64 P- is the filter's own
+//               prior of that step bit for bit.  W = A P_f[j] is kept.
 //   solve       D = P_s[j+1] - P-, then P- = U^T U in place and G = P-^-1 W column by column in place (rts_solve.h)
 //   smoothing   x_s[j] = x_f[j] + G^T (x_s[j+1] - x_pred[j+1]);  P_s[j] = P_f[j] + G^T D G, column by column into the
 //               rows of the factor, which is dead once G is solved
@@ -41,72 +40,19 @@
 #include "rollout_step.h"
 #include "rollout_sweep.h"
 #include "rts_solve.h"
+#include "cov_tile.h"
 #include "dev_launch.h"
 
 namespace cs {
 namespace {
 
 // the lane's LDS rows (row k at [k * kBlock]): triangle 0, W = A P_f (W[i][c] at i * 12 + c) with one row of padding
-// behind it (the stage of the 12 x 12 stores: a lane's matrix row-major at stride 145), triangle 1, x_s[j+1]
+// behind it (the stage of the 12 x 12 stores, cov_tile.h), triangle 1, x_s[j+1]
 constexpr int kRowW = kEkfSym;
-constexpr int kStageStride = 145;  // (odd: the lanes' stage writes fall into different banks)
 constexpr int kRowT1 = kRowW + kStageStride;
 constexpr int kRowXs = kRowT1 + kEkfSym;
 constexpr int kRtsRows = kRowXs + 12;
-static_assert(kStageStride * kWave <= (kRowT1 - kRowW) * kBlock, "the stage fits W and its padding row");
 static_assert(kRtsRows * kBlock * sizeof(double) <= 160 * 1024, "the LDS of one CU");
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void store_out(void* dst, size_t at, double v, uint32_t f32) {
-  if (f32)
-    reinterpret_cast<float*>(dst)[at] = (float)v;
-  else
-    reinterpret_cast<double*>(dst)[at] = v;
-}
-
-// The wavefront's staged matrices (lane l's at stage[l * kStageStride ..], row-major) to rows `at` .. of an [.., N, 144]
-// output: a whole wavefront's 64 x 144 values are one contiguous run, read back linearly so that every store instruction
-// writes whole lines; a partial wavefront lane by lane.
-__device__ __forceinline__ void store_matrix(void* dst, size_t at, const double* stage, const RowOut& ro, uint32_t f32) {
-  if (ro.whole) {
-    const size_t base = (at + ro.env0) * 144;
-#pragma clang loop unroll(disable)
-    for (int v = 0; v < 144; ++v) {
-      const int el = v * kWave + ro.lane;
-      const int ln = el / 144, idx = el - ln * 144;
-      store_out(dst, base + el, stage[ln * kStageStride + idx], f32);
-    }
-  } else if (ro.valid) {
-    const size_t base = (at + ro.i) * 144;
-    const double* mine = stage + ro.lane * kStageStride;
-#pragma clang loop unroll(disable)
-    for (int v = 0; v < 144; ++v) store_out(dst, base + v, mine[v], f32);
-  }
-}
-
-// the upper triangle of a row-major 12 x 12 matrix in global memory -> a packed triangle in the lane's LDS column
-// (unrolled: the 78 loads are independent and in flight together; one at a time they would cost 78 L2 latencies a step)
-__device__ __forceinline__ void load_triangle(double* T, const double* p) {
-#pragma unroll
-  for (int a = 0; a < 12; ++a) {
-#pragma unroll
-    for (int j = a; j < 12; ++j) T[(j * (j + 1) / 2 + a) * kBlock] = p[a * 12 + j];
-  }
-}
-
-// a packed triangle -> the lane's stage, full and symmetric (the caller syncs the wavefront before the stage is stored)
-__device__ __forceinline__ void stage_triangle(double* mine, const double* T) {
-#pragma clang loop unroll(disable)
-  for (int a = 0; a < 12; ++a) {
-#pragma unroll
-    for (int b = 0; b < 12; ++b) mine[a * 12 + b] = T[ekf_sym_at(a, b) * kBlock];
-  }
-}
 
 template <int TASK, int MODE, bool GYRO>
 __global__ __launch_bounds__(kBlock) void rollout_rts_kernel(const DevConst c, const DevState s, const cs_rollout_io io,
@@ -177,55 +123,13 @@ __global__ __launch_bounds__(kBlock) void rollout_rts_kernel(const DevConst c, c
 
     // ---- the step's wrench, as the filter made it for step j+2 ----
     const float4 act = load_action_at<TASK>(io.actions_dev + (next + ii) * A);
-    const float araw[4] = {act.x, act.y, act.z, act.w};
-    float mf[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) mf[k] = clip01(araw[k]);
-    Wrench w;
-    w.bz = thrust_model(q, mf[0], mf[1], mf[2], mf[3]);
-    torque_model(q, mf[0], mf[1], mf[2], mf[3], w);
+    const Wrench w = step_wrench(q, act);
 
     load_triangle(Ta, pf);
 
-    // ---- the prediction: 12 blocks of 2 directions through the tangents of the step, the actions known ----
-    const Wrench zero{0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma clang loop unroll(disable)
-    for (int b = 0; b < 12; ++b) {
-      const bool second = b >= 6;  // pass 1: columns 2 b', 2 b' + 1 of P_f -> those of W; pass 2: rows of W -> columns of P-
-      const int c0 = (second ? b - 6 : b) * kJacDirs;
-      JacPoint pt;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) pt.x[k] = xf[k * xf_stride];
-      pt.fs = fs0;
-      pt.active = fs0 != CS_STATUS_LANDED;
-      pt.px = pt.py = pt.pz = -0.0;
-      double v[kJacDirs][12];
-      const Wrench dw[kJacDirs] = {zero, zero};
-#pragma unroll
-      for (int d = 0; d < kJacDirs; ++d) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k)
-          v[d][k] = second ? W[((c0 + d) * 12 + k) * kBlock] : Ta[ekf_sym_at(k, c0 + d) * kBlock];
-      }
-      double xn[12];
-      jacobian_block<FULL, GYRO>(c, q, w, dw, pt, xn, v);
-      if (!second) {
-#pragma unroll
-        for (int d = 0; d < kJacDirs; ++d) {
-#pragma unroll
-          for (int k = 0; k < 12; ++k) W[(k * 12 + c0 + d) * kBlock] = v[d][k];
-        }
-      } else {  // column c0 + d of P- above its diagonal (every column of P_f was read in pass 1), plus Q
-#pragma unroll
-        for (int d = 0; d < kJacDirs; ++d) {
-          const int col = c0 + d;
-#pragma unroll
-          for (int k = 0; k < 12; ++k) {
-            if (k <= col) Ta[(col * (col + 1) / 2 + k) * kBlock] = v[d][k] + r.Q_dev[k * 12 + col];
-          }
-        }
-      }
-    }
+    // ---- the prediction: P- = A P_f[j] A^T + Q at the filter's point, by the filter's function (its branch bits are
+    //      on the filter's tape already) ----
+    cov_predict<FULL, GYRO>(c, q, w, fs0, xf, xf_stride, Ta, W, r.Q_dev);
 
     // ---- D = P_s[j+1] - P-, the factor of P-, G = P-^-1 W ----
 #pragma unroll 13
@@ -296,8 +200,6 @@ hipError_t launch_rollout_rts(int task, int mode, const DevConst& c, const DevSt
   CS_DISPATCH(rts_t, c, s, io, r, stream)
 }
 
-bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 }  // namespace
 }  // namespace cs
 
@@ -305,42 +207,28 @@ extern "C" int cs_rollout_rts(cs_ctx* ctx, const cs_rollout_io* io, const cs_rol
   using cs::report_error;
   const char* who = "cs_rollout_rts";
   if (int rc_ = cs::check_rollout_io(io, who, false)) return rc_;
-  if (rio == nullptr) return report_error(CS_ERR_ARG, "cs_rollout_rts: null rio");
-  if (rio->struct_size != sizeof(cs_rollout_rts_io))
-    return report_error(CS_ERR_ABI, ("cs_rollout_rts: rio->struct_size " + std::to_string(rio->struct_size) + " != " +
-                                     std::to_string(sizeof(cs_rollout_rts_io)) + " (sizeof(cs_rollout_rts_io))").c_str());
-  if (io->start_x_dev == nullptr || io->start_status_dev == nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_rts: start_x_dev (the filter's x0) and start_status_dev are required");
-  if (io->start_force_dev != nullptr || io->start_prev_shaping_dev != nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_rts: start_force_dev and start_prev_shaping_dev must be NULL");
-  if (io->reward_dev != nullptr || io->terminated_dev != nullptr || io->truncated_dev != nullptr ||
-      io->status_dev != nullptr || io->gx_dev != nullptr || io->gr_dev != nullptr || io->g_actions_dev != nullptr ||
-      io->g_x0_dev != nullptr)
-    return report_error(CS_ERR_ARG,
-                        "cs_rollout_rts: the reward, flag, status, cotangent and gradient pointers must be NULL");
-  if (rio->out_dtype != CS_JAC_F64 && rio->out_dtype != CS_JAC_F32)
-    return report_error(CS_ERR_ARG, "cs_rollout_rts: unknown rio->out_dtype (CS_JAC_F64 or CS_JAC_F32)");
+  const bool no_start = io->start_x_dev == nullptr || io->start_status_dev == nullptr;
+  const bool extra = io->reward_dev != nullptr || io->terminated_dev != nullptr || io->truncated_dev != nullptr ||
+                     io->status_dev != nullptr || io->gx_dev != nullptr || io->gr_dev != nullptr ||
+                     io->g_actions_dev != nullptr || io->g_x0_dev != nullptr;
+  if (int rc_ = cs::check_filter_io(
+          io, who, {"rio", "cs_rollout_rts_io", rio, sizeof(cs_rollout_rts_io)},
+          no_start ? "start_x_dev (the filter's x0) and start_status_dev are required" : nullptr,
+          extra ? "the reward, flag, status, cotangent and gradient pointers must be NULL" : nullptr))
+    return rc_;
   if (rio->x_f_dev == nullptr || rio->x_pred_dev == nullptr || rio->status_f_dev == nullptr ||
       rio->P_f_dev == nullptr || rio->Q_dev == nullptr || rio->P0_dev == nullptr)
     return report_error(CS_ERR_ARG,
                         "cs_rollout_rts: x_f_dev, x_pred_dev, status_f_dev, P_f_dev, Q_dev and P0_dev are required");
   if ((rio->end_x_dev == nullptr) != (rio->end_P_dev == nullptr))
     return report_error(CS_ERR_ARG, "cs_rollout_rts: end_x_dev and end_P_dev are given both or neither");
-  const void* f64s[] = {io->start_x_dev, io->x_dev, rio->x_f_dev, rio->x_pred_dev, rio->P_f_dev, rio->Q_dev,
-                        rio->P0_dev, rio->end_x_dev, rio->end_P_dev, rio->x0_dev};
-  for (const void* p : f64s)
-    if (!cs::aligned8(p)) return report_error(CS_ERR_ARG, "cs_rollout_rts: a float64 array is not 8-B aligned");
-  const uintptr_t out_mask = rio->out_dtype == CS_JAC_F32 ? 3u : 7u;
-  const void* outs[] = {rio->P_tape_dev, rio->var_dev, rio->P0_s_dev};
-  for (const void* p : outs)
-    if ((reinterpret_cast<uintptr_t>(p) & out_mask) != 0)
-      return report_error(CS_ERR_ARG, "cs_rollout_rts: an output array is not aligned to its element size");
-  if ((reinterpret_cast<uintptr_t>(io->actions_dev) & 3u) != 0)
-    return report_error(CS_ERR_ARG, "cs_rollout_rts: actions_dev is not 4-B aligned");
   cs::ContextView v;
-  if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
-  if (v.c->act_f32)
-    return report_error(CS_ERR_ARG, "cs_rollout_rts: not available with the float32 motor model (action_arith)");
+  if (int rc_ = cs::enter_filter_context(ctx, who, stream, rio->out_dtype,
+                                         {io->start_x_dev, io->x_dev, rio->x_f_dev, rio->x_pred_dev, rio->P_f_dev,
+                                          rio->Q_dev, rio->P0_dev, rio->end_x_dev, rio->end_P_dev, rio->x0_dev},
+                                         {rio->P_tape_dev, rio->var_dev, rio->P0_s_dev}, {io->actions_dev},
+                                         "actions_dev", &v))
+    return rc_;
   const hipError_t e = cs::launch_rollout_rts(v.task, v.mode, *v.c, *v.s, *io, *rio, (hipStream_t)stream);
   if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_rts: kernel launch");
   return CS_OK;

@@ -19,14 +19,12 @@ CS_MPPI_FN uint32_t es_noise_key(uint64_t seed) {
 // epsilon of (global pair index, nonce `stream`, parameter index p): counter = (pair, stream), key = key_es + p (mod
 // 2^32) -- a pure function of its arguments and the seed, the same whatever the population size, the number of
 // parameters, the split of the population over calls (pair_base) or the launch history.  The pair index and the nonce
-// are full 32-bit numbers (the index wraps at 2^32); keys are distinct for p < 2^32.  The value is mppi_noise's:
-// T = the sum of the four 16-bit halves of the 64 output bits minus 131 070, epsilon = (float)T x kMppiNoiseScale:
-// Irwin-Hall of order 4, mean 0, variance 1 - 2^-32, support +-3.46.
+// are full 32-bit numbers (the index wraps at 2^32); keys are distinct for p < 2^32.  The value is mppi_noise's
+// (mppi_irwin_hall): Irwin-Hall of order 4, mean 0, variance 1 - 2^-32, support +-3.46.
 CS_MPPI_FN float es_noise(uint32_t key_es, uint32_t pair, uint32_t stream, uint32_t p) {
   uint32_t r0, r1;
   mppi_philox2x32_10(pair, stream, key_es + p, r0, r1);
-  const int32_t t = (int32_t)((r0 >> 16) + (r0 & 0xFFFFu) + (r1 >> 16) + (r1 & 0xFFFFu)) - 131070;
-  return (float)t * kMppiNoiseScale;
+  return mppi_irwin_hall(r0, r1);
 }
 
 }  // namespace cs

@@ -45,16 +45,21 @@ CS_MPPI_FN void mppi_philox2x32_10(uint32_t c0, uint32_t c1, uint32_t key, uint3
   o1 = c1;
 }
 
+// The Irwin-Hall draw of order 4 from the two words of one Philox call (also es_noise.h's and pf_noise.h's):
+// T = the sum of the four 16-bit halves of the 64 bits minus 131 070 (an exact integer, |T| <= 131 070);
+// epsilon = (float)T x kMppiNoiseScale: mean 0, variance 1 - 2^-32, support +-3.46.
+CS_MPPI_FN float mppi_irwin_hall(uint32_t r0, uint32_t r1) {
+  const int32_t t = (int32_t)((r0 >> 16) + (r0 & 0xFFFFu) + (r1 >> 16) + (r1 & 0xFFFFu)) - 131070;
+  return (float)t * kMppiNoiseScale;
+}
+
 // epsilon of (global env id, nonce `stream`, step k = 1.., sample p, action component j): counter = (env id, stream),
 // key = key_noise + (((k - 1) << 16) + p) * 4 + j (mod 2^32) -- a pure function of its arguments and the seed, the same
 // whatever the batch size, the sharding, the number of samples or the launch history; distinct keys for k <= 16 384.
-// T = the sum of the four 16-bit halves of the 64 output bits minus 131 070 (an exact integer, |T| <= 131 070);
-// epsilon = (float)T x kMppiNoiseScale: Irwin-Hall of order 4, mean 0, variance 1 - 2^-32, support +-3.46.
 CS_MPPI_FN float mppi_noise(uint32_t key_noise, uint32_t env_id, uint32_t stream, uint32_t k, uint32_t p, uint32_t j) {
   uint32_t r0, r1;
   mppi_philox2x32_10(env_id, stream, key_noise + ((((k - 1u) << kMppiSampleBits) + p) * 4u + j), r0, r1);
-  const int32_t t = (int32_t)((r0 >> 16) + (r0 & 0xFFFFu) + (r1 >> 16) + (r1 & 0xFFFFu)) - 131070;
-  return (float)t * kMppiNoiseScale;
+  return mppi_irwin_hall(r0, r1);
 }
 
 // Smooth noise (cs_rollout_mppi_costs_ex / cs_rollout_mppi_update_ex, copterstep_rollout_mppi_smooth.hip; DESIGN.md

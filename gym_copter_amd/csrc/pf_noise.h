@@ -30,13 +30,12 @@ CS_MPPI_FN void pf_words(uint32_t key_pf, uint32_t g, uint32_t nonce, uint32_t k
   mppi_philox2x32_10(g, nonce, key_pf + ((((k << kPfParticleBits) + p) << kPfSlotBits) + j), r0, r1);
 }
 
-// epsilon of state component j = 0 .. 11: mppi_noise's Irwin-Hall draw of order 4 (mean 0, variance 1 - 2^-32, support
-// +-3.46): T = the sum of the four 16-bit halves minus 131 070, epsilon = (float)T x kMppiNoiseScale.
+// epsilon of state component j = 0 .. 11: mppi_noise's Irwin-Hall draw of order 4 (mppi_irwin_hall: mean 0, variance
+// 1 - 2^-32, support +-3.46).
 CS_MPPI_FN float pf_noise(uint32_t key_pf, uint32_t g, uint32_t nonce, uint32_t k, uint32_t p, uint32_t j) {
   uint32_t r0, r1;
   pf_words(key_pf, g, nonce, k, p, j, r0, r1);
-  const int32_t t = (int32_t)((r0 >> 16) + (r0 & 0xFFFFu) + (r1 >> 16) + (r1 & 0xFFFFu)) - 131070;
-  return (float)t * kMppiNoiseScale;
+  return mppi_irwin_hall(r0, r1);
 }
 
 // u of step k >= 1: the top 16 bits of the first word of slot 12 at particle 0 -- the offset of the systematic

@@ -29,53 +29,21 @@ PfResult = collections.namedtuple("PfResult", "x var ess resampled best status P
                                               "pstatus_tape lw_tape wq_tape anc_tape")
 
 
-def pf_model(self, H, r, Q):
-    """H [M,12], r [M] and the process noise, checked on the host and kept on the device as (H, r, Lq): Q [12,12]
-    symmetric positive definite is factored (numpy.linalg.cholesky), Q [12] of variances >= 0 gives diag sqrt(Q).  The
-    same values are uploaded once; device tensors are recognised by identity and version."""
-    torch = _torch()
-    tensors = all(isinstance(m, torch.Tensor) for m in (H, r, Q))
-    ident = tuple((id(m), m._version, m.data_ptr()) for m in (H, r, Q)) if tensors else None
-    cache = getattr(self, "_pf_m", None)
-    if ident is not None and cache is not None and cache[2] == ident:
-        return cache[1]
-
-    def host(m, name):
-        a = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m)
-        if a.dtype.kind not in "fiu":
-            raise ValueError("%s must be a real floating-point array, got dtype %s" % (name, a.dtype))
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if not np.isfinite(a).all():
-            raise ValueError("%s must be finite" % name)
-        return a
-    h = host(H, "H")
-    if h.ndim != 2 or h.shape[1] != 12 or not 1 <= h.shape[0] <= _lib.EKF_MAX_MEAS:
-        raise ValueError("H must have shape (M, 12) with 1 <= M <= %d, got %s" % (_lib.EKF_MAX_MEAS, h.shape))
-    rv = host(r, "r")
-    if rv.shape != (h.shape[0],):
-        raise ValueError("r must have shape (%d,) (one variance per row of H), got %s" % (h.shape[0], rv.shape))
-    if not (rv > 0).all():
-        raise ValueError("r must be positive: the measurement variances")
-    q = host(Q, "Q")
+def _noise_factor(q):
+    """Lq of the process noise q, a finite float64 host array: Q [12,12] symmetric positive definite is factored
+    (numpy.linalg.cholesky), Q [12] of variances >= 0 gives diag sqrt(Q)."""
     if q.shape == (12,):
         if not (q >= 0).all():
             raise ValueError("Q must be >= 0: the process noise variances")
-        lq = np.diag(np.sqrt(q))
-    elif q.shape == (12, 12):
-        if not np.array_equal(q, q.T):
-            raise ValueError("Q must be symmetric")
-        try:
-            lq = np.linalg.cholesky(q)
-        except np.linalg.LinAlgError:
-            raise ValueError("Q must be positive definite (a Q with zero variances: pass the 12 variances)") from None
-    else:
+        return np.diag(np.sqrt(q))
+    if q.shape != (12, 12):
         raise ValueError("Q must have shape (12, 12) or (12,), got %s" % (q.shape,))
-    lq = np.ascontiguousarray(lq)
-    key = (h.tobytes(), rv.tobytes(), lq.tobytes())
-    if cache is None or cache[0] != key:
-        cache = (key, [torch.from_numpy(m).to(self.device) for m in (h, rv, lq)])
-    cache = self._pf_m = (cache[0], cache[1], ident, (H, r, Q) if tensors else None)
-    return cache[1]
+    if not np.array_equal(q, q.T):
+        raise ValueError("Q must be symmetric")
+    try:
+        return np.linalg.cholesky(q)
+    except np.linalg.LinAlgError:
+        raise ValueError("Q must be positive definite (a Q with zero variances: pass the 12 variances)") from None
 
 
 def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce=0, ess_frac=0.5, status0=None,
@@ -101,7 +69,8 @@ def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce
     self._check_open()
     torch = _torch()
     dtype = self._out_dtype(dtype)
-    Hd, rd, Lqd = self._pf_model(H, r, Q)
+    Hd, rd, Lqd = self._filter_model("pf", (H, r, Q), lambda: (
+        *self._measurement_model(H, r), _noise_factor(self._host_array(Q, "Q"))))
     M = int(Hd.shape[0])
     P = particles
     if not isinstance(P, (int, np.integer)) or isinstance(P, bool) or P < _lib.PF_MIN_PARTICLES or \
@@ -143,12 +112,7 @@ def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce
     else:
         xt = self._ekf_input(x0, (12, n), "x0", keep)
         io.start_x_dev = xt.data_ptr()
-        if status0 is None:
-            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=dev)
-            keep.append(st)
-            io.start_status_dev = st.data_ptr()
-        else:
-            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
+        self._start_status(io, status0, keep)
         if P0 is not None:
             Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
             try:

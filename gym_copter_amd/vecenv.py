@@ -1496,47 +1496,73 @@ class CopterVecEnv(_VectorEnvBase):
         self._keep = keep + [xbar, Kg, d]
         return ro, acts
 
-    # -- the extended Kalman filter over the env step --------
-    def _ekf_model(self, H, r, Q):
-        """H [M,12], r [M] and Q [12,12], checked on the host (finite; 1 <= M <= 12; r > 0; Q symmetric) and kept on the
-        device: the same values are uploaded once (a streaming filter passes them with every chunk).  Host arrays are
-        compared by value; device tensors are recognised by identity and version (the same, unmodified tensors as in the
-        last call cost no device-to-host copy), and checked on the host once when they are new."""
+    # -- the filter family (DESIGN sections 19 to 21): the model every env and step shares, and the start's status ----
+    def _filter_model(self, slot, given, check):
+        """The arrays a filter shares among every env and step -- `given`, the caller's (H, r, Q) or (Q,) -- checked on
+        the host and kept on the device: check() returns the float64 host arrays to upload (_host_array's, checked
+        further).  The same values are uploaded once (a streaming filter passes them with every chunk).
+        Host arrays are compared by value; device tensors are recognised by identity and version (the same, unmodified
+        tensors as in the last call cost no device-to-host copy), and checked on the host once when they are new.
+        `slot` names the calling entry point's cache."""
         torch = _torch()
-        tensors = all(isinstance(m, torch.Tensor) for m in (H, r, Q))
-        ident = tuple((id(m), m._version, m.data_ptr()) for m in (H, r, Q)) if tensors else None
-        cache = getattr(self, "_ekf_m", None)
+        tensors = all(isinstance(m, torch.Tensor) for m in given)
+        ident = tuple((id(m), m._version, m.data_ptr()) for m in given) if tensors else None
+        caches = self.__dict__.setdefault("_filter_m", {})
+        cache = caches.get(slot)
         if ident is not None and cache is not None and cache[2] == ident:
             return cache[1]
+        model = [np.ascontiguousarray(a) for a in check()]
+        key = tuple(a.tobytes() for a in model)
+        if cache is None or cache[0] != key:
+            cache = (key, [torch.from_numpy(a).to(self.device) for a in model])
+        # (the caller's tensors are kept alive with their identity, so that an id cannot be reused by another tensor)
+        caches[slot] = (cache[0], cache[1], ident, given if tensors else None)
+        return cache[1]
 
-        def host(m, name):
-            a = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m)
-            if a.dtype.kind not in "fiu":
-                raise ValueError("%s must be a real floating-point array, got dtype %s" % (name, a.dtype))
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if not np.isfinite(a).all():
-                raise ValueError("%s must be finite" % name)
-            return a
-        h = host(H, "H")
+    @staticmethod
+    def _host_array(m, name):
+        """m, a tensor or an array of real numbers, as a finite float64 host array."""
+        a = np.asarray(m.detach().cpu() if isinstance(m, _torch().Tensor) else m)
+        if a.dtype.kind not in "fiu":
+            raise ValueError("%s must be a real floating-point array, got dtype %s" % (name, a.dtype))
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if not np.isfinite(a).all():
+            raise ValueError("%s must be finite" % name)
+        return a
+
+    def _measurement_model(self, H, r):
+        """H [M,12] (1 <= M <= 12) and r [M] > 0 of rollout_ekf and rollout_pf, on the host."""
+        h = self._host_array(H, "H")
         if h.ndim != 2 or h.shape[1] != 12 or not 1 <= h.shape[0] <= _lib.EKF_MAX_MEAS:
             raise ValueError("H must have shape (M, 12) with 1 <= M <= %d, got %s" % (_lib.EKF_MAX_MEAS, h.shape))
-        rv = host(r, "r")
+        rv = self._host_array(r, "r")
         if rv.shape != (h.shape[0],):
             raise ValueError("r must have shape (%d,) (one variance per row of H), got %s" % (h.shape[0], rv.shape))
         if not (rv > 0).all():
             raise ValueError("r must be positive: the measurement variances")
-        q = host(Q, "Q")
+        return h, rv
+
+    def _process_noise(self, Q):
+        """Q [12,12] symmetric of rollout_ekf and rollout_rts, on the host."""
+        q = self._host_array(Q, "Q")
         if q.shape != (12, 12):
             raise ValueError("Q must have shape (12, 12), got %s" % (q.shape,))
         if not np.array_equal(q, q.T):
             raise ValueError("Q must be symmetric")
-        key = (h.tobytes(), rv.tobytes(), q.tobytes())
-        if cache is None or cache[0] != key:
-            cache = (key, [torch.from_numpy(m).to(self.device) for m in (h, rv, q)])
-        # (the caller's tensors are kept alive with their identity, so that an id cannot be reused by another tensor)
-        cache = self._ekf_m = (cache[0], cache[1], ident, (H, r, Q) if tensors else None)
-        return cache[1]
+        return q
 
+    def _start_status(self, io, status0, keep):
+        """io.start_status_dev of a filter's start: the caller's status0 [N] uint8, AIRBORNE by default."""
+        torch = _torch()
+        n = self.num_envs
+        if status0 is None:
+            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=self.device)
+            keep.append(st)
+            io.start_status_dev = st.data_ptr()
+        else:
+            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
+
+    # -- the extended Kalman filter over the env step (DESIGN section 19) --------
     def _ekf_input(self, v, shape, name, keep):
         """A per-env input of rollout_ekf as a contiguous float64 device tensor, kept alive in `keep`: a floating-point
         tensor on this env's device, or a host array."""
@@ -1584,19 +1610,15 @@ class CopterVecEnv(_VectorEnvBase):
         self._check_open()
         torch = _torch()
         dtype = self._out_dtype(dtype)
-        Hd, rd, Qd = self._ekf_model(H, r, Q)
+        Hd, rd, Qd = self._filter_model("ekf", (H, r, Q), lambda: (
+            *self._measurement_model(H, r), self._process_noise(Q)))
         M = int(Hd.shape[0])
         io, K, keep = self._rollout_io(actions, None)
         n, dev = self.num_envs, self.device
         zt = self._ekf_input(z, (K, n, M), "z", keep)
         xt = self._ekf_input(x0, (12, n), "x0", keep)
         Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
-        if status0 is None:
-            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=dev)
-            keep.append(st)
-            io.start_status_dev = st.data_ptr()
-        else:
-            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
+        self._start_status(io, status0, keep)
         io.start_x_dev = xt.data_ptr()
         eio = _lib.RolloutEkfIO()
         eio.struct_size = C.sizeof(_lib.RolloutEkfIO)
@@ -1627,35 +1649,9 @@ class CopterVecEnv(_VectorEnvBase):
     # -- the bootstrap particle filter over the env step: its host side lives with its streaming
     #    driver in pf.py and is bound here.  (The list of guarded entry points in tests/test_gpu_output_bounds.py is
     #    read from this class's `def`s; rollout_pf's guarded-output test is in tests/test_gpu_rollout_pf.py.) --------
-    _pf_model = _pf.pf_model
     rollout_pf = _pf.rollout_pf
 
     # -- the Rauch-Tung-Striebel smoother over the filter's tapes --------
-    def _rts_Q(self, Q):
-        """Q [12,12], checked on the host (finite, symmetric) and kept on the device: the same values are uploaded once
-        (a chunked smoother passes them with every chunk); a device tensor is recognised by identity and version."""
-        torch = _torch()
-        ident = (id(Q), Q._version, Q.data_ptr()) if isinstance(Q, torch.Tensor) else None
-        cache = getattr(self, "_rts_q", None)
-        if ident is not None and cache is not None and cache[2] == ident:
-            return cache[1]
-        q = np.asarray(Q.detach().cpu() if isinstance(Q, torch.Tensor) else Q)
-        if q.dtype.kind not in "fiu":
-            raise ValueError("Q must be a real floating-point array, got dtype %s" % q.dtype)
-        q = np.ascontiguousarray(q, dtype=np.float64)
-        if q.shape != (12, 12):
-            raise ValueError("Q must have shape (12, 12), got %s" % (q.shape,))
-        if not np.isfinite(q).all():
-            raise ValueError("Q must be finite")
-        if not np.array_equal(q, q.T):
-            raise ValueError("Q must be symmetric")
-        key = q.tobytes()
-        if cache is None or cache[0] != key:
-            cache = (key, torch.from_numpy(q).to(self.device))
-        # (the caller's tensor is kept alive with its identity, so that an id cannot be reused by another tensor)
-        cache = self._rts_q = (cache[0], cache[1], ident, Q if ident is not None else None)
-        return cache[1]
-
     def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):
         """A Rauch-Tung-Striebel fixed-interval smoother over the tapes of rollout_ekf, K backward steps per env in one
         kernel: the estimate of every step given the measurements of all K steps, and that of the starting point.  The
@@ -1684,7 +1680,7 @@ class CopterVecEnv(_VectorEnvBase):
         dtype = self._out_dtype(dtype)
         if self.config.action_arith != _ARITH["float64"]:
             raise ValueError('rollout_rts is not available under action_arith="float32"')
-        Qd = self._rts_Q(Q)
+        Qd, = self._filter_model("rts", (Q,), lambda: (self._process_noise(Q),))
         io, K, keep = self._rollout_io(actions, None)
         n, dev = self.num_envs, self.device
         if not isinstance(filt, EkfResult):
@@ -1699,12 +1695,7 @@ class CopterVecEnv(_VectorEnvBase):
                          (filt.P_tape, "filt.P_tape", (K, n, 12, 12), torch.float64))
         xt = self._ekf_input(x0, (12, n), "x0", keep)
         Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
-        if status0 is None:
-            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=dev)
-            keep.append(st)
-            io.start_status_dev = st.data_ptr()
-        else:
-            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
+        self._start_status(io, status0, keep)
         io.start_x_dev = xt.data_ptr()
         rio = _lib.RolloutRtsIO()
         rio.struct_size = C.sizeof(_lib.RolloutRtsIO)
