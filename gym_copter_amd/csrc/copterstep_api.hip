@@ -354,39 +354,25 @@ int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, Pa
   return CS_OK;
 }
 
-int mlp_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out) {
-  if (ctx->mlp_partials == nullptr) {
+int grad_scratch(cs_ctx* ctx, GradScratch slot, const char* who, void* stream, size_t bytes, double** out) {
+  double*& buffer = slot == kScratchMlpGrad ? ctx->mlp_partials
+                    : slot == kScratchEsGrad ? ctx->es_partials
+                                             : ctx->ppo_partials;
+  if (buffer == nullptr) {
     if (capturing((hipStream_t)stream))
       return fail(CS_ERR_ARG, std::string(who) + ": the first call on a context allocates its scratch: make it outside "
                                                  "graph capture");
     DeviceGuard guard(ctx->cfg.device);
-    CS_HIP(hipMalloc((void**)&ctx->mlp_partials, bytes));
+    CS_HIP(hipMalloc((void**)&buffer, bytes));
   }
-  *out = ctx->mlp_partials;
+  *out = buffer;
   return CS_OK;
 }
 
-int es_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out) {
-  if (ctx->es_partials == nullptr) {
-    if (capturing((hipStream_t)stream))
-      return fail(CS_ERR_ARG, std::string(who) + ": the first call on a context allocates its scratch: make it outside "
-                                                 "graph capture");
-    DeviceGuard guard(ctx->cfg.device);
-    CS_HIP(hipMalloc((void**)&ctx->es_partials, bytes));
-  }
-  *out = ctx->es_partials;
-  return CS_OK;
-}
-
-int ppo_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out) {
-  if (ctx->ppo_partials == nullptr) {
-    if (capturing((hipStream_t)stream))
-      return fail(CS_ERR_ARG, std::string(who) + ": the first call on a context allocates its scratch: make it outside "
-                                                 "graph capture");
-    DeviceGuard guard(ctx->cfg.device);
-    CS_HIP(hipMalloc((void**)&ctx->ppo_partials, bytes));
-  }
-  *out = ctx->ppo_partials;
+int check_hidden(const char* who, const char* field, int value) {
+  if (value < 0 || value > CS_MLP_MAX_HIDDEN)
+    return fail(CS_ERR_ARG, std::string(who) + ": " + field + " " + std::to_string(value) + " is not in [0, " +
+                                std::to_string(CS_MLP_MAX_HIDDEN) + "]");
   return CS_OK;
 }
 

@@ -61,14 +61,14 @@ struct ParamView {
 // (outside stream order: the first call with an override or a parameter gradient allocates)
 int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, ParamView* out);
 
-// (copterstep_api.hip) the context's scratch of cs_mlp_param_grad (copterstep_mlp_grad.hip): `bytes` of workgroup
-// partials, allocated by the first call (refused while `stream` is being captured) and released by cs_destroy
-int mlp_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
-// (copterstep_api.hip) the context's scratch of cs_es_gradient (copterstep_rollout_es.hip), a buffer of its own under the
-// same rules; every call asks for the same `bytes` (the largest population's partials)
-int es_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
-// (copterstep_api.hip) the context's scratch of cs_ppo_grad (copterstep_ppo_grad.hip), a buffer of its own under the
-// same rules; every call asks for the same `bytes` (the widest networks' partials)
-int ppo_grad_scratch(cs_ctx* ctx, const char* who, void* stream, size_t bytes, double** out);
+// (copterstep_api.hip) a context's scratch of workgroup partials, one buffer per user: cs_mlp_param_grad
+// (copterstep_mlp_grad.hip), cs_es_gradient (copterstep_rollout_es.hip) and cs_ppo_grad (copterstep_ppo_grad.hip).
+// `bytes` is what the first call allocates (refused while `stream` is being captured) and cs_destroy releases; every
+// call of a user asks for the same `bytes`, its largest case's partials.
+enum GradScratch { kScratchMlpGrad, kScratchEsGrad, kScratchPpoGrad };
+int grad_scratch(cs_ctx* ctx, GradScratch slot, const char* who, void* stream, size_t bytes, double** out);
+
+// (copterstep_api.hip) the hidden width `value` of the MLP argument blocks' field `field` is in [0, CS_MLP_MAX_HIDDEN]
+int check_hidden(const char* who, const char* field, int value);
 
 }  // namespace cs

@@ -5,13 +5,9 @@
 // The loop replaced: the backward of lander.py:40-65 under a policy, the part of it that a training step needs for the
 // policy's own weights (gym_copter_amd.mlp.param_grad is the same sum as torch matrix products).
 //
-// A split-K "skinny GEMM": the inner dimension is R = K N rows, the output P <= 1092 numbers.  Every wavefront takes
-// tiles of 64 consecutive rows and keeps its share of the output in registers: lane = (row slot s, hidden unit j) with
-// HP = the hidden width rounded up to a power of two and 64 / HP rows in flight; lane (s, j) owns gW1[j][.], gb1[j],
-// gW2[.][j] (and a copy of gb2).  A tile's rows come in coalesced and go through the LDS as float64, so a lane reads its
-// slot's row at a slot-uniform address.  The slots of a wavefront are summed by a fixed shuffle tree, the four
-// wavefronts of a workgroup through the LDS, and each workgroup writes one [P] partial; mlp_grad_sum_kernel adds the
-// partials in a fixed order.  No floating-point atomics: the order of summation depends on (R, shape) alone.
+// The split-K reduction of mlp_grad_kit.h over R = K N rows: lane = (row slot s, hidden unit j), its sums in registers,
+// one [P] partial per workgroup, which mlp_grad_sum_kernel adds in a fixed order.  A tile's 64 consecutive rows come in
+// coalesced and go through the LDS as float64, so a lane reads its slot's row at a slot-uniform address.
 #include <string>
 
 #include "copterstep_jacobian.h"
@@ -19,16 +15,10 @@
 // the sums are explicit fma chains (the arithmetic include/copterstep.h documents), whatever the compiler would contract
 #pragma clang fp contract(off)
 
-#include "wave_sync.h"
+#include "mlp_grad_kit.h"
 
 namespace cs {
 namespace {
-
-constexpr int kGradWaves = 4;                    // wavefronts per workgroup
-constexpr int kGradBlock = 64 * kGradWaves;
-constexpr int kGradChunk = 8;                    // accumulators reduced per pass through the LDS
-constexpr uint32_t kGradMaxGroups = 1024;        // workgroups (= partials) at most: 4 per CU
-constexpr uint32_t kGradMaxParams = CS_MLP_MAX_HIDDEN * (12 + 1) + 4 * (CS_MLP_MAX_HIDDEN + 1);  // Hover3D, H = 64
 
 // HP: 0 = the linear policy (one row per lane), else the hidden width rounded up (8, 16, 32 or 64 lanes per row)
 template <int OBS, int A, int HP>
@@ -38,32 +28,20 @@ __global__ __launch_bounds__(kGradBlock) void mlp_param_grad_kernel(const float*
                                                                     const uint32_t ga_f32, const uint64_t rows,
                                                                     const uint32_t tiles_per_group,
                                                                     const uint32_t P, double* __restrict__ partials) {
-  constexpr int LIVE = HP == 0 ? 1 : HP;  // lanes of a wavefront that hold its sums after the slot reduction
+  constexpr int LIVE = grad_live(HP), NACC = grad_nacc(OBS, A, HP);
   [[maybe_unused]] constexpr int SLOTS = 64 / LIVE;        // (HP > 0) rows in flight per wavefront
-  constexpr int NACC = HP == 0 ? A * (OBS + 1) : OBS + 1 + 2 * A;
   constexpr int ROW = OBS + A;            // float64 values of a staged row
-  constexpr int STAGE = kGradWaves * 64 * ROW, RED = kGradWaves * kGradChunk * 64;
-  __shared__ __attribute__((aligned(16))) double smem[STAGE > RED ? STAGE : RED];
+  constexpr int STAGE = kGradWaves * 64 * ROW;
+  __shared__ __attribute__((aligned(16))) double smem[STAGE > kGradRed ? STAGE : kGradRed];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t tile_index = blockIdx.x;  // (the workgroup: its share of the row tiles, its partial; no state tiles here)
   double* const od = smem + wave * 64 * ROW;  // the wavefront's tile: obs [64][OBS] ...
   double* const gd = od + 64 * OBS;           // ... and g_a [64][A], float64
 
-  // lane (s, j)'s weights in float64: W1[j][.], b1[j], W2[.][j]; zero for the idle lanes j >= H (they add zeros)
+  // lane (s, j)'s weights in float64 and its sums (mlp_grad_kit.h)
   [[maybe_unused]] const int j = HP == 0 ? 0 : lane & (LIVE - 1), s = HP == 0 ? 0 : lane / LIVE;
-  double w1[OBS], b1 = 0.0, w2[A];
-#pragma unroll
-  for (int i = 0; i < OBS; ++i) w1[i] = 0.0;
-#pragma unroll
-  for (int c = 0; c < A; ++c) w2[c] = 0.0;
-  if (HP != 0 && j < H) {
-#pragma unroll
-    for (int i = 0; i < OBS; ++i) w1[i] = (double)params[j * OBS + i];
-    b1 = (double)params[H * OBS + j];
-#pragma unroll
-    for (int c = 0; c < A; ++c) w2[c] = (double)params[H * OBS + H + c * H + j];
-  }
-  // HP > 0: [gW1[j][0..OBS), gb1[j], gW2[0..A)[j], gb2[0..A)];  HP = 0: [gW[c][i] at c OBS + i, gb[c] at A OBS + c]
+  [[maybe_unused]] double w1[OBS], b1, w2[A];
+  grad_lane_weights<OBS, A, HP>(params, H, j, w1, b1, w2);
   double acc[NACC];
 #pragma unroll
   for (int q = 0; q < NACC; ++q) acc[q] = 0.0;
@@ -114,60 +92,14 @@ __global__ __launch_bounds__(kGradBlock) void mlp_param_grad_kernel(const float*
         double pre = b1;
 #pragma unroll
         for (int i = 0; i < OBS; ++i) pre = fma(w1[i], o[i], pre);
-        const double h = tanh(pre);
-        double gh = 0.0;
-#pragma unroll
-        for (int c = 0; c < A; ++c) gh = fma(w2[c], g[c], gh);
-        const double gp = gh * (1.0 - h * h);
-#pragma unroll
-        for (int i = 0; i < OBS; ++i) acc[i] = fma(gp, o[i], acc[i]);
-        acc[OBS] += gp;
-#pragma unroll
-        for (int c = 0; c < A; ++c) {
-          acc[OBS + 1 + c] = fma(g[c], h, acc[OBS + 1 + c]);
-          acc[OBS + 1 + A + c] += g[c];
-        }
+        grad_unit_accumulate<OBS, A>(w2, o, g, tanh(pre), acc);
       }
     }
     wave_sync();  // (the next tile overwrites these rows)
   }
 
-  // ---- the workgroup's partial: the slots of a wavefront by a fixed shuffle tree, the wavefronts through the LDS ----
-  double* const red = smem;  // [kGradWaves][kGradChunk][64]
-  double* const out = partials + (size_t)tile_index * P;
-#pragma unroll
-  for (int q0 = 0; q0 < NACC; q0 += kGradChunk) {
-    __syncthreads();  // (the staged rows, or the previous pass's sums, have been read)
-#pragma unroll
-    for (int ql = 0; ql < kGradChunk; ++ql) {
-      if (q0 + ql < NACC) {
-        double v = acc[q0 + ql];
-#pragma unroll
-        for (int off = 32; off >= LIVE; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane < LIVE) red[(wave * kGradChunk + ql) * 64 + lane] = v;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < kGradChunk * LIVE; idx += kGradBlock) {
-      const int ql = idx / LIVE, jj = idx % LIVE, q = q0 + ql;
-      if (q >= NACC) continue;
-      double t = red[ql * 64 + jj];
-#pragma unroll
-      for (int w = 1; w < kGradWaves; ++w) t += red[(w * kGradChunk + ql) * 64 + jj];
-      if constexpr (HP == 0) {
-        out[q] = t;
-      } else if (jj < H) {  // theta's layout: [W1 (H x OBS), b1 (H), W2 (A x H), b2 (A)]
-        if (q < OBS)
-          out[jj * OBS + q] = t;
-        else if (q == OBS)
-          out[H * OBS + jj] = t;
-        else if (q < OBS + 1 + A)
-          out[H * OBS + H + (q - OBS - 1) * H + jj] = t;
-        else if (jj == 0)
-          out[H * OBS + H + A * H + (q - OBS - 1 - A)] = t;
-      }
-    }
-  }
+  // ---- the workgroup's partial ----
+  grad_partial_reduce<OBS, A, HP>(acc, smem, partials + (size_t)tile_index * P, H);
 }
 
 // g_params[p] = the sum of parameter p's partials in a fixed order: four wavefronts take a quarter of the workgroups
@@ -210,41 +142,20 @@ struct GradArgs {
 
 template <int OBS, int A, int HP>
 hipError_t grad_launch(const GradArgs& a, hipStream_t stream) {
-  const uint64_t tiles = (a.rows + 63) / 64;
-  const uint32_t per_group = (uint32_t)((tiles + kGradMaxGroups - 1) / kGradMaxGroups);
-  const uint32_t groups = (uint32_t)((tiles + per_group - 1) / per_group);
-  hipLaunchKernelGGL((mlp_param_grad_kernel<OBS, A, HP>), dim3(groups), dim3(kGradBlock), 0, stream, a.params, a.hidden,
-                     a.obs, a.g_actions, a.ga_f32, a.rows, per_group, a.P, a.partials);
+  const GradSplit split = grad_split(a.rows);
+  hipLaunchKernelGGL((mlp_param_grad_kernel<OBS, A, HP>), dim3(split.groups), dim3(kGradBlock), 0, stream, a.params,
+                     a.hidden, a.obs, a.g_actions, a.ga_f32, a.rows, split.per_group, a.P, a.partials);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(mlp_grad_sum_kernel, dim3((a.P + 63) / 64), dim3(kGradBlock), 0, stream, a.partials, groups, a.P,
-                     a.g_params);
+  hipLaunchKernelGGL(mlp_grad_sum_kernel, dim3((a.P + 63) / 64), dim3(kGradBlock), 0, stream, a.partials, split.groups,
+                     a.P, a.g_params);
   return hipGetLastError();
 }
 
-template <int OBS, int A>
-hipError_t grad_launch_width(const GradArgs& a, hipStream_t stream) {
-  const int H = a.hidden;
-  if (H == 0) return grad_launch<OBS, A, 0>(a, stream);
-  if (H <= 8) return grad_launch<OBS, A, 8>(a, stream);
-  if (H <= 16) return grad_launch<OBS, A, 16>(a, stream);
-  if (H <= 32) return grad_launch<OBS, A, 32>(a, stream);
-  return grad_launch<OBS, A, 64>(a, stream);
-}
-
 hipError_t launch_mlp_param_grad(int task, const GradArgs& a, hipStream_t stream) {
-  switch (task_obs_dim(task)) {  // the four (OBS, A) shapes of the six tasks
-    case 10:
-      return grad_launch_width<10, 4>(a, stream);
-    case 12:
-      return grad_launch_width<12, 4>(a, stream);
-    case 6:
-      return grad_launch_width<6, 2>(a, stream);
-    case 2:
-      return grad_launch_width<2, 1>(a, stream);
-    default:
-      return hipErrorInvalidValue;
-  }
+  return for_task_shape(task, [&](auto obs, auto act) {
+    return for_grad_width(a.hidden, [&](auto hp) { return grad_launch<obs(), act(), hp()>(a, stream); });
+  });
 }
 
 }  // namespace
@@ -259,9 +170,7 @@ extern "C" int cs_mlp_param_grad(cs_ctx* ctx, const cs_mlp_grad_io* io, void* st
                                          std::to_string(sizeof(cs_mlp_grad_io)) + " (sizeof(cs_mlp_grad_io))").c_str());
   if (io->ga_dtype != CS_JAC_F64 && io->ga_dtype != CS_JAC_F32)
     return cs::report_error(CS_ERR_ARG, (w + ": unknown ga_dtype (CS_JAC_F64 or CS_JAC_F32)").c_str());
-  if (io->hidden < 0 || io->hidden > CS_MLP_MAX_HIDDEN)
-    return cs::report_error(CS_ERR_ARG, (w + ": hidden " + std::to_string(io->hidden) + " is not in [0, " +
-                                         std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
+  if (int rc_ = cs::check_hidden(w.c_str(), "hidden", io->hidden)) return rc_;
   if (io->num_steps < 1) return cs::report_error(CS_ERR_ARG, (w + ": num_steps must be >= 1").c_str());
   if (io->params_dev == nullptr) return cs::report_error(CS_ERR_ARG, (w + ": params_dev is required").c_str());
   if (io->obs_dev == nullptr) return cs::report_error(CS_ERR_ARG, (w + ": obs_dev (the obs tape) is required").c_str());
@@ -270,11 +179,11 @@ extern "C" int cs_mlp_param_grad(cs_ctx* ctx, const cs_mlp_grad_io* io, void* st
   cs::ContextView v;
   if (int rc_ = cs::enter_context(ctx, w.c_str(), stream, &v)) return rc_;
   double* partials = nullptr;
-  if (int rc_ = cs::mlp_grad_scratch(ctx, w.c_str(), stream,
-                                     (size_t)cs::kGradMaxGroups * cs::kGradMaxParams * sizeof(double), &partials))
+  if (int rc_ = cs::grad_scratch(ctx, cs::kScratchMlpGrad, w.c_str(), stream,
+                                 (size_t)cs::kGradMaxGroups * cs::kMlpMaxParams * sizeof(double), &partials))
     return rc_;
-  const int od = cs::task_obs_dim(v.task), ad = cs::task_act_dim(v.task), H = io->hidden;
-  const uint32_t P = (uint32_t)(H == 0 ? ad * (od + 1) : H * (od + 1) + ad * (H + 1));
+  const int H = io->hidden;
+  const uint32_t P = cs::mlp_param_count(cs::task_obs_dim(v.task), cs::task_act_dim(v.task), H);
   const cs::GradArgs a{io->params_dev, H, io->obs_dev, io->g_actions_dev, io->ga_dtype == CS_JAC_F32 ? 1u : 0u,
                        (uint64_t)io->num_steps * v.s->n, P, partials, io->g_params_dev};
   const hipError_t e = cs::launch_mlp_param_grad(v.task, a, (hipStream_t)stream);

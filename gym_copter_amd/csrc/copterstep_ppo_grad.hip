@@ -5,10 +5,8 @@
 // The loop replaced: the body of gym_copter_amd/ppo.py's minibatch loop up to and including loss.backward() -- an index
 // gather of five tapes, two MLP forwards, the loss, two backwards and the masked reductions, a few dozen torch launches.
 //
-// The reduction is copterstep_mlp_grad.hip's split-K layout -- lane = (row slot s, hidden unit j), HP = the width
-// rounded up to a power of two, 64 / HP rows in flight per wavefront, lane (s, j) owning gW1[j][.], gb1[j], gW2[.][j];
-// a fixed shuffle tree over the slots, the LDS over the wavefronts, one partial per workgroup, a fixed-order sum kernel --
-// with three additions: a tile's rows are GATHERED through the minibatch's index (lane l fetches sample l's row with
+// The reduction is cs_mlp_param_grad's split-K layout, from the same header (mlp_grad_kit.h: lane = (row slot s, hidden
+// unit j), one partial per workgroup, a fixed-order sum kernel), with three additions: a tile's rows are GATHERED through the minibatch's index (lane l fetches sample l's row with
 // 8- or 16-byte loads, range-checked in the kernel); the forward runs inside the tile (the outputs are a butterfly over
 // the HP lanes of a slot, after which every lane of the slot holds mu, hence dL/dlogp and g_mu); and the advantage's
 // mean and deviation come from two small passes over the B advantages whose per-workgroup partials every wavefront of the
@@ -22,24 +20,18 @@
 // the sums are explicit fma chains (the arithmetic include/copterstep.h documents), whatever the compiler would contract
 #pragma clang fp contract(off)
 
-#include "wave_sync.h"
+#include "mlp_grad_kit.h"
 
 namespace cs {
 namespace {
 
-constexpr int kGradWaves = 4;                    // wavefronts per workgroup
-constexpr int kGradBlock = 64 * kGradWaves;
-constexpr int kGradChunk = 8;                    // accumulators reduced per pass through the LDS
-constexpr uint32_t kGradMaxGroups = 1024;        // workgroups (= partials) at most: 4 per CU
 constexpr uint32_t kPrepMaxGroups = 256;         // workgroups of the advantage passes at most
-constexpr uint32_t kMaxActor = CS_MLP_MAX_HIDDEN * (12 + 1) + 4 * (CS_MLP_MAX_HIDDEN + 1);  // Hover3D, H = 64
-constexpr uint32_t kMaxCritic = CS_MLP_MAX_HIDDEN * (12 + 1) + (CS_MLP_MAX_HIDDEN + 1);
 constexpr uint32_t kScalars = 8;                 // per-workgroup scalar columns behind the gradient's
 // the scalar columns: sum w Ahat rho', sum w (logp_old - logp), clipped samples, max |rho - 1|, sum w (V - ret)^2
 enum { kScSurr = 0, kScKl = 1, kScClip = 2, kScMax = 3, kScValue = 4 };
 constexpr int kHeadPolicy = 0, kHeadValue = 1;
 // the context's scratch: the partials [kGradMaxGroups][P + Pv + A + kScalars], then the advantage passes' [3][kPrepMaxGroups]
-constexpr size_t kPartialDoubles = (size_t)kGradMaxGroups * (kMaxActor + kMaxCritic + 4 + kScalars);
+constexpr size_t kPartialDoubles = (size_t)kGradMaxGroups * (kMlpMaxParams + kMlpMaxValueParams + 4 + kScalars);
 constexpr size_t kScratchBytes = (kPartialDoubles + 3 * kPrepMaxGroups) * sizeof(double);
 
 struct PpoArgs {
@@ -208,15 +200,14 @@ __device__ __forceinline__ void value_row(const RowConst<A>& k, const double* x,
 template <int OBS, int A, int HP, int HEAD>
 __global__ __launch_bounds__(kGradBlock) void ppo_grad_kernel(const PpoArgs a) {
   constexpr int NOUT = HEAD == kHeadPolicy ? A : 1;  // the network's outputs
-  constexpr int LIVE = HP == 0 ? 1 : HP;   // lanes of a wavefront that hold its sums after the slot reduction
+  constexpr int LIVE = grad_live(HP), NACC = grad_nacc(OBS, NOUT, HP);
   [[maybe_unused]] constexpr int SLOTS = 64 / LIVE;        // (HP > 0) rows in flight per wavefront
-  constexpr int NACC = HP == 0 ? NOUT * (OBS + 1) : OBS + 1 + 2 * NOUT;
   constexpr int NX = HEAD == kHeadPolicy ? A + 3 : 2;      // a row's extras: [a, logp_old, adv, w] or [ret, w]
   constexpr int NSC = HEAD == kHeadPolicy ? A + 4 : 1;     // scalar accumulators: [g_ls, the four statistics] or [sum d^2]
   static_assert(NSC <= kGradChunk, "the scalars are reduced in one pass");
   constexpr int ROW = OBS + NX;            // float64 values of a staged row
-  constexpr int STAGE = HP == 0 ? 0 : kGradWaves * 64 * ROW, RED = kGradWaves * kGradChunk * 64;
-  __shared__ __attribute__((aligned(16))) double smem[STAGE > RED ? STAGE : RED];
+  constexpr int STAGE = HP == 0 ? 0 : kGradWaves * 64 * ROW;
+  __shared__ __attribute__((aligned(16))) double smem[STAGE > kGradRed ? STAGE : kGradRed];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t tile_index = blockIdx.x;  // (the workgroup: its share of the sample tiles, its partial; no state tiles here)
   [[maybe_unused]] double* const rd = smem + wave * 64 * ROW;  // the wavefront's tile: [64][ROW] float64
@@ -247,24 +238,13 @@ __global__ __launch_bounds__(kGradBlock) void ppo_grad_kernel(const PpoArgs a) {
     k.logc = 0.5 * A * 1.8378770664093453;  // ln(2 pi)
   }
 
-  // lane (s, j)'s weights in float64: W1[j][.], b1[j], W2[.][j], and b2; zero for the idle lanes j >= H (they add zeros)
+  // lane (s, j)'s weights in float64 (mlp_grad_kit.h), and b2 for the forward; its sums
   [[maybe_unused]] const int j = HP == 0 ? 0 : lane & (LIVE - 1), s = HP == 0 ? 0 : lane / LIVE;
-  [[maybe_unused]] double w1[OBS], b1 = 0.0, w2[NOUT];
+  [[maybe_unused]] double w1[OBS], b1, w2[NOUT];
   double b2[NOUT];
+  grad_lane_weights<OBS, NOUT, HP>(params, H, j, w1, b1, w2);
 #pragma unroll
-  for (int i = 0; i < OBS; ++i) w1[i] = 0.0;
-#pragma unroll
-  for (int c = 0; c < NOUT; ++c) w2[c] = 0.0;
-  if (HP != 0 && j < H) {
-#pragma unroll
-    for (int i = 0; i < OBS; ++i) w1[i] = (double)params[j * OBS + i];
-    b1 = (double)params[H * OBS + j];
-#pragma unroll
-    for (int c = 0; c < NOUT; ++c) w2[c] = (double)params[H * OBS + H + c * H + j];
-  }
-#pragma unroll
-  for (int c = 0; c < NOUT; ++c) b2[c] = (double)params[HP == 0 ? NOUT * OBS + c : H * OBS + H + NOUT * H + c];
-  // HP > 0: [gW1[j][0..OBS), gb1[j], gW2[0..NOUT)[j], gb2[0..NOUT)];  HP = 0: [gW[c][i] at c OBS + i, gb[c] at NOUT OBS + c]
+  for (int c = 0; c < NOUT; ++c) b2[c] = (double)params[HP == 0 ? NOUT * OBS + c : mlp_layout(OBS, NOUT, H).b2 + c];
   double acc[NACC], sc[NSC];
 #pragma unroll
   for (int q = 0; q < NACC; ++q) acc[q] = 0.0;
@@ -346,60 +326,16 @@ __global__ __launch_bounds__(kGradBlock) void ppo_grad_kernel(const PpoArgs a) {
           policy_row<A>(k, rx, out, g, sc);
         else
           value_row<A>(k, rx, out, g, sc);
-        double gh = 0.0;
-#pragma unroll
-        for (int c = 0; c < NOUT; ++c) gh = fma(w2[c], g[c], gh);
-        const double gp = gh * (1.0 - h * h);
-#pragma unroll
-        for (int v = 0; v < OBS; ++v) acc[v] = fma(gp, ro[v], acc[v]);
-        acc[OBS] += gp;
-#pragma unroll
-        for (int c = 0; c < NOUT; ++c) {
-          acc[OBS + 1 + c] = fma(g[c], h, acc[OBS + 1 + c]);
-          acc[OBS + 1 + NOUT + c] += g[c];
-        }
+        grad_unit_accumulate<OBS, NOUT>(w2, ro, g, h, acc);
       }
       wave_sync();  // (the next tile overwrites these rows)
     }
   }
 
-  // ---- the workgroup's partial: the slots of a wavefront by a fixed shuffle tree, the wavefronts through the LDS ----
+  // ---- the workgroup's partial, this head's columns of it ----
   double* const red = smem;  // [kGradWaves][kGradChunk][64]
   double* const part = a.partials + (size_t)tile_index * a.stride;
-  double* const out = part + a.offset;
-#pragma unroll
-  for (int q0 = 0; q0 < NACC; q0 += kGradChunk) {
-    __syncthreads();  // (the staged rows, or the previous pass's sums, have been read)
-#pragma unroll
-    for (int ql = 0; ql < kGradChunk; ++ql) {
-      if (q0 + ql < NACC) {
-        double v = acc[q0 + ql];
-#pragma unroll
-        for (int off = 32; off >= LIVE; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane < LIVE) red[(wave * kGradChunk + ql) * 64 + lane] = v;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < kGradChunk * LIVE; idx += kGradBlock) {
-      const int ql = idx / LIVE, jj = idx % LIVE, q = q0 + ql;
-      if (q >= NACC) continue;
-      double t = red[ql * 64 + jj];
-#pragma unroll
-      for (int w = 1; w < kGradWaves; ++w) t += red[(w * kGradChunk + ql) * 64 + jj];
-      if constexpr (HP == 0) {
-        out[q] = t;
-      } else if (jj < H) {  // theta's layout: [W1 (H x OBS), b1 (H), W2 (NOUT x H), b2 (NOUT)]
-        if (q < OBS)
-          out[jj * OBS + q] = t;
-        else if (q == OBS)
-          out[H * OBS + jj] = t;
-        else if (q < OBS + 1 + NOUT)
-          out[H * OBS + H + (q - OBS - 1) * H + jj] = t;
-        else if (jj == 0)
-          out[H * OBS + H + NOUT * H + (q - OBS - 1 - NOUT)] = t;
-      }
-    }
-  }
+  grad_partial_reduce<OBS, NOUT, HP>(acc, red, part + a.offset, H);
   // ---- the scalars, which every lane of a slot holds alike: lane j = 0 of each slot counts, the same two levels; the
   // largest |rho - 1| is a maximum, not a sum ----
   __syncthreads();
@@ -492,28 +428,17 @@ __global__ __launch_bounds__(kGradBlock) void ppo_grad_sum_kernel(const double* 
 
 template <int OBS, int A, int HEAD>
 hipError_t head_launch(const PpoArgs& a, uint32_t groups, hipStream_t stream) {
-  const int H = a.hidden;
-  const dim3 grid(groups), block(kGradBlock);
-  if (H == 0)
-    hipLaunchKernelGGL((ppo_grad_kernel<OBS, A, 0, HEAD>), grid, block, 0, stream, a);
-  else if (H <= 8)
-    hipLaunchKernelGGL((ppo_grad_kernel<OBS, A, 8, HEAD>), grid, block, 0, stream, a);
-  else if (H <= 16)
-    hipLaunchKernelGGL((ppo_grad_kernel<OBS, A, 16, HEAD>), grid, block, 0, stream, a);
-  else if (H <= 32)
-    hipLaunchKernelGGL((ppo_grad_kernel<OBS, A, 32, HEAD>), grid, block, 0, stream, a);
-  else
-    hipLaunchKernelGGL((ppo_grad_kernel<OBS, A, 64, HEAD>), grid, block, 0, stream, a);
-  return hipGetLastError();
+  return for_grad_width(a.hidden, [&](auto hp) {
+    hipLaunchKernelGGL((ppo_grad_kernel<OBS, A, hp(), HEAD>), dim3(groups), dim3(kGradBlock), 0, stream, a);
+    return hipGetLastError();
+  });
 }
-
-uint32_t mlp_params(int od, int ad, int H) { return (uint32_t)(H == 0 ? ad * (od + 1) : H * (od + 1) + ad * (H + 1)); }
 
 template <int OBS, int A>
 hipError_t ppo_launch(const cs_ppo_grad_io& io, double* scratch, hipStream_t stream) {
   const uint64_t B = (uint64_t)io.num_samples, R = (uint64_t)io.num_rows;
   const bool critic = io.critic_dev != nullptr;
-  const uint32_t P = mlp_params(OBS, A, io.hidden), Pv = critic ? mlp_params(OBS, 1, io.critic_hidden) : 0u;
+  const uint32_t P = mlp_param_count(OBS, A, io.hidden), Pv = critic ? mlp_param_count(OBS, 1, io.critic_hidden) : 0u;
   const uint32_t ngrad = P + Pv + A, stride = ngrad + kScalars;
   double* const partials = scratch;
   double* const prep = scratch + kPartialDoubles;
@@ -529,9 +454,8 @@ hipError_t ppo_launch(const cs_ppo_grad_io& io, double* scratch, hipStream_t str
                        io.live_dev, io.index_dev, io.row_base, R, B, prep);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
-  const uint64_t tiles = (B + 63) / 64;
-  const uint32_t per_group = (uint32_t)((tiles + kGradMaxGroups - 1) / kGradMaxGroups);
-  const uint32_t groups = (uint32_t)((tiles + per_group - 1) / per_group);
+  const GradSplit split = grad_split(B);
+  const uint32_t groups = split.groups;
   PpoArgs a{};
   a.params = io.actor_dev;
   a.log_std = io.log_std_dev;
@@ -552,7 +476,7 @@ hipError_t ppo_launch(const cs_ppo_grad_io& io, double* scratch, hipStream_t str
   a.hidden = io.hidden;
   a.prep_groups = prep_groups;
   a.normalize = io.normalize;
-  a.tiles_per_group = per_group;
+  a.tiles_per_group = split.per_group;
   a.stride = stride;
   a.offset = 0;
   a.ls_offset = P + Pv;
@@ -571,18 +495,7 @@ hipError_t ppo_launch(const cs_ppo_grad_io& io, double* scratch, hipStream_t str
 }
 
 hipError_t launch_ppo_grad(int task, const cs_ppo_grad_io& io, double* scratch, hipStream_t stream) {
-  switch (task_obs_dim(task)) {  // the four (OBS, A) shapes of the six tasks
-    case 10:
-      return ppo_launch<10, 4>(io, scratch, stream);
-    case 12:
-      return ppo_launch<12, 4>(io, scratch, stream);
-    case 6:
-      return ppo_launch<6, 2>(io, scratch, stream);
-    case 2:
-      return ppo_launch<2, 1>(io, scratch, stream);
-    default:
-      return hipErrorInvalidValue;
-  }
+  return for_task_shape(task, [&](auto obs, auto act) { return ppo_launch<obs(), act()>(io, scratch, stream); });
 }
 
 bool misaligned(const void* p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
@@ -593,12 +506,8 @@ int check_ppo_io(const cs_ppo_grad_io* io, const std::string& w) {
   if (io->struct_size != sizeof(cs_ppo_grad_io))
     return report_error(CS_ERR_ABI, (w + ": pio->struct_size " + std::to_string(io->struct_size) + " != " +
                                      std::to_string(sizeof(cs_ppo_grad_io)) + " (sizeof(cs_ppo_grad_io))").c_str());
-  if (io->hidden < 0 || io->hidden > CS_MLP_MAX_HIDDEN)
-    return report_error(CS_ERR_ARG, (w + ": hidden " + std::to_string(io->hidden) + " is not in [0, " +
-                                     std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
-  if (io->critic_hidden < 0 || io->critic_hidden > CS_MLP_MAX_HIDDEN)
-    return report_error(CS_ERR_ARG, (w + ": critic_hidden " + std::to_string(io->critic_hidden) + " is not in [0, " +
-                                     std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
+  if (int rc_ = check_hidden(w.c_str(), "hidden", io->hidden)) return rc_;
+  if (int rc_ = check_hidden(w.c_str(), "critic_hidden", io->critic_hidden)) return rc_;
   if (io->normalize > 1u) return report_error(CS_ERR_ARG, (w + ": normalize must be 0 or 1").c_str());
   if (io->num_rows < 1) return report_error(CS_ERR_ARG, (w + ": num_rows must be >= 1").c_str());
   if (io->num_samples < 1) return report_error(CS_ERR_ARG, (w + ": num_samples must be >= 1").c_str());
@@ -638,7 +547,7 @@ extern "C" int cs_ppo_grad(cs_ctx* ctx, const cs_ppo_grad_io* pio, void* stream)
   cs::ContextView v;
   if (int rc_ = cs::enter_context(ctx, w.c_str(), stream, &v)) return rc_;  // (refuses an open served session)
   double* scratch = nullptr;
-  if (int rc_ = cs::ppo_grad_scratch(ctx, w.c_str(), stream, cs::kScratchBytes, &scratch)) return rc_;
+  if (int rc_ = cs::grad_scratch(ctx, cs::kScratchPpoGrad, w.c_str(), stream, cs::kScratchBytes, &scratch)) return rc_;
   const hipError_t e = cs::launch_ppo_grad(v.task, *pio, scratch, (hipStream_t)stream);
   if (e != hipSuccess) return cs::report_hip(e, (w + ": kernel launch").c_str());
   return CS_OK;

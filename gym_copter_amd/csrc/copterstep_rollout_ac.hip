@@ -18,7 +18,7 @@
 #include "copterstep_jacobian.h"
 
 // the step must round as the step kernels do (copterstep_kernels.hip), and the policy's float32 arithmetic is
-// cs_rollout_mlp_states': the explicit fmaf chains below, nothing contracted
+// cs_rollout_mlp_states': the explicit fmaf chains of mlp_policy.h, nothing contracted
 #pragma clang fp contract(off)
 
 #include "dev_tile.h"
@@ -30,6 +30,7 @@
 #include "dev_task.h"
 #include "dev_pid.h"
 #include "ppo_noise.h"
+#include "mlp_policy.h"
 #include "dev_launch.h"
 
 namespace cs {
@@ -51,47 +52,6 @@ struct AcArgs {
   int num_steps, hidden, critic_hidden;
   uint32_t key, nonce, deterministic;
 };
-
-// A weight: the address is wave-uniform, and the constant address space lets the compiler fetch it with a scalar load
-// (the parameters are never written by these kernels).
-typedef __attribute__((address_space(4))) const float ConstF32;
-__device__ __forceinline__ float weight(const float* p, int idx) { return ((ConstF32*)p)[idx]; }
-
-// pi_theta(o) in float32: mlp_forward of copterstep_rollout_mlp.hip, operation for operation (every sum an fmaf chain
-// from the bias in index order, the device library's tanhf, streamed over the hidden units)
-template <int OBS, int A>
-__device__ __forceinline__ void mlp_forward(const float* P, int H, const float (&o)[OBS], float (&a)[A]) {
-  if (H == 0) {  // [W (A x OBS), b (A)]
-#pragma unroll
-    for (int c = 0; c < A; ++c) {
-      float s = weight(P, A * OBS + c);
-#pragma unroll
-      for (int j = 0; j < OBS; ++j) s = fmaf(weight(P, c * OBS + j), o[j], s);
-      a[c] = s;
-    }
-    return;
-  }
-  const int b1 = H * OBS, w2 = b1 + H, b2 = w2 + A * H;  // [W1 (H x OBS), b1 (H), W2 (A x H), b2 (A)]
-#pragma unroll
-  for (int c = 0; c < A; ++c) a[c] = weight(P, b2 + c);
-#pragma clang loop unroll(disable)
-  for (int h = 0; h < H; ++h) {
-    float pre = weight(P, b1 + h);
-#pragma unroll
-    for (int j = 0; j < OBS; ++j) pre = fmaf(weight(P, h * OBS + j), o[j], pre);
-    const float t = tanhf(pre);
-#pragma unroll
-    for (int c = 0; c < A; ++c) a[c] = fmaf(weight(P, w2 + c * H + h), t, a[c]);
-  }
-}
-
-// the action as advance() takes it (load_action_at's fan-out of the task's A columns onto the four motors)
-template <int A>
-__device__ __forceinline__ float4 motors_of(const float (&a)[A]) {
-  if constexpr (A == 4) return make_float4(a[0], a[1], a[2], a[3]);
-  else if constexpr (A == 2) return make_float4(a[0], a[1], a[1], a[0]);
-  else return make_float4(a[0], a[0], a[0], a[0]);
-}
 
 // one float32 row of W values of this lane, [.., N, W] at env `at` (64-bit): one 16 / 8 / 4-byte store where W allows
 template <int W>
@@ -300,12 +260,8 @@ int check_ac_io(const cs_rollout_ac_io* aio, const char* who) {
     return report_error(CS_ERR_ABI, (w + ": aio->struct_size " + std::to_string(aio->struct_size) + " != " +
                                      std::to_string(sizeof(cs_rollout_ac_io)) + " (sizeof(cs_rollout_ac_io))").c_str());
   if (aio->num_steps < 1) return report_error(CS_ERR_ARG, (w + ": num_steps must be >= 1").c_str());
-  if (aio->hidden < 0 || aio->hidden > CS_MLP_MAX_HIDDEN)
-    return report_error(CS_ERR_ARG, (w + ": hidden " + std::to_string(aio->hidden) + " is not in [0, " +
-                                     std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
-  if (aio->critic_hidden < 0 || aio->critic_hidden > CS_MLP_MAX_HIDDEN)
-    return report_error(CS_ERR_ARG, (w + ": critic_hidden " + std::to_string(aio->critic_hidden) + " is not in [0, " +
-                                     std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
+  if (int rc_ = check_hidden(who, "hidden", aio->hidden)) return rc_;
+  if (int rc_ = check_hidden(who, "critic_hidden", aio->critic_hidden)) return rc_;
   if (aio->deterministic > 1u) return report_error(CS_ERR_ARG, (w + ": deterministic must be 0 or 1").c_str());
   if (aio->actor_dev == nullptr) return report_error(CS_ERR_ARG, (w + ": actor_dev is required").c_str());
   if (aio->log_std_dev == nullptr) return report_error(CS_ERR_ARG, (w + ": log_std_dev is required").c_str());

@@ -30,6 +30,7 @@
 #include "rollout_adjoint.h"
 #include "rollout_step.h"
 #include "es_noise.h"
+#include "mlp_policy.h"
 #include "dev_launch.h"
 
 namespace cs {
@@ -48,51 +49,6 @@ struct PopArgs {
   int hidden;
 };
 
-// A member's weights: the address is wave-uniform and in the constant address space, so the compiler fetches it with
-// scalar loads (copterstep_rollout_mlp.hip's path; the table is never written by these kernels).  Staging the row in the
-// LDS was measured and lost.
-typedef __attribute__((address_space(4))) const float ConstF32;
-struct Weights {
-  const float* w;
-  __device__ __forceinline__ float operator()(int idx) const { return ((ConstF32*)w)[idx]; }
-};
-
-// pi_theta(o) in float32: mlp_forward of copterstep_rollout_mlp.hip, operation for operation (every sum an fmaf chain
-// from the bias in index order, the device library's tanhf, streamed over the hidden units)
-template <int OBS, int A>
-__device__ __forceinline__ void mlp_forward(const Weights weight, int H, const float (&o)[OBS], float (&a)[A]) {
-  if (H == 0) {  // [W (A x OBS), b (A)]
-#pragma unroll
-    for (int c = 0; c < A; ++c) {
-      float s = weight(A * OBS + c);
-#pragma unroll
-      for (int j = 0; j < OBS; ++j) s = fmaf(weight(c * OBS + j), o[j], s);
-      a[c] = s;
-    }
-    return;
-  }
-  const int b1 = H * OBS, w2 = b1 + H, b2 = w2 + A * H;  // [W1 (H x OBS), b1 (H), W2 (A x H), b2 (A)]
-#pragma unroll
-  for (int c = 0; c < A; ++c) a[c] = weight(b2 + c);
-#pragma clang loop unroll(disable)
-  for (int h = 0; h < H; ++h) {
-    float pre = weight(b1 + h);
-#pragma unroll
-    for (int j = 0; j < OBS; ++j) pre = fmaf(weight(h * OBS + j), o[j], pre);
-    const float t = tanhf(pre);
-#pragma unroll
-    for (int c = 0; c < A; ++c) a[c] = fmaf(weight(w2 + c * H + h), t, a[c]);
-  }
-}
-
-// the action as rollout_step takes it (load_action_at's fan-out of the task's A columns onto the four motors)
-template <int A>
-__device__ __forceinline__ float4 motors_of(const float (&a)[A]) {
-  if constexpr (A == 4) return make_float4(a[0], a[1], a[2], a[3]);
-  else if constexpr (A == 2) return make_float4(a[0], a[1], a[1], a[0]);
-  else return make_float4(a[0], a[0], a[0], a[0]);
-}
-
 // 3 wavefronts per SIMD: the kernel needs 163 VGPRs without its tapes' staging, and with per-wavefront weights the
 // third wavefront covers their scalar-load misses: 4 929 against 6 177 us at 2^20 envs, H = 32, K = 64
 // (profiles/rollout_es_bench.txt, rows "default" and "waves2").
@@ -106,9 +62,8 @@ void rollout_mlp_population_kernel(const DevConst c, const DevState s, const cs_
   const uint32_t i = tile_index * kBlock + threadIdx.x;
   const uint32_t n = s.n;
   const bool valid = i < n;
-  // the wavefront's member: a function of blockIdx alone
-  const float* const row = m.table + (size_t)((tile_index * (uint32_t)kBlock) / m.E) * m.P;
-  const Weights weight{row};
+  // the wavefront's member: its row of the table is a function of blockIdx alone, so its weights are wave-uniform
+  const float* const theta = m.table + (size_t)((tile_index * (uint32_t)kBlock) / m.E) * m.P;
 
   Coef q = uniform_coef(c);
   if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, valid ? i : 0u);
@@ -136,7 +91,7 @@ void rollout_mlp_population_kernel(const DevConst c, const DevState s, const cs_
     float o[OBS], a[A];
 #pragma unroll
     for (int j = 0; j < OBS; ++j) o[j] = (float)e.x[FIRST + j];
-    mlp_forward<OBS, A>(weight, m.hidden, o, a);
+    mlp_forward<OBS, A>(theta, m.hidden, o, a);
 
     const bool resetting = e.reset_pending;
     double reward;
@@ -201,9 +156,9 @@ hipError_t launch_population(int task, int mode, const DevConst& c, const DevSta
 // ---- the mirrored population and the search gradient ----
 constexpr int kEsBlock = 256;
 constexpr uint32_t kEsMaxChunks = CS_ES_MAX_MEMBERS / 2 / CS_ES_PAIR_CHUNK;
-// the context's scratch of partial sums (es_grad_scratch): [chunks, P] of the largest population and policy, 8.9 MB
+// the context's scratch of partial sums (grad_scratch): [chunks, P] of the largest population and policy, 8.9 MB
 constexpr size_t kEsScratchBytes = (size_t)kEsMaxChunks * CS_ES_MAX_PARAMS * sizeof(double);
-static_assert(CS_ES_MAX_PARAMS == CS_MLP_MAX_HIDDEN * (12 + 1) + 4 * (CS_MLP_MAX_HIDDEN + 1), "Hover3D, H = 64");
+static_assert(CS_ES_MAX_PARAMS == kMlpMaxParams, "Hover3D, H = 64");
 
 // table[2i] = theta + sigma eps_i, table[2i+1] = theta - sigma eps_i: the pair in grid x, 256 parameters per workgroup in y
 __global__ __launch_bounds__(kEsBlock) void es_perturb_kernel(const float* __restrict__ theta, float* __restrict__ table,
@@ -274,9 +229,7 @@ int check_population_io(const cs_rollout_io* io, const cs_rollout_population_io*
     return report_error(CS_ERR_ABI, (w + ": pio->struct_size " + std::to_string(pio->struct_size) + " != " +
                                      std::to_string(sizeof(cs_rollout_population_io)) +
                                      " (sizeof(cs_rollout_population_io))").c_str());
-  if (pio->hidden < 0 || pio->hidden > CS_MLP_MAX_HIDDEN)
-    return report_error(CS_ERR_ARG, (w + ": hidden " + std::to_string(pio->hidden) + " is not in [0, " +
-                                     std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
+  if (int rc_ = check_hidden(who, "hidden", pio->hidden)) return rc_;
   if (pio->members < 1) return report_error(CS_ERR_ARG, (w + ": members must be >= 1").c_str());
   if (pio->envs_per_member < 64 || pio->envs_per_member % 64 != 0)
     return report_error(CS_ERR_ARG, (w + ": envs_per_member " + std::to_string(pio->envs_per_member) +
@@ -328,8 +281,8 @@ extern "C" int cs_rollout_mlp_population(cs_ctx* ctx, const cs_rollout_io* io, c
     return cs::report_error(CS_ERR_ARG, (std::string(who) + ": members x envs_per_member = " + std::to_string(M) +
                                          " x " + std::to_string(E) + " is not the context's " +
                                          std::to_string(v.s->n) + " envs").c_str());
-  const int od = cs::task_obs_dim(v.task), ad = cs::task_act_dim(v.task), H = pio->hidden;
-  const uint32_t P = (uint32_t)(H == 0 ? ad * (od + 1) : H * (od + 1) + ad * (H + 1));
+  const int H = pio->hidden;
+  const uint32_t P = cs::mlp_param_count(cs::task_obs_dim(v.task), cs::task_act_dim(v.task), H);
   const cs::PopArgs m{pio->params_table_dev, pio->returns_dev, pio->lengths_dev, pio->end_flags_dev,
                       pio->end_status_dev,   pio->member_returns_dev, pio->gamma, E, P, H};
   hipError_t e = cs::launch_population(v.task, v.mode, *v.c, *v.s, *io, m, (hipStream_t)stream);
@@ -363,7 +316,7 @@ extern "C" int cs_es_gradient(cs_ctx* ctx, const cs_es_io* eio, void* stream) {
   cs::ContextView v;
   if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
   double* partials = nullptr;
-  if (int rc_ = cs::es_grad_scratch(ctx, who, stream, cs::kEsScratchBytes, &partials)) return rc_;
+  if (int rc_ = cs::grad_scratch(ctx, cs::kScratchEsGrad, who, stream, cs::kEsScratchBytes, &partials)) return rc_;
   const uint32_t pairs = (uint32_t)eio->members / 2u, P = (uint32_t)eio->num_params;
   const uint32_t chunks = (pairs + CS_ES_PAIR_CHUNK - 1) / CS_ES_PAIR_CHUNK, tiles = (P + cs::kBlock - 1) / cs::kBlock;
   hipLaunchKernelGGL(cs::es_gradient_kernel, dim3(tiles, chunks), dim3(cs::kBlock), 0, (hipStream_t)stream,

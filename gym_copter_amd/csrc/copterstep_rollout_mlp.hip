@@ -17,7 +17,7 @@
 #include "copterstep_jacobian.h"
 
 // the primal must round as the step kernels do (copterstep_kernels.hip), and the policy's float32 arithmetic is the
-// explicit fmaf chain below, whatever the compiler would contract
+// explicit fmaf chain of mlp_policy.h, whatever the compiler would contract
 #pragma clang fp contract(off)
 
 #include "dev_tile.h"
@@ -29,6 +29,7 @@
 #include "rollout_adjoint.h"
 #include "rollout_step.h"
 #include "rollout_sweep.h"
+#include "mlp_policy.h"
 #include "dev_launch.h"
 
 namespace cs {
@@ -42,73 +43,6 @@ struct MlpArgs {
   float* obs;            // [K,N,OBS] the observation tape, or nullptr
   int hidden;            // 0 .. CS_MLP_MAX_HIDDEN
 };
-
-// A weight: the address is wave-uniform, and the constant address space lets the compiler fetch it with a scalar load
-// (the params are never written by these kernels).
-typedef __attribute__((address_space(4))) const float ConstF32;
-__device__ __forceinline__ float weight(const float* p, int idx) { return ((ConstF32*)p)[idx]; }
-
-// pi_theta(o) in float32, the arithmetic include/copterstep.h documents: every sum an fmaf chain that starts from the
-// bias and adds the terms in index order; tanhf the device library's.  Streams over the hidden units (pre_j -> h_j ->
-// a[0..A) += W2[., j] h_j).
-template <int OBS, int A>
-__device__ __forceinline__ void mlp_forward(const float* P, int H, const float (&o)[OBS], float (&a)[A]) {
-  if (H == 0) {  // [W (A x OBS), b (A)]
-#pragma unroll
-    for (int c = 0; c < A; ++c) {
-      float s = weight(P, A * OBS + c);
-#pragma unroll
-      for (int j = 0; j < OBS; ++j) s = fmaf(weight(P, c * OBS + j), o[j], s);
-      a[c] = s;
-    }
-    return;
-  }
-  const int b1 = H * OBS, w2 = b1 + H, b2 = w2 + A * H;  // [W1 (H x OBS), b1 (H), W2 (A x H), b2 (A)]
-#pragma unroll
-  for (int c = 0; c < A; ++c) a[c] = weight(P, b2 + c);
-#pragma clang loop unroll(disable)
-  for (int h = 0; h < H; ++h) {
-    float pre = weight(P, b1 + h);
-#pragma unroll
-    for (int j = 0; j < OBS; ++j) pre = fmaf(weight(P, h * OBS + j), o[j], pre);
-    const float t = tanhf(pre);
-#pragma unroll
-    for (int c = 0; c < A; ++c) a[c] = fmaf(weight(P, w2 + c * H + h), t, a[c]);
-  }
-}
-
-// lam[FIRST + j] += (J_o pi(o)^T ga)_j in float64: o = the float32 observation of x (its rounding straight-through), the
-// hidden units recomputed in float64 (tanh' = 1 - h^2).  Streams over the hidden units as mlp_forward does.
-template <int TASK>
-__device__ __forceinline__ void mlp_vjp(const float* P, int H, const double (&x)[12], const double (&ga)[4],
-                                        double (&lam)[12]) {
-  constexpr int OBS = task_obs_dim(TASK), FIRST = task_obs_first(TASK), A = task_act_dim(TASK);
-  double o[OBS];
-#pragma unroll
-  for (int j = 0; j < OBS; ++j) o[j] = (double)(float)x[FIRST + j];
-  if (H == 0) {
-#pragma unroll
-    for (int c = 0; c < A; ++c) {
-#pragma unroll
-      for (int j = 0; j < OBS; ++j) lam[FIRST + j] = fma((double)weight(P, c * OBS + j), ga[c], lam[FIRST + j]);
-    }
-    return;
-  }
-  const int b1 = H * OBS, w2 = b1 + H;
-#pragma clang loop unroll(disable)
-  for (int h = 0; h < H; ++h) {
-    double pre = (double)weight(P, b1 + h);
-#pragma unroll
-    for (int j = 0; j < OBS; ++j) pre = fma((double)weight(P, h * OBS + j), o[j], pre);
-    const double t = tanh(pre);
-    double gh = 0.0;
-#pragma unroll
-    for (int c = 0; c < A; ++c) gh = fma((double)weight(P, w2 + c * H + h), ga[c], gh);
-    const double gp = gh * (1.0 - t * t);
-#pragma unroll
-    for (int j = 0; j < OBS; ++j) lam[FIRST + j] = fma(gp, (double)weight(P, h * OBS + j), lam[FIRST + j]);
-  }
-}
 
 // One float32 row of W values per lane, [.., N, W] at row `row` (64-bit): a whole wavefront's 64 rows are contiguous
 // and go out through the LDS as 16 B stores (64 W floats = 16 W float4), a partial one lane by lane.
@@ -136,14 +70,6 @@ __device__ __forceinline__ void store_row_f32(float* lds, float* base, size_t ro
 #pragma unroll
     for (int j = 0; j < W; ++j) dst[j] = v[j];
   }
-}
-
-// the action as rollout_step takes it (load_action_at's fan-out of the task's A columns onto the four motors)
-template <int A>
-__device__ __forceinline__ float4 motors_of(const float (&a)[A]) {
-  if constexpr (A == 4) return make_float4(a[0], a[1], a[2], a[3]);
-  else if constexpr (A == 2) return make_float4(a[0], a[1], a[1], a[0]);
-  else return make_float4(a[0], a[0], a[0], a[0]);
 }
 
 // The closed-loop forward keeps its own loop: rollout_forward (rollout_sweep.h) with the policy as its action source
@@ -329,9 +255,7 @@ int check_rollout_io_mlp(const cs_rollout_io* io, const cs_rollout_mlp_io* mio, 
   if (mio->struct_size != sizeof(cs_rollout_mlp_io))
     return report_error(CS_ERR_ABI, (w + ": mio->struct_size " + std::to_string(mio->struct_size) + " != " +
                                      std::to_string(sizeof(cs_rollout_mlp_io)) + " (sizeof(cs_rollout_mlp_io))").c_str());
-  if (mio->hidden < 0 || mio->hidden > CS_MLP_MAX_HIDDEN)
-    return report_error(CS_ERR_ARG, (w + ": hidden " + std::to_string(mio->hidden) + " is not in [0, " +
-                                     std::to_string(CS_MLP_MAX_HIDDEN) + "]").c_str());
+  if (int rc_ = check_hidden(who, "hidden", mio->hidden)) return rc_;
   if (mio->params_dev == nullptr) return report_error(CS_ERR_ARG, (w + ": params_dev is required").c_str());
   if (mio->actions_out_dev == nullptr)
     return report_error(CS_ERR_ARG, (w + ": actions_out_dev (the action tape) is required").c_str());
