@@ -91,7 +91,7 @@ def _against_reference(task, substeps, mode="float64", vehicles=False, mars=Fals
 
 
 @pytest.mark.parametrize("substeps", [1, 10])
-@pytest.mark.parametrize("task", ["lander3d", "hover3d", "lander2d", "hover1d"])
+@pytest.mark.parametrize("task", ["lander3d", "hover3d", "lander2d", "hover1d", "lander1d", "hover2d"])
 def test_jacobian_matches_central_differences_of_the_reference(task, substeps):
     _against_reference(task, substeps, force=(substeps == 10))
 

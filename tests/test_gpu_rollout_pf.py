@@ -19,7 +19,7 @@ from oracle.refcpu import AIRBORNE, CRASHED, LANDED
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not have_gpu(), reason="needs a HIP device")]
 
-TASK_A = {"lander3d": 4, "hover3d": 4, "lander2d": 2, "hover1d": 1}
+TASK_A = {"lander3d": 4, "hover3d": 4, "lander2d": 2, "hover2d": 2, "lander1d": 1, "hover1d": 1}
 AH = hover_action()
 N, K = pf_ref.TEST_N, pf_ref.TEST_K
 SEED = 3
@@ -74,12 +74,15 @@ def _particle_env(task, P, substeps, variant=None, installed=None, mode="float64
     return env
 
 
-def _check_steps(name, env, penv, p, res, P, exact=True, first_step=1, start=None):
-    """every step of res (a tape=True result, cloned) against the reference from the device's own tapes; returns the
-    status tape [K,N,P] and the resampled flags"""
+WORST = {}
+
+
+def _check_steps(name, env, penv, p, res, P, exact=True, first_step=1, start=None, g=None):
+    """every step of res (a tape=True result, cloned) against the reference from the device's own tapes; g: the global
+    ids of env's lanes (env_id_base + lane; default base 0); returns the status tape [K,N,P] and the resampled flags"""
     import torch
     steps = res.x.shape[0]
-    g = np.arange(N)
+    g = np.arange(N) if g is None else np.asarray(g, np.int64)
     H, r, nonce = p["H"], p["r"], p["nonce"]
     Lq = pf_ref.factor_q(p["Q"])
     if start is None:
@@ -153,6 +156,7 @@ def _check_steps(name, env, penv, p, res, P, exact=True, first_step=1, start=Non
     worst["loglik"] = e / llbar
     assert e <= llbar, (name, "loglik", e, llbar)
     assert np.array_equal(to_np(res.ok), ok)
+    WORST[name] = worst
     print("%s: worst ratio to the bar " % name + " ".join("%s %.3f" % kv for kv in worst.items()))
     return pst, to_np(res.resampled), wqt
 
@@ -160,7 +164,7 @@ def _check_steps(name, env, penv, p, res, P, exact=True, first_step=1, start=Non
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. every step, through a touchdown that splits the particles
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("P,substeps", [(64, 1), (256, 10), (1024, 1), (1024, 10)])
+@pytest.mark.parametrize("P,substeps", [(64, 1), (128, 1), (256, 10), (512, 10), (1024, 1), (1024, 10)])
 def test_every_step_on_the_devices_own_tapes(P, substeps):
     import torch
     rng = np.random.default_rng(900 + P + substeps)
@@ -199,6 +203,87 @@ def test_every_step_on_the_devices_own_tapes(P, substeps):
         after = env.get_state()
         for key in before:
             assert np.array_equal(np.asarray(before[key]), np.asarray(after[key]), equal_nan=True), key
+    finally:
+        env.close()
+        penv.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1b. the draws away from global id 0 and from small steps; ess_frac at both ends
+# ---------------------------------------------------------------------------------------------------------------------
+def test_draws_follow_the_global_env_id_up_to_the_last_one():
+    """env_id_base = 2^32 - N, the largest cs_create admits: the last lane's id is 2^32 - 1, where pf_ref.words is pinned
+    to the host build of pf_noise.h (test_rollout_pf_cpu.py).  Then a shard of two lanes with base + 3: what lanes 3 and
+    4 of the whole batch give, bit for bit, whatever the batch size."""
+    import torch
+    P = 128
+    base = 2 ** 32 - N
+    rng = np.random.default_rng(941)
+    env = _env("lander3d", N, env_id_base=base)
+    shard = _env("lander3d", 2, env_id_base=base + 3)
+    penv = _particle_env("lander3d", P, 1)
+    try:
+        env.reset()
+        shard.reset()
+        p = _problem(env, "lander3d", rng)
+        res = _clone(_run(env, p, P))
+        _check_steps("lander3d ids from 2^32 - %d" % N, env, penv, p, res, P, g=base + np.arange(N))
+        cut = lambda t, lanes_first: (t[3:5] if lanes_first else t[:, 3:5]).contiguous()      # noqa: E731
+        p2 = dict(p, acts=cut(p["acts"], False), z=cut(p["z"], False), x0=cut(p["x0"], False), P0=cut(p["P0"], True),
+                  st0=cut(p["st0"], True))
+        part = _run(shard, p2, P)
+        for nm, a, b in zip(res._fields, part, res):
+            assert a.shape[0] in (2, K) and b.shape[0] in (N, K), nm
+            assert torch.equal(a, cut(b, b.shape[0] == N)), nm
+    finally:
+        env.close()
+        shard.close()
+        penv.close()
+
+
+def test_draws_follow_the_global_step_up_to_the_last_one():
+    """first_step = 2^32 - K: the last step's index is 2^32 - 1, the largest cs_rollout_pf admits (the key's (k << 10)
+    wraps in 32 bits there, as pf_ref.words restates and the host build of pf_noise.h confirms on the CPU)."""
+    import torch
+    P = 128
+    first = 2 ** 32 - K
+    rng = np.random.default_rng(942)
+    env = _env("lander3d", N)
+    penv = _particle_env("lander3d", P, 1)
+    try:
+        env.reset()
+        p = _problem(env, "lander3d", rng)
+        early = _run(env, p, P).part_tape[0].clone()
+        res = _clone(_run(env, p, P, first_step=first))
+        _check_steps("lander3d steps from 2^32 - %d" % K, env, penv, p, res, P, first_step=first)
+        differs = (res.part_tape[0] != early).flatten(1).any(dim=1)
+        assert bool(differs.all()), differs.tolist()
+    finally:
+        env.close()
+        penv.close()
+
+
+def test_ess_frac_zero_never_resamples_and_one_resamples_whenever_the_weights_differ():
+    import torch
+    P = 64
+    rng = np.random.default_rng(943)
+    env = _env("lander3d", N)
+    penv = _particle_env("lander3d", P, 1)
+    try:
+        env.reset()
+        p = _problem(env, "lander3d", rng)
+        at_half = int(_run(env, p, P).resampled.sum())
+        p0 = dict(p, ess_frac=0.0)
+        res = _clone(_run(env, p0, P))
+        _, resampled, _ = _check_steps("lander3d ess_frac=0", env, penv, p0, res, P)
+        assert not resampled.any()
+        ident = torch.arange(P, dtype=res.anc_tape.dtype, device=env.device).expand(K, N, P)
+        assert torch.equal(res.anc_tape, ident)
+        p1 = dict(p, ess_frac=1.0)
+        res = _clone(_run(env, p1, P))
+        _, resampled, _ = _check_steps("lander3d ess_frac=1", env, penv, p1, res, P)
+        print("resampled (step, env) pairs of %d: %d at ess_frac 0.5, %d at 1.0" % (K * N, at_half, int(resampled.sum())))
+        assert int(resampled.sum()) > at_half
     finally:
         env.close()
         penv.close()

@@ -11,7 +11,7 @@ quadrant of either sign, on the edges of the reduction, past the fold at 8e5 rad
    and the terminated flags the oracle's step gives;
 5. yaw periodicity at large magnitude: the derivatives at psi_big against those at its twin psi_red';
 6. rollout_mlp_states under a zero policy and the filter's x_pred equal rollout_states at the wide starts, and one run
-   of the filter's step-by-step check.
+   each of the step-by-step checks of the filter, the smoother on its tapes, and the particle filter.
 The conditions these rest on are checked on the oracle alone by tests/test_wide_attitudes_cpu.py.
 
 Measured on an MI355X (every test prints its own figures; the table is in DESIGN.md section 3): 1. float64 5.4e-15 of
@@ -376,6 +376,7 @@ def test_the_filter_predicts_with_the_rollouts_step_at_wide_attitudes():
     import ekf_ref
     from gym_copter_amd import measure
     from test_gpu_rollout_ekf import _check_steps, _clone, _model, _run, _spd
+    from test_gpu_rollout_rts import _check_rows, _rts
     p = ap.points()
     sel = np.flatnonzero(np.isin(p.group, [g for g in ap.WIDE_GROUPS if g != "fold"]) & (np.arange(ap.N) % 8 != 0))
     n, K = sel.size, 4
@@ -393,5 +394,47 @@ def test_the_filter_predicts_with_the_rollouts_step_at_wide_attitudes():
         res = _clone(_run(env, prob, tape=True))
         _check_steps("wide attitudes", env, prob, res)
         assert (np.abs(x0[[6, 8]]) > 2.0).any() and (np.abs(x0[10]) > 100).any()
+        # the smoother on the same tapes: every backward step at the bars of tests/test_gpu_rollout_rts.py
+        smoothed = _clone(_rts(env, prob, res))
+        _check_rows("wide attitudes", env, prob, res, smoothed)
     finally:
         env.close()
+
+
+def test_the_particle_filter_steps_its_particles_at_wide_attitudes():
+    """cs_rollout_pf on five lanes of five wide groups (a yaw past 100 rad, a roll or pitch past 2 rad, one at pi/2),
+    motors around hover, K = 4, 64 particles from a small P0, float64: every prior particle is rollout_states' step
+    from the same point plus the reference's noise bit for bit, and the statuses and everything downstream meet the
+    checks of tests/test_gpu_rollout_pf.py (its _check_steps, run once)."""
+    import ekf_ref
+    import test_gpu_rollout_pf as F
+    from test_gpu_rollout_ekf import _model, _spd
+    p = ap.points()
+    usable = (np.arange(ap.N) % 8 != 0) & np.isfinite(p.x[10])           # motors around hover, a finite yaw
+    sel = np.array([np.flatnonzero((p.group == grp) & usable & cond)[0] for grp, cond in (
+        ("quadrant", True), ("ymid", np.abs(p.x[10]) > 100), ("r0815", True), ("rpi2", True),
+        ("r231", np.abs(p.x[[6, 8]]).max(axis=0) > 2.0))])
+    n, K, P = sel.size, 4, 64
+    assert n == F.N and len(set(p.group[sel])) == n and "fold" not in p.group[sel] and "nonfinite" not in p.group[sel]
+    rng = np.random.default_rng(23)
+    env = F._env("lander3d", n)
+    penv = F._particle_env("lander3d", P, 1)
+    try:
+        env.reset()
+        x0, st0 = np.ascontiguousarray(p.x[:, sel]), p.status[sel].copy()
+        assert (np.abs(x0[[6, 8]]) > 2.0).any() and (np.abs(x0[10]) > 100).any()
+        acts = (p.actions[sel][None] * rng.uniform(0.9, 1.1, (K, n, 4))).astype(np.float32)
+        H, r = _model(rng, 6, True)
+        acts_d = _dev(acts, env)
+        truth = to_np(env.rollout_states(acts_d, state={"x": x0, "status": st0}).x).astype(np.float64)
+        z = truth @ H.T + np.sqrt(r) * rng.standard_normal((K, n, 6))
+        prob = dict(acts=acts_d, z=_dev(z, env), H=H, r=r, Q=ekf_ref.test_Q(), x0=_dev(x0, env),
+                    P0=_dev(1e-4 * _spd(rng, n), env), st0=_dev(st0, env), nonce=11, ess_frac=0.5)
+        res = F._clone(F._run(env, prob, P))
+        F._check_steps("wide attitudes", env, penv, prob, res, P)
+        # the particles stayed wide: no lane's cloud was pulled into the first quadrant
+        part = to_np(res.part_tape)
+        assert (np.abs(part[..., [6, 8]]) > 2.0).any() and (np.abs(part[..., 10]) > 100).any()
+    finally:
+        env.close()
+        penv.close()
