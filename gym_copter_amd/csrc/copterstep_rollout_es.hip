@@ -73,12 +73,7 @@ void rollout_mlp_population_kernel(const DevConst c, const DevState s, const cs_
   unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
   resolve_episode<MODE>(c, tile, e);
   double px, py, pz;
-  if (io.start_x_dev != nullptr) {
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
-    e.reset_pending = false;
-  } else {
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-  }
+  rollout_start<TASK, MODE>(c, q, io, tile, i, n, valid, e, px, py, pz);
 
   const int K = io.num_steps;
   double ret = 0.0, disc = 1.0;
@@ -97,11 +92,7 @@ void rollout_mlp_population_kernel(const DevConst c, const DevState s, const cs_
     double reward;
     bool term, trunc;
     rollout_step<TASK, MODE>(c, q, e, motors_of<A>(a), px, py, pz, reward, term, trunc);
-    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
-      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-    } else if (!e.pend) {
-      px = py = pz = -0.0;
-    }
+    next_perturbation<MODE>(c, q, tile, i, resetting, e, px, py, pz);
 
     if (!done) {  // the episode's return up to and including its last step d
       const double term_k = disc * reward;

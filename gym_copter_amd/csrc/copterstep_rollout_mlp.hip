@@ -97,12 +97,7 @@ __global__ __launch_bounds__(kBlock) void rollout_mlp_states_kernel(const DevCon
   unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
   resolve_episode<MODE>(c, tile, e);
   double px, py, pz;
-  if (io.start_x_dev != nullptr) {
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
-    e.reset_pending = false;
-  } else {
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-  }
+  rollout_start<TASK, MODE>(c, q, io, tile, i, n, valid, e, px, py, pz);
 
   const float* u_lane = m.offsets != nullptr ? m.offsets + (size_t)(valid ? i : 0u) * A : nullptr;
   const size_t act_step = (size_t)n * A;
@@ -128,11 +123,7 @@ __global__ __launch_bounds__(kBlock) void rollout_mlp_states_kernel(const DevCon
     double reward;
     bool term, trunc;
     rollout_step<TASK, MODE>(c, q, e, motors_of<A>(a), px, py, pz, reward, term, trunc);
-    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
-      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-    } else if (!e.pend) {
-      px = py = pz = -0.0;
-    }
+    next_perturbation<MODE>(c, q, tile, i, resetting, e, px, py, pz);
 
     if (io.x_dev != nullptr) {
       if (whole) {  // 64 rows of 96 B through the LDS: six 1 KiB stores of 16 B per lane

@@ -9,7 +9,8 @@
 // Costs: one lane per env on the tile layout of the step kernels (tile t -> workgroup t in x), the sample in grid y.
 // The loop is rollout_forward's (rollout_sweep.h) with the noise as the action source and no stores but one float64 per
 // lane at the end.  Update: one lane per env, the step in grid y; every wavefront recomputes its 64 envs' weights from
-// the cost columns ([P,N]: each row a coalesced load) and accumulates the A components of its step.
+// the cost columns ([P,N]: each row a coalesced load) and accumulates the A components of its step.  A step's cost terms
+// and the update's body are rollout_mppi.h's (mppi_step_cost, mppi_update_lane), shared with the knot-noise kernels.
 #include "copterstep_jacobian.h"
 
 // the samples' states must be cs_rollout_states' bit for bit; the cost's float64 arithmetic is not contracted either
@@ -55,12 +56,7 @@ __global__ __launch_bounds__(kBlock, 2) void rollout_mppi_costs_kernel(const Dev
   unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
   resolve_episode<MODE>(c, tile, e);
   double px, py, pz;
-  if (io.start_x_dev != nullptr) {
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
-    e.reset_pending = false;
-  } else {
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-  }
+  rollout_start<TASK, MODE>(c, q, io, tile, i, n, valid, e, px, py, pz);
 
   float sig[A];
   double aref[A];
@@ -96,29 +92,8 @@ __global__ __launch_bounds__(kBlock, 2) void rollout_mppi_costs_kernel(const Dev
     double reward;
     bool term, trunc;
     rollout_step<TASK, MODE>(c, q, e, fan_out<A>(a), px, py, pz, reward, term, trunc);
-    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
-      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-    } else if (!e.pend) {
-      px = py = pz = -0.0;
-    }
-    // the step's cost terms, each added to S on its own
-    double dx[12], da[A];
-    const double2* xv = reinterpret_cast<const double2*>(xr);
-    xr += xstep;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const double2 v = xv[j];
-      dx[2 * j] = e.x[2 * j] - v.x;
-      dx[2 * j + 1] = e.x[2 * j + 1] - v.y;
-    }
-#pragma unroll
-    for (int j = 0; j < A; ++j) da[j] = (double)a[j] - aref[j];
-    // (the address is made opaque per step: the 166 loop-invariant reads would otherwise be hoisted into registers)
-    const double* w = wts;
-    asm volatile("" : "+v"(w));
-    S += half_quadratic<12>(k == K - 1 ? w + tri_size(12) : w, dx);
-    S += half_quadratic<A>(w + 2 * tri_size(12), da);
-    S -= m.wr * reward;
+    next_perturbation<MODE>(c, q, tile, i, resetting, e, px, py, pz);
+    mppi_step_cost<A>(wts, xr, xstep, e.x, a, [&](int j) { return aref[j]; }, k == K - 1, m.wr, reward, S);
   }
   if (valid) m.costs[(size_t)p * n + i] = S;  // (64-bit: P x N doubles pass 4 GiB)
 }
@@ -131,52 +106,9 @@ __global__ __launch_bounds__(kBlock) void rollout_mppi_update_kernel(uint32_t n,
   const uint32_t i = tile * kBlock + threadIdx.x;
   if (i >= n) return;
   const uint32_t gid = id_lo + i;
-  const uint32_t P = m.samples;
-  const double* col = m.costs + i;
-
-  bool any = false;
-  double beta = 0.0;
-#pragma clang loop unroll(disable)
-  for (uint32_t p = 0; p < P; ++p) {
-    const double v = col[(size_t)p * n];
-    if (finite64(v) && (!any || v < beta)) {
-      any = true;
-      beta = v;
-    }
-  }
-  float sig[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) sig[j] = m.sigma[j];
-  double eta = 0.0, eta2 = 0.0, acc[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) acc[j] = 0.0;
-  if (any) {
-#pragma clang loop unroll(disable)
-    for (uint32_t p = 0; p < P; ++p) {
-      const double v = col[(size_t)p * n];
-      const double w = finite64(v) ? exp(-(v - beta) / m.lambda) : 0.0;
-      eta += w;
-      eta2 += w * w;
-      if (p != 0u) {  // (sample 0 is the nominal: its perturbation is zero)
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float da = sig[j] * mppi_noise(m.key, gid, m.nonce, k0 + 1u, p, (uint32_t)j);
-          acc[j] += w * (double)da;
-        }
-      }
-    }
-  }
-  const size_t at = ((size_t)k0 * n + i) * A;
-  const double inv_eta = 1.0 / eta;  // (eta >= 1 when any: the best sample's weight is exp(0))
-#pragma unroll
-  for (int j = 0; j < A; ++j) {
-    const float ab = abar_dev[at + j];
-    m.out[at + j] = any ? clip01((float)((double)ab + inv_eta * acc[j])) : ab;
-  }
-  if (k0 == 0u) {
-    if (m.ess != nullptr) m.ess[i] = any ? (eta * eta) / eta2 : 0.0;
-    if (m.cost_min != nullptr) m.cost_min[i] = any ? beta : __builtin_inf();
-  }
+  // (the scalar temperature is checked by the entry point: always warm)
+  mppi_update_lane<A>(n, i, k0, abar_dev, m, m.lambda, true,
+                      [&](uint32_t p, uint32_t j) { return mppi_noise(m.key, gid, m.nonce, k0 + 1u, p, j); });
 }
 
 template <int TASK, int MODE>
@@ -217,15 +149,9 @@ extern "C" int cs_rollout_mppi_costs(cs_ctx* ctx, const cs_rollout_io* io, const
   cs::ContextView v;
   if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
   const cs::MppiArgs m = cs::mppi_args(ctx, *mio);
-  hipError_t e = cs::launch_mppi_costs(v.task, v.mode, *v.c, *v.s, *io, m, (hipStream_t)stream);
+  const hipError_t e = cs::launch_mppi_costs(v.task, v.mode, *v.c, *v.s, *io, m, (hipStream_t)stream);
   if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mppi_costs: kernel launch");
-  if (m.best != nullptr) {
-    hipLaunchKernelGGL(cs::mppi_best_kernel, dim3(cs::grid_for(v.s->n)), dim3(cs::kBlock), 0, (hipStream_t)stream,
-                       v.s->n, m);
-    e = hipGetLastError();
-    if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mppi_costs: arg-min kernel launch");
-  }
-  return CS_OK;
+  return cs::launch_mppi_best(m, v.s->n, (hipStream_t)stream, who);
 }
 
 extern "C" int cs_rollout_mppi_update(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio,

@@ -8,7 +8,8 @@
 // and are made again only at the steps where the knot number changes (a uniform branch: the table is the launch's); a
 // knot that moves on by one takes over its neighbour's draws, so a hold of h steps costs A Philox calls per h steps.  Update: the
 // white kernel's, with the knot pair of step k0 drawn per sample (uniform per workgroup) and lambda read per lane.
-// Temperature: one lane per env, float64, 51 passes over the env's cost column.
+// Temperature: one lane per env, float64, 51 passes over the env's cost column.  What the two files' kernels have in
+// common word for word -- a step's cost terms, the update's body, the column's finite minimum -- is rollout_mppi.h's.
 #include "copterstep_jacobian.h"
 
 // the samples' states must be cs_rollout_states' bit for bit; the cost's float64 arithmetic is not contracted either
@@ -84,12 +85,7 @@ __global__ __launch_bounds__(kBlock, 2) void rollout_mppi_smooth_costs_kernel(co
   unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
   resolve_episode<MODE>(c, tile, e);
   double px, py, pz;
-  if (io.start_x_dev != nullptr) {
-    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
-    e.reset_pending = false;
-  } else {
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-  }
+  rollout_start<TASK, MODE>(c, q, io, tile, i, n, valid, e, px, py, pz);
 
   const uint32_t gid = c.id_lo + ii;
   const float* abar = io.actions_dev + (size_t)ii * A;
@@ -144,29 +140,9 @@ __global__ __launch_bounds__(kBlock, 2) void rollout_mppi_smooth_costs_kernel(co
     double reward;
     bool term, trunc;
     rollout_step<TASK, MODE>(c, q, e, fan_out<A>(a), px, py, pz, reward, term, trunc);
-    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
-      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-    } else if (!e.pend) {
-      px = py = pz = -0.0;
-    }
-    // the step's cost terms, each added to S on its own
-    double dx[12], da[A];
-    const double2* xv = reinterpret_cast<const double2*>(xr);
-    xr += xstep;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const double2 v = xv[j];
-      dx[2 * j] = e.x[2 * j] - v.x;
-      dx[2 * j + 1] = e.x[2 * j + 1] - v.y;
-    }
-#pragma unroll
-    for (int j = 0; j < A; ++j) da[j] = (double)a[j] - (arp != nullptr ? arp[j] : 0.0);
-    // (the address is made opaque per step: the 166 loop-invariant reads would otherwise be hoisted into registers)
-    const double* w = wts;
-    asm volatile("" : "+v"(w));
-    S += half_quadratic<12>(k == K - 1 ? w + tri_size(12) : w, dx);
-    S += half_quadratic<A>(w + 2 * tri_size(12), da);
-    S -= m.wr * reward;
+    next_perturbation<MODE>(c, q, tile, i, resetting, e, px, py, pz);
+    mppi_step_cost<A>(
+        wts, xr, xstep, e.x, a, [&](int j) { return arp != nullptr ? arp[j] : 0.0; }, k == K - 1, m.wr, reward, S);
   }
   if (valid) m.costs[(size_t)p * n + i] = S;  // (64-bit: P x N doubles pass 4 GiB)
 }
@@ -180,58 +156,14 @@ __global__ __launch_bounds__(kBlock) void rollout_mppi_smooth_update_kernel(uint
   const uint32_t i = tile * kBlock + threadIdx.x;
   if (i >= n) return;
   const uint32_t gid = id_lo + i;
-  const uint32_t P = m.samples;
-  const double* col = m.costs + i;
   uint32_t knot;
   float w0, w1;
   knot_of_step(x.knot, x.weight, k0, knot, w0, w1);
   const double lambda = x.lam != nullptr ? x.lam[i] : m.lambda;
   const bool warm = lambda > 0.0 && finite64(lambda);  // (false for a NaN)
-
-  bool any = false;
-  double beta = 0.0;
-#pragma clang loop unroll(disable)
-  for (uint32_t p = 0; p < P; ++p) {
-    const double v = col[(size_t)p * n];
-    if (finite64(v) && (!any || v < beta)) {
-      any = true;
-      beta = v;
-    }
-  }
-  const bool move = any && warm;
-  float sig[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) sig[j] = m.sigma[j];
-  double eta = 0.0, eta2 = 0.0, acc[A];
-#pragma unroll
-  for (int j = 0; j < A; ++j) acc[j] = 0.0;
-  if (move) {
-#pragma clang loop unroll(disable)
-    for (uint32_t p = 0; p < P; ++p) {
-      const double v = col[(size_t)p * n];
-      const double w = finite64(v) ? exp(-(v - beta) / lambda) : 0.0;
-      eta += w;
-      eta2 += w * w;
-      if (p != 0u) {  // (sample 0 is the nominal: its perturbation is zero)
-#pragma unroll
-        for (int j = 0; j < A; ++j) {
-          const float da = sig[j] * mppi_noise_smooth(m.key, gid, m.nonce, knot, w0, w1, p, (uint32_t)j);
-          acc[j] += w * (double)da;
-        }
-      }
-    }
-  }
-  const size_t at = ((size_t)k0 * n + i) * A;
-  const double inv_eta = 1.0 / eta;  // (eta >= 1 when move: the best sample's weight is exp(0))
-#pragma unroll
-  for (int j = 0; j < A; ++j) {
-    const float ab = abar_dev[at + j];
-    m.out[at + j] = move ? clip01((float)((double)ab + inv_eta * acc[j])) : ab;
-  }
-  if (k0 == 0u) {
-    if (m.ess != nullptr) m.ess[i] = move ? (eta * eta) / eta2 : 0.0;
-    if (m.cost_min != nullptr) m.cost_min[i] = any ? beta : __builtin_inf();
-  }
+  mppi_update_lane<A>(n, i, k0, abar_dev, m, lambda, warm, [&](uint32_t p, uint32_t j) {
+    return mppi_noise_smooth(m.key, gid, m.nonce, knot, w0, w1, p, j);
+  });
 }
 
 // E(lambda) = (sum w)^2 / sum w^2 over the finite costs of a column whose minimum finite cost is beta
@@ -254,16 +186,7 @@ __global__ __launch_bounds__(kBlock, 8) void mppi_temperature_kernel(uint32_t n,
   const uint32_t i = tile * kBlock + threadIdx.x;
   if (i >= n) return;
   const double* col = costs + i;
-  bool any = false;
-  double beta = 0.0;
-#pragma clang loop unroll(disable)
-  for (uint32_t p = 0; p < P; ++p) {
-    const double v = col[(size_t)p * n];
-    if (finite64(v) && (!any || v < beta)) {
-      any = true;
-      beta = v;
-    }
-  }
+  const auto [any, beta] = column_min(col, n, P);
   double lambda = x.lam_max, E = 0.0;
   if (any) {
     E = effective_size(col, n, P, beta, x.lam_max);
@@ -347,16 +270,10 @@ extern "C" int cs_rollout_mppi_costs_ex(cs_ctx* ctx, const cs_rollout_io* io, co
   cs::ContextView v;
   if (int rc_ = cs::enter_context(ctx, who, stream, &v)) return rc_;
   const cs::MppiArgs m = cs::mppi_args(ctx, *mio);
-  hipError_t e = cs::launch_mppi_smooth_costs(v.task, v.mode, *v.c, *v.s, *io, m, cs::mppi_ext(*ext),
-                                              (hipStream_t)stream);
+  const hipError_t e = cs::launch_mppi_smooth_costs(v.task, v.mode, *v.c, *v.s, *io, m, cs::mppi_ext(*ext),
+                                                    (hipStream_t)stream);
   if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mppi_costs_ex: kernel launch");
-  if (m.best != nullptr) {
-    hipLaunchKernelGGL(cs::mppi_best_kernel, dim3(cs::grid_for(v.s->n)), dim3(cs::kBlock), 0, (hipStream_t)stream,
-                       v.s->n, m);
-    e = hipGetLastError();
-    if (e != hipSuccess) return cs::report_hip(e, "cs_rollout_mppi_costs_ex: arg-min kernel launch");
-  }
-  return CS_OK;
+  return cs::launch_mppi_best(m, v.s->n, (hipStream_t)stream, who);
 }
 
 extern "C" int cs_rollout_mppi_update_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_mppi_io* mio,

@@ -1,7 +1,8 @@
 // rollout_mppi.h -- what the MPPI translation units share (copterstep_rollout_mppi.hip: the white-noise kernels of
 // DESIGN.md section 14; copterstep_rollout_mppi_smooth.hip: the knot-noise kernels and the temperature of section 15):
-// the checked argument block, the cost's matrices in the LDS, the motor fan-out, the arg-min kernel and the block
-// checks.  Included after the device headers and mppi_noise.h, inside a translation unit that has set
+// the checked argument block, the cost's matrices in the LDS, the motor fan-out, a step's cost terms, the finite minimum
+// of a cost column, the weighted update's body (the update rule exists here alone), the arg-min kernel with its launch,
+// and the block checks.  Included after the device headers and mppi_noise.h, inside a translation unit that has set
 // `#pragma clang fp contract(off)`; not a stand-alone header.
 #pragma once
 
@@ -70,7 +71,103 @@ __device__ __forceinline__ float4 fan_out(const float (&a)[A]) {
     return make_float4(a[0], a[0], a[0], a[0]);
 }
 
-// best[i] = the arg-min over the finite costs of env i, the lowest index on ties, -1 if none is finite
+// One step's cost terms, each added to S on its own: 1/2 dx^T Q dx with dx = x - x_ref (xr: the lane's row, moved on by
+// xstep for the next step; Q_final at the last step), 1/2 da^T R da with da = a - a_ref, and -wr reward.  wts: the
+// kernel's staged triangles Q, Q at the last step, R.  aref(j): a_ref's component j, read where the kernel keeps it
+// (registers in the white kernel, per step through the scalar unit in the knot-noise one), after the x_ref loads as the
+// kernels had it: with da made by the caller before them the knot-noise cost kernel ran up to 1.5 % slower at one
+// substep (profiles/forward_shared_refactor_ab.txt).
+template <int A, class AREF>
+__device__ __forceinline__ void mppi_step_cost(const double* wts, const double*& xr, size_t xstep,
+                                               const double (&x)[12], const float (&a)[A], AREF aref, bool last,
+                                               double wr, double reward, double& S) {
+  double dx[12], da[A];
+  const double2* xv = reinterpret_cast<const double2*>(xr);
+  xr += xstep;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const double2 v = xv[j];
+    dx[2 * j] = x[2 * j] - v.x;
+    dx[2 * j + 1] = x[2 * j + 1] - v.y;
+  }
+#pragma unroll
+  for (int j = 0; j < A; ++j) da[j] = (double)a[j] - aref(j);
+  // (the address is made opaque per step: the 166 loop-invariant reads would otherwise be hoisted into registers)
+  const double* w = wts;
+  asm volatile("" : "+v"(w));
+  S += half_quadratic<12>(last ? w + tri_size(12) : w, dx);
+  S += half_quadratic<A>(w + 2 * tri_size(12), da);
+  S -= wr * reward;
+}
+
+// The finite minimum of a lane's cost column (col = costs + i of [P,N]): any = one of the P costs is finite, beta = the
+// least of those
+struct ColumnMin {
+  bool any;
+  double beta;
+};
+
+__device__ __forceinline__ ColumnMin column_min(const double* col, uint32_t n, uint32_t P) {
+  ColumnMin r{false, 0.0};
+#pragma clang loop unroll(disable)
+  for (uint32_t p = 0; p < P; ++p) {
+    const double v = col[(size_t)p * n];
+    if (finite64(v) && (!r.any || v < r.beta)) {
+      r.any = true;
+      r.beta = v;
+    }
+  }
+  return r;
+}
+
+// The weighted update of env i's step k0 + 1 (DESIGN.md sections 14 and 15), the body of both update kernels:
+// w_p = exp(-(S_p - beta) / lambda) over the finite costs, abar += sum_p w_p sigma eps_p / sum_p w_p, clipped; the tape
+// is copied where no cost is finite or the temperature is not `warm` (finite and > 0).  eps(p, j): the draw of sample
+// p >= 1, component j, at this step.  Step 0's lanes store ess and cost_min.
+template <int A, class NOISE>
+__device__ __forceinline__ void mppi_update_lane(uint32_t n, uint32_t i, uint32_t k0, const float* abar_dev,
+                                                 const MppiArgs& m, double lambda, bool warm, NOISE eps) {
+  const uint32_t P = m.samples;
+  const double* col = m.costs + i;
+  const auto [any, beta] = column_min(col, n, P);
+  const bool move = any && warm;
+  float sig[A];
+#pragma unroll
+  for (int j = 0; j < A; ++j) sig[j] = m.sigma[j];
+  double eta = 0.0, eta2 = 0.0, acc[A];
+#pragma unroll
+  for (int j = 0; j < A; ++j) acc[j] = 0.0;
+  if (move) {
+#pragma clang loop unroll(disable)
+    for (uint32_t p = 0; p < P; ++p) {
+      const double v = col[(size_t)p * n];
+      const double w = finite64(v) ? exp(-(v - beta) / lambda) : 0.0;
+      eta += w;
+      eta2 += w * w;
+      if (p != 0u) {  // (sample 0 is the nominal: its perturbation is zero)
+#pragma unroll
+        for (int j = 0; j < A; ++j) {
+          const float da = sig[j] * eps(p, (uint32_t)j);
+          acc[j] += w * (double)da;
+        }
+      }
+    }
+  }
+  const size_t at = ((size_t)k0 * n + i) * A;
+  const double inv_eta = 1.0 / eta;  // (eta >= 1 when move: the best sample's weight is exp(0))
+#pragma unroll
+  for (int j = 0; j < A; ++j) {
+    const float ab = abar_dev[at + j];
+    m.out[at + j] = move ? clip01((float)((double)ab + inv_eta * acc[j])) : ab;
+  }
+  if (k0 == 0u) {
+    if (m.ess != nullptr) m.ess[i] = move ? (eta * eta) / eta2 : 0.0;
+    if (m.cost_min != nullptr) m.cost_min[i] = any ? beta : __builtin_inf();
+  }
+}
+
+// best[i] = the arg-min over the finite costs of env i, the lowest index on ties, -1 if none is finite (its own loop:
+// it tracks the index, with that tie rule)
 __global__ __launch_bounds__(kBlock) void mppi_best_kernel(uint32_t n, const MppiArgs m) {
   const uint32_t tile = blockIdx.x;
   const uint32_t i = tile * kBlock + threadIdx.x;
@@ -133,6 +230,15 @@ inline MppiArgs mppi_args(cs_ctx* ctx, const cs_rollout_mppi_io& o) {
                   o.R_dev, o.costs_dev, o.best_dev, o.actions_out_dev, o.ess_dev, o.cost_min_dev, o.lam,
                   o.reward_weight, mppi_noise_key(context_seed(ctx)), o.noise_stream, (uint32_t)o.num_samples,
                   o.x_ref_steps};
+}
+
+// the optional arg-min over the costs a cost entry point `who` has just launched (best_dev NULL: nothing)
+inline int launch_mppi_best(const MppiArgs& m, uint32_t n, hipStream_t stream, const std::string& who) {
+  if (m.best == nullptr) return CS_OK;
+  hipLaunchKernelGGL(mppi_best_kernel, dim3(grid_for(n)), dim3(kBlock), 0, stream, n, m);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return report_hip(e, (who + ": arg-min kernel launch").c_str());
+  return CS_OK;
 }
 
 }  // namespace

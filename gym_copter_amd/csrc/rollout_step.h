@@ -1,8 +1,12 @@
-// rollout_step.h -- the pieces the differentiable rollouts share (copterstep_rollout_grad.hip: cs_rollout_states /
-// cs_rollout_vjp; copterstep_rollout_mlp.hip: the closed-loop cs_rollout_mlp_*): the explicit start point, one
-// _Task.step() with auto-reset disabled, the backward's tape loads and cotangents, and the adjoint of one step.  Device
-// code of those translation units (included inside their floating-point-contraction pragma, after rollout_adjoint.h);
-// not a stand-alone header.  DESIGN.md sections 10 and 12.
+// rollout_step.h -- the pieces the rollout kernels share.  For the five forwards whose states must be
+// cs_rollout_states' bit for bit (rollout_forward in rollout_sweep.h, the closed-loop forward of
+// copterstep_rollout_mlp.hip, the cost kernels of copterstep_rollout_mppi.hip and copterstep_rollout_mppi_smooth.hip,
+// the population kernel of copterstep_rollout_es.hip): the explicit start point, the choice between it and the stored
+// env (rollout_start), one _Task.step() with auto-reset disabled, and the perturbation of the step after it
+// (next_perturbation).  For the backwards (rollout_vjp_sweep, copterstep_rollout_lqr.hip, which decode the start
+// themselves): the tape loads and cotangents, and the adjoint of one step.  Device code of those translation units
+// (included inside their floating-point-contraction pragma, after rollout_adjoint.h); not a stand-alone header.
+// DESIGN.md sections 10, 12 and 14 to 16.
 #pragma once
 
 #ifdef CS_DEBUG_ROLLOUT  // debug build (make DEFS=-DCS_DEBUG_ROLLOUT exp NAME=debug): the recompute is checked
@@ -35,6 +39,21 @@ __device__ __forceinline__ void explicit_start(const DevConst& c, const Coef& q,
     prev_sh = (double)(T)lander_shaping(c, x);
   } else {
     prev_sh = 0.0;
+  }
+}
+
+// Where a forward rollout starts, after the caller's unpack_env / resolve_episode of the stored env: io's explicit start
+// point (no reset is pending there), else the stored env with its pending perturbation.  The one definition of the five
+// forward kernels, whose states the tests compare bit for bit.
+template <int TASK, int MODE, class TILE>
+__device__ __forceinline__ void rollout_start(const DevConst& c, const Coef& q, const cs_rollout_io& io,
+                                              const TILE& tile, uint32_t i, uint32_t n, bool valid, Env<MODE>& e,
+                                              double& px, double& py, double& pz) {
+  if (io.start_x_dev != nullptr) {
+    explicit_start<TASK, MODE>(c, q, io, i, n, valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
+    e.reset_pending = false;
+  } else {
+    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
   }
 }
 
@@ -93,6 +112,20 @@ __device__ __forceinline__ void rollout_step(const DevConst& c, const Coef& q, E
     e.steps = 1;
     e.prev_sh = c.reset_shaping;
     e.reset_pending = false;
+  }
+}
+
+// The perturbation of the step after a rollout_step: the new episode's where that step was the reset (`resetting`: the
+// Philox draw step() would make), none once the pending one is consumed.  With rollout_start, the forward kernels' one
+// definition.
+template <int MODE, class TILE>
+__device__ __forceinline__ void next_perturbation(const DevConst& c, const Coef& q, const TILE& tile, uint32_t i,
+                                                  bool resetting, const Env<MODE>& e, double& px, double& py,
+                                                  double& pz) {
+  if (resetting) {
+    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
+  } else if (!e.pend) {
+    px = py = pz = -0.0;
   }
 }
 

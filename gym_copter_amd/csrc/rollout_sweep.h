@@ -81,12 +81,7 @@ __device__ __forceinline__ void rollout_forward(const DevConst& c, const DevStat
   unpack_env<MODE, TILE>(c, tile.load_group(0), tile.load_group(1), tile.load_group(2), tile.load_group(3), e);
   resolve_episode<MODE>(c, tile, e);
   double px, py, pz;
-  if (io.start_x_dev != nullptr) {
-    explicit_start<TASK, MODE>(c, q, io, i, n, r.valid, e.x, e.fs, e.pend, px, py, pz, e.prev_sh);
-    e.reset_pending = false;
-  } else {
-    pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-  }
+  rollout_start<TASK, MODE>(c, q, io, tile, i, n, r.valid, e, px, py, pz);
 
   act.begin(r.valid ? i : 0u, n);
 #pragma clang loop unroll(disable)
@@ -97,11 +92,7 @@ __device__ __forceinline__ void rollout_forward(const DevConst& c, const DevStat
     double reward;
     bool term, trunc;
     rollout_step<TASK, MODE>(c, q, e, a, px, py, pz, reward, term, trunc);
-    if (resetting) {  // the new episode's perturbation (the Philox draw step() would make)
-      pending_perturbation<MODE, true>(c, q, tile, i, e.episode, e.ep_far, e.pend, e.expl, px, py, pz);
-    } else if (!e.pend) {
-      px = py = pz = -0.0;
-    }
+    next_perturbation<MODE>(c, q, tile, i, resetting, e, px, py, pz);
     if (io.x_dev != nullptr) store_x_row(xrow, io.x_dev, row, r, e.x);
     if (r.valid) {
       if (io.reward_dev != nullptr) io.reward_dev[row + i] = reward;
