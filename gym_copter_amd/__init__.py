@@ -4,8 +4,8 @@ Only what the hot path needs lives here: csrc/ (HIP kernels + C ABI), the ctypes
 and the Gymnasium-style vector-env host class.  See DESIGN.md and INTEGRATION.md.
 """
 from ._lib import CopterStepError  # noqa: F401
-from .vecenv import (CopterVecEnv, EkfResult, LqrGains, MlpRollout, MppiCosts, MppiUpdate, PfResult,  # noqa: F401
-                     Rollout, RtsResult, StepJacobian)
+from .vecenv import (CopterVecEnv, EkfResult, LqgResult, LqrGains, MlpRollout, MppiCosts, MppiUpdate,  # noqa: F401
+                     PfResult, Rollout, RtsResult, StepJacobian)
 from .vecenv import ActorCritic, MppiTemperature, Population, PpoGrad, mppi_knots  # noqa: F401
 from .autodiff import differentiable_mlp_rollout, differentiable_rollout, ppo_loss  # noqa: F401
 from . import mlp  # noqa: F401
@@ -13,6 +13,7 @@ from .ilqr import ilqr  # noqa: F401
 from .mppi import mppi  # noqa: F401
 from .ekf import ekf, measure, smooth  # noqa: F401
 from .pf import pf  # noqa: F401
+from .lqg import lqg, measurement_noise  # noqa: F401
 from .es import es  # noqa: F401
 from .ppo import ppo  # noqa: F401
 from .spaces import box_class as _box_class

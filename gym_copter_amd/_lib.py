@@ -136,6 +136,18 @@ class RolloutEkfIO(C.Structure):
                 ("loglik_dev", C.c_void_p), ("branch_dev", C.c_void_p), ("ok_dev", C.c_void_p)]
 
 
+class RolloutLqgIO(C.Structure):
+    """Mirror of `struct cs_rollout_lqg_io` (cs_rollout_lqg)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_meas", C.c_int32),
+                ("reserved_", C.c_uint32), ("K_dev", C.c_void_p), ("xbar_dev", C.c_void_p), ("e_dev", C.c_void_p),
+                ("H_dev", C.c_void_p), ("r_dev", C.c_void_p), ("Q_dev", C.c_void_p), ("P0_dev", C.c_void_p),
+                ("xhat0_dev", C.c_void_p), ("status0_dev", C.c_void_p), ("actions_out_dev", C.c_void_p),
+                ("z_dev", C.c_void_p), ("xhat_dev", C.c_void_p), ("x_pred_dev", C.c_void_p), ("P_dev", C.c_void_p),
+                ("P_tape_dev", C.c_void_p), ("var_dev", C.c_void_p), ("nis_dev", C.c_void_p),
+                ("loglik_dev", C.c_void_p), ("fstatus_dev", C.c_void_p), ("branch_dev", C.c_void_p),
+                ("ok_dev", C.c_void_p)]
+
+
 class RolloutRtsIO(C.Structure):
     """Mirror of `struct cs_rollout_rts_io` (cs_rollout_rts)."""
     _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("x_f_dev", C.c_void_p),
@@ -299,6 +311,7 @@ SYMBOLS = {
     "cs_rollout_ekf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutEkfIO), _P]),
     "cs_rollout_rts": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutRtsIO), _P]),
     "cs_rollout_pf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutPfIO), _P]),
+    "cs_rollout_lqg": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqgIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),

@@ -221,6 +221,13 @@ class ShardedCopterVecEnv:
         return self.local.rollout_ekf(self._local_rollout_actions(actions), z, H, r, Q, x0, P0, status0=status0,
                                       tape=tape, dtype=dtype)
 
+    def rollout_lqg(self, actions, gains, xbar, noise, H, r, Q, xhat0, P0, status0=None, state=None, tape=False,
+                    dtype=None):
+        """CopterVecEnv.rollout_lqg of this rank's envs: shard-local (gains, xbar, noise, xhat0, P0, status0, state: the
+        local envs')."""
+        return self.local.rollout_lqg(self._local_rollout_actions(actions), gains, xbar, noise, H, r, Q, xhat0, P0,
+                                      status0=status0, state=state, tape=tape, dtype=dtype)
+
     def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):
         """CopterVecEnv.rollout_rts of this rank's envs: shard-local (filt, x0, P0, status0, end: the local envs')."""
         return self.local.rollout_rts(self._local_rollout_actions(actions), filt, Q, x0, P0, status0=status0, end=end,

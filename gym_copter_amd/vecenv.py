@@ -28,6 +28,7 @@ import numpy as np
 from . import _lib
 from . import mlp as _mlp
 from . import pf as _pf
+from . import lqg as _lqg
 from .spaces import gymnasium_api
 
 # Envs that hold a device context.  Whatever is still open when the interpreter exits is closed by an exit handler,
@@ -107,6 +108,7 @@ EkfResult = collections.namedtuple("EkfResult", "x x_pred P var nis loglik statu
 # ok [N] bool (every Cholesky pivot positive and finite)
 RtsResult = collections.namedtuple("RtsResult", "x P_tape var x0 P0 ok")
 PfResult = _pf.PfResult      # CopterVecEnv.rollout_pf's result (pf.py)
+LqgResult = _lqg.LqgResult   # CopterVecEnv.rollout_lqg's result (lqg.py)
 # CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
 MppiCosts = collections.namedtuple("MppiCosts", "costs best")
 MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
@@ -1650,6 +1652,11 @@ class CopterVecEnv(_VectorEnvBase):
     #    driver in pf.py and is bound here.  (The list of guarded entry points in tests/test_gpu_output_bounds.py is
     #    read from this class's `def`s; rollout_pf's guarded-output test is in tests/test_gpu_rollout_pf.py.) --------
     rollout_pf = _pf.rollout_pf
+
+    # -- output-feedback rollouts, the feedback law on the filter's estimate: the host side lives with
+    #    its driver in lqg.py and is bound here, as rollout_pf is; its guarded-output test is
+    #    tests/test_gpu_lqg_output_bounds.py --------
+    rollout_lqg = _lqg.rollout_lqg
 
     # -- the Rauch-Tung-Striebel smoother over the filter's tapes --------
     def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):

@@ -1041,6 +1041,63 @@ typedef struct cs_rollout_pf_io {
 } cs_rollout_pf_io;
 int cs_rollout_pf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_pf_io* pio, void* stream);
 
+/* Output-feedback (LQG) rollouts on the device: cs_rollout_feedback_states' affine law evaluated
+ * at the estimate of cs_rollout_ekf's filter, which predicts with the very action the law just chose -- truth, sensor,
+ * filter and controller of K steps per env in one call.  Upstream lines composed: those of cs_rollout_states
+ * (envs/task.py:77-137 step, dynamics/__init__.py:114-197 setMotors) for the truth and those of cs_rollout_ekf
+ * (copterstep_jacobian.hip's: setMotors, the state derivative, step) for the filter.
+ *
+ * Per env, for step k = 1..K, in float64 without contraction, in this order:
+ *   law      a_k = fl32( abar_k + sum_{j=0..11} K_k[c][j] (xhat_{k-1}[j] - xbar_{k-1}[j]) ) per motor c: from (double) abar,
+ *            for j ascending one subtraction, one multiply and one add, never fused; one rounding to float32.  This is
+ *            cs_rollout_feedback_states' arithmetic without alpha d, at the filter's posterior mean instead of the true
+ *            state.  xhat_0 = xhat0_dev, the caller's starting estimate (step 1 has a deviation term); xbar_dev row k-1
+ *            is the reference point BEFORE step k; abar = io->actions_dev.  a_k is stored unclipped to actions_out_dev
+ *            (the step clips).
+ *   truth    one step of cs_rollout_states under a_k from io's start point -- the stored env or io's explicit start with
+ *            its pending force, a pending NEXT_STEP reset, prev_shaping, the step counter, the storage rounding of the
+ *            mode; no env state is written.  Its tapes go to io's x_dev, reward_dev, terminated_dev, truncated_dev and
+ *            status_dev (each may be NULL), bit-identical to cs_rollout_states fed actions_out_dev.
+ *   measure  z_k[i] = sum_j H[i][j] x_k[j] + e_k[i], x_k the row written to x_dev; j ascending, the first product starts
+ *            the sum, one multiply and one add per term, then one add of e.  e_dev is the caller's noise tape, already
+ *            scaled by sqrt(r); a NaN entry means "no measurement" and yields a NaN z.  z is stored to z_dev (or NULL).
+ *   filter   cs_rollout_ekf's predict under a_k (the same float32 value; the mean without storage rounding, P- = A P A^T
+ *            + Q), then its M sequential scalar updates on z_k.  xhat_dev, fstatus_dev (the filter's own status; it may
+ *            differ from the truth's), x_pred_dev, P_dev, P_tape_dev, var_dev, nis_dev, loglik_dev, branch_dev and ok_dev
+ *            are cs_rollout_ekf's x, status, ... outputs, defined and rounded (out_dtype) as there; each may be NULL.
+ * The truth has no process noise (its disturbance is the env's own perturbation force) and e is not drawn on the device.
+ * Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32; io's cotangent and gradient pointers must be NULL.
+ * Asynchronous on `stream`; lio->struct_size must be sizeof(cs_rollout_lqg_io) (else CS_ERR_ABI); both blocks are checked
+ * before the context, with cs_rollout_ekf's alignment rules. */
+typedef struct cs_rollout_lqg_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_lqg_io) */
+  uint32_t out_dtype;          /* CS_JAC_F64 / CS_JAC_F32: P_dev, P_tape_dev, var_dev, nis_dev, loglik_dev */
+  int32_t num_meas;            /* M, 1 .. CS_EKF_MAX_MEAS */
+  uint32_t reserved_;          /* 0 */
+  const double* K_dev;         /* [K,N,A,12] float64, required */
+  const double* xbar_dev;      /* [K,N,12] float64, required: row k-1 is the reference before step k */
+  const double* e_dev;         /* [K,N,M] float64, required: the measurement noise, NaN = no measurement */
+  const double* H_dev;         /* [M,12], required */
+  const double* r_dev;         /* [M], required */
+  const double* Q_dev;         /* [12,12], required */
+  const double* P0_dev;        /* [N,12,12], required */
+  const double* xhat0_dev;     /* [12,N], required: the starting estimate */
+  const uint8_t* status0_dev;  /* [N], required: its flight status */
+  float* actions_out_dev;      /* [K,N,A] float32, required */
+  double* z_dev;               /* [K,N,M] */
+  double* xhat_dev;            /* [K,N,12] */
+  double* x_pred_dev;          /* [K,N,12] */
+  void* P_dev;                 /* [N,12,12] */
+  void* P_tape_dev;            /* [K,N,12,12] */
+  void* var_dev;               /* [K,N,12] */
+  void* nis_dev;               /* [K,N] */
+  void* loglik_dev;            /* [N] */
+  uint8_t* fstatus_dev;        /* [K,N] */
+  uint8_t* branch_dev;         /* [K,N] */
+  uint8_t* ok_dev;             /* [N] */
+} cs_rollout_lqg_io;
+int cs_rollout_lqg(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_lqg_io* lio, void* stream);
+
 /* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
  * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,
  * tilt, the motor clip).  For every env, P perturbed copies of the nominal action tape abar = io->actions_dev [K,N,A] are

@@ -11,7 +11,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt ppo_grad > profiles/ppo_grad_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_ekf > profiles/rollout_ekf_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_rts > profiles/rollout_rts_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_pf > profiles/rollout_pf_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_pf > profiles/rollout_pf_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_lqg > profiles/rollout_lqg_resources.txt"""
 import re
 import sys
 
@@ -73,7 +74,10 @@ HEADS = {"rollout_mlp": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_pf.hip: the bootstrap particle filter
 # rollout_pf_kernel<TASK, MODE, GYRO> (one workgroup of min(P, 256) lanes per env; the particles, their weights and the
 # cumulative weights in dynamic LDS, 124 P + 3 072 bytes per workgroup -- not part of the static figure below; DESIGN.md
-# section 21)."""}
+# section 21).""", "rollout_lqg": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_lqg.hip: the output-feedback rollout
+# rollout_lqg_kernel<TASK, MODE, GYRO> (the filter's covariance, W = A P and means and the parked true state in
+# lane-private LDS columns, 265 rows: one wavefront per CU; DESIGN.md section 22)."""}
 
 
 def main(path, which="rollout_mlp"):
