@@ -5,7 +5,7 @@ and the Gymnasium-style vector-env host class.  See DESIGN.md and INTEGRATION.md
 """
 from ._lib import CopterStepError  # noqa: F401
 from .vecenv import (CopterVecEnv, EkfResult, LqgResult, LqrGains, MlpRollout, MppiCosts, MppiUpdate,  # noqa: F401
-                     PfResult, Rollout, RtsResult, StepJacobian)
+                     PfResult, Rollout, RtsResult, StepJacobian, UkfResult)
 from .vecenv import ActorCritic, MppiTemperature, Population, PpoGrad, mppi_knots  # noqa: F401
 from .autodiff import differentiable_mlp_rollout, differentiable_rollout, ppo_loss  # noqa: F401
 from . import mlp  # noqa: F401
@@ -14,6 +14,7 @@ from .mppi import mppi  # noqa: F401
 from .ekf import ekf, measure, smooth  # noqa: F401
 from .pf import pf  # noqa: F401
 from .lqg import lqg, measurement_noise  # noqa: F401
+from .ukf import ukf  # noqa: F401
 from .es import es  # noqa: F401
 from .ppo import ppo  # noqa: F401
 from .spaces import box_class as _box_class

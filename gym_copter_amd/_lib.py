@@ -148,6 +148,17 @@ class RolloutLqgIO(C.Structure):
                 ("ok_dev", C.c_void_p)]
 
 
+class RolloutUkfIO(C.Structure):
+    """Mirror of `struct cs_rollout_ukf_io` (cs_rollout_ukf)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_meas", C.c_int32),
+                ("reserved_", C.c_uint32), ("gamma", C.c_double), ("wm0", C.c_double), ("wc0", C.c_double),
+                ("wi", C.c_double), ("H_dev", C.c_void_p), ("r_dev", C.c_void_p), ("Q_dev", C.c_void_p),
+                ("P0_dev", C.c_void_p), ("z_dev", C.c_void_p), ("x_pred_dev", C.c_void_p), ("P_dev", C.c_void_p),
+                ("P_tape_dev", C.c_void_p), ("var_dev", C.c_void_p), ("nis_dev", C.c_void_p),
+                ("loglik_dev", C.c_void_p), ("spread_dev", C.c_void_p), ("ok_dev", C.c_void_p),
+                ("points_dev", C.c_void_p), ("points_pred_dev", C.c_void_p), ("point_status_dev", C.c_void_p)]
+
+
 class RolloutRtsIO(C.Structure):
     """Mirror of `struct cs_rollout_rts_io` (cs_rollout_rts)."""
     _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("x_f_dev", C.c_void_p),
@@ -312,6 +323,7 @@ SYMBOLS = {
     "cs_rollout_rts": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutRtsIO), _P]),
     "cs_rollout_pf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutPfIO), _P]),
     "cs_rollout_lqg": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqgIO), _P]),
+    "cs_rollout_ukf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutUkfIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),

@@ -228,6 +228,12 @@ class ShardedCopterVecEnv:
         return self.local.rollout_lqg(self._local_rollout_actions(actions), gains, xbar, noise, H, r, Q, xhat0, P0,
                                       status0=status0, state=state, tape=tape, dtype=dtype)
 
+    def rollout_ukf(self, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta=0.0, kappa=1.0, tape=False,
+                    points=False, dtype=None):
+        """CopterVecEnv.rollout_ukf of this rank's envs: shard-local (z, x0, P0, status0: the local envs')."""
+        return self.local.rollout_ukf(self._local_rollout_actions(actions), z, H, r, Q, x0, P0, status0=status0,
+                                      alpha=alpha, beta=beta, kappa=kappa, tape=tape, points=points, dtype=dtype)
+
     def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):
         """CopterVecEnv.rollout_rts of this rank's envs: shard-local (filt, x0, P0, status0, end: the local envs')."""
         return self.local.rollout_rts(self._local_rollout_actions(actions), filt, Q, x0, P0, status0=status0, end=end,

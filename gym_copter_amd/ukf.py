@@ -1,0 +1,151 @@
+"""The unscented Kalman filter on the device: CopterVecEnv.rollout_ukf -- one call of
+cs_rollout_ukf on the env's cached buffers; vecenv.py binds it to the class -- the weights of the scaled unscented
+transform, and ukf(), the streaming driver whose measurements arrive a chunk of steps at a time.
+
+    z = H x + e,  e ~ N(0, diag(r));     P = L L^T,  points xhat, xhat +- gamma L[:,j];     each through the step;
+    x-, P- = their weighted mean and covariance + Q;     sequential scalar updates
+
+It stands between rollout_ekf (one Jacobian, at the branch the mean is on) and rollout_pf (64 to 1 024 sampled
+particles): 25 deterministic points per env, no Jacobian, and a prior that sees every branch the points land on."""
+import collections
+import ctypes as C
+import math
+
+from . import _lib
+
+# CopterVecEnv.rollout_ukf's result: the filtered means x [K,N,12] and the priors x_pred [K,N,12], the last posterior
+# P [N,12,12], the posteriors' diagonals var [K,N,12], nis [K,N], loglik [N], the status [K,N] of the filter's own mean
+# (point 0's), spread [K,N] uint8 (how many of the 25 points ended the step with another status), ok [N] bool, P_tape
+# [K,N,12,12] (tape=True, else None) and, with points=True (else None), the points before the physics [K,N,25,12],
+# after it [K,N,25,12] and their statuses [K,N,25]
+UkfResult = collections.namedtuple(
+    "UkfResult", "x x_pred P var nis loglik status spread ok P_tape points points_pred point_status")
+
+NUM_POINTS = 25     # 2 * 12 + 1
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def weights(alpha=1.0, beta=0.0, kappa=1.0):
+    """(gamma, wm0, wc0, wi) of the scaled unscented transform for 12 states: lambda = alpha^2 (12 + kappa) - 12,
+    gamma = sqrt(12 + lambda), wm0 = lambda / (12 + lambda), wc0 = wm0 + 1 - alpha^2 + beta, wi = 1 / (2 (12 + lambda)).
+    wm0 + 24 wi = 1 whatever the arguments.  ValueError if 12 + lambda <= 0 or an argument is not finite."""
+    alpha, beta, kappa = float(alpha), float(beta), float(kappa)
+    if not all(math.isfinite(v) for v in (alpha, beta, kappa)):
+        raise ValueError("alpha, beta and kappa must be finite, got %r" % ((alpha, beta, kappa),))
+    lam = alpha * alpha * (12.0 + kappa) - 12.0
+    c = 12.0 + lam
+    if not c > 0.0:
+        raise ValueError("12 + lambda = alpha^2 (12 + kappa) must be > 0, got %r (alpha=%r, kappa=%r)" % (c, alpha, kappa))
+    wm0 = lam / c
+    return math.sqrt(c), wm0, wm0 + 1.0 - alpha * alpha + beta, 1.0 / (2.0 * c)
+
+
+def rollout_ukf(self, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta=0.0, kappa=1.0, tape=False,
+                points=False, dtype=None):
+    """An unscented Kalman filter over the env step, K predict / update steps per env in one kernel: 25 sigma points
+    per env and step, each through the step's own physics -- no Jacobian; a belief that straddles a touchdown, a crash
+    or the motor clip is propagated on every side its points land on.  The filter's state is the caller's: NO env state
+    is read but the configuration and the vehicle, and none changes.
+
+    actions, z (NaN = no measurement), H [M,12], r [M] > 0, Q [12,12] symmetric, x0 [12,N], P0 [N,12,12] (its upper
+    triangle is read) and status0 [N] (default AIRBORNE) are rollout_ekf's.  P0 must be positive definite, and Q should
+    be: the covariance is factored at every step, and a pivot that is <= 0 or not finite clears that env's ok (every
+    output is written regardless).
+
+    Per step: if the mean is LANDED, x- = xhat and P- = P + Q.  Else P = L L^T (lower Cholesky); the points are xhat,
+    xhat + gamma L[:,j] and xhat - gamma L[:,j], j = 0 .. 11, in this order; each goes through the physics from (the
+    point, the status of the mean), exactly as rollout_states takes it from that explicit start; the status after the
+    step is point 0's; x- = wm0 y0 + wi sum y_i, P- = wc0 d0 d0^T + wi sum d_i d_i^T + Q with d_i = y_i - x- (evaluated
+    in one pass about y0: include/copterstep.h).  Then rollout_ekf's sequential scalar updates.
+
+    alpha, beta, kappa: the scaled unscented transform's (weights()).  The defaults (1, 0, 1) make every weight positive,
+    hence P- positive semidefinite by construction; (1, 0, 0) is the cubature rule (wm0 = 0); a small alpha makes wm0 and
+    wc0 negative, and P- can then lose definiteness.  ValueError when 12 + lambda <= 0.
+
+    Returns UkfResult(x, x_pred, P, var, nis, loglik, status, spread, ok, P_tape, points, points_pred, point_status):
+    rollout_ekf's outputs without `branch`, plus spread [K,N] uint8 -- how many of the 25 points ended the step with
+    another status than point 0's (0 on a LANDED step) -- and, with points=True, the points before the physics
+    [K,N,25,12], after it [K,N,25,12] and their statuses [K,N,25] (always float64; on a LANDED step all 25 rows hold
+    xhat and the statuses are LANDED).  dtype: torch.float64 (default) or torch.float32 (P, var, nis, loglik, P_tape:
+    the float64 values rounded).  Not available under action_arith="float32".  Asynchronous on the current stream; the
+    tensors are buffers of this env, overwritten by its next call with the same K, dtype, tape and points."""
+    self._check_open()
+    torch = _torch()
+    dtype = self._out_dtype(dtype)
+    gamma, wm0, wc0, wi = weights(alpha, beta, kappa)
+    Hd, rd, Qd = self._filter_model("ukf", (H, r, Q), lambda: (
+        *self._measurement_model(H, r), self._process_noise(Q)))
+    M = int(Hd.shape[0])
+    io, K, keep = self._rollout_io(actions, None)
+    n, dev = self.num_envs, self.device
+    zt = self._ekf_input(z, (K, n, M), "z", keep)
+    xt = self._ekf_input(x0, (12, n), "x0", keep)
+    Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
+    self._start_status(io, status0, keep)
+    io.start_x_dev = xt.data_ptr()
+    uio = _lib.RolloutUkfIO()
+    uio.struct_size = C.sizeof(_lib.RolloutUkfIO)
+    uio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
+    uio.num_meas = M
+    uio.gamma, uio.wm0, uio.wc0, uio.wi = gamma, wm0, wc0, wi
+    uio.H_dev, uio.r_dev, uio.Q_dev = Hd.data_ptr(), rd.data_ptr(), Qd.data_ptr()
+    uio.P0_dev, uio.z_dev = Pt.data_ptr(), zt.data_ptr()
+    tape, points = bool(tape), bool(points)
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+    out = self._rollout_cache(("ukf", K, dtype, tape, points), lambda: UkfResult(
+        e((K, n, 12), torch.float64), e((K, n, 12), torch.float64), e((n, 12, 12), dtype), e((K, n, 12), dtype),
+        e((K, n), dtype), e(n, dtype), e((K, n), torch.uint8), e((K, n), torch.uint8), e(n, torch.bool),
+        e((K, n, 12, 12), dtype) if tape else None,
+        e((K, n, NUM_POINTS, 12), torch.float64) if points else None,
+        e((K, n, NUM_POINTS, 12), torch.float64) if points else None,
+        e((K, n, NUM_POINTS), torch.uint8) if points else None))
+    io.x_dev, io.status_dev = out.x.data_ptr(), out.status.data_ptr()
+    uio.x_pred_dev, uio.P_dev, uio.var_dev = out.x_pred.data_ptr(), out.P.data_ptr(), out.var.data_ptr()
+    uio.nis_dev, uio.loglik_dev = out.nis.data_ptr(), out.loglik.data_ptr()
+    uio.spread_dev, uio.ok_dev = out.spread.data_ptr(), out.ok.data_ptr()
+    if tape:
+        uio.P_tape_dev = out.P_tape.data_ptr()
+    if points:
+        uio.points_dev, uio.points_pred_dev = out.points.data_ptr(), out.points_pred.data_ptr()
+        uio.point_status_dev = out.point_status.data_ptr()
+    with torch.cuda.device(self.device):
+        _lib.check(self._lib.cs_rollout_ukf(self._ctx, C.byref(io), C.byref(uio), self._stream()))
+    self._keep = keep + [Hd, rd, Qd]
+    return out
+
+
+def ukf(env, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta=0.0, kappa=1.0, chunk=None, points=False):
+    """Run env.rollout_ukf over actions [K,N,A] and z [K,N,M] in chunks of `chunk` steps (None: one call), as a filter
+    whose measurements arrive `chunk` at a time: the mean, the covariance and the status after each chunk start the next.
+    Returns UkfResult with the tapes of all K steps concatenated (P_tape included; the point tapes with points=True), P
+    the last posterior, loglik the sum of the chunks' and ok their conjunction -- tensors of their own, not the env's
+    buffers.  Every tape, P and ok are bit-identical to the single call's: a chunk boundary rounds nothing (float64
+    throughout).  loglik equals the single call's to rounding only: it is the sum of the chunks' sums.  The other
+    arguments are rollout_ukf's."""
+    torch = _torch()
+    K = int(actions.shape[0])
+    chunk = K if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1, got %r" % (chunk,))
+    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] != K:
+        raise ValueError("z must be a tensor of shape (K, N, M) with K = %d steps" % K)
+    taped = ("x", "x_pred", "var", "nis", "status", "spread", "P_tape") + \
+        (("points", "points_pred", "point_status") if points else ())
+    parts = {name: [] for name in taped}
+    x, P, status = x0, P0, status0
+    loglik, ok = None, None
+    for k0 in range(0, K, chunk):
+        res = env.rollout_ukf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, x, P, status0=status, alpha=alpha,
+                              beta=beta, kappa=kappa, tape=True, points=points)
+        for name in taped:
+            parts[name].append(getattr(res, name).clone())
+        x, P, status = res.x[-1].T.contiguous(), res.P.clone(), res.status[-1].clone()
+        loglik = res.loglik.clone() if loglik is None else loglik + res.loglik
+        ok = res.ok.clone() if ok is None else ok & res.ok
+    cat = {name: torch.cat(parts[name]) for name in taped}
+    return UkfResult(cat["x"], cat["x_pred"], P, cat["var"], cat["nis"], loglik, cat["status"], cat["spread"], ok,
+                     cat["P_tape"], cat.get("points"), cat.get("points_pred"), cat.get("point_status"))

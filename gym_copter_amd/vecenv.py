@@ -29,6 +29,7 @@ from . import _lib
 from . import mlp as _mlp
 from . import pf as _pf
 from . import lqg as _lqg
+from . import ukf as _ukf
 from .spaces import gymnasium_api
 
 # Envs that hold a device context.  Whatever is still open when the interpreter exits is closed by an exit handler,
@@ -109,6 +110,7 @@ EkfResult = collections.namedtuple("EkfResult", "x x_pred P var nis loglik statu
 RtsResult = collections.namedtuple("RtsResult", "x P_tape var x0 P0 ok")
 PfResult = _pf.PfResult      # CopterVecEnv.rollout_pf's result (pf.py)
 LqgResult = _lqg.LqgResult   # CopterVecEnv.rollout_lqg's result (lqg.py)
+UkfResult = _ukf.UkfResult   # CopterVecEnv.rollout_ukf's result (ukf.py)
 # CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
 MppiCosts = collections.namedtuple("MppiCosts", "costs best")
 MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
@@ -1657,6 +1659,11 @@ class CopterVecEnv(_VectorEnvBase):
     #    its driver in lqg.py and is bound here, as rollout_pf is; its guarded-output test is
     #    tests/test_gpu_lqg_output_bounds.py --------
     rollout_lqg = _lqg.rollout_lqg
+
+    # -- the unscented Kalman filter over the env step: the host side lives with its streaming driver
+    #    in ukf.py and is bound here, as rollout_pf is; its guarded-output test is
+    #    tests/test_gpu_ukf_output_bounds.py --------
+    rollout_ukf = _ukf.rollout_ukf
 
     # -- the Rauch-Tung-Striebel smoother over the filter's tapes --------
     def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):

@@ -43,6 +43,8 @@
  *                            over that filter's tapes            counterpart: a fixed-interval smoother)
  *   cs_rollout_pf            a bootstrap particle filter over   the rollout lines above, per particle (no upstream
  *                            the step, K steps per env           counterpart: a sampling state estimator)
+ *   cs_rollout_ukf           an unscented Kalman filter over    the rollout lines above, per sigma point (no upstream
+ *                            the step, K steps per env           counterpart: a derivative-free state estimator)
  *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
  *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
  *   cs_rollout_mppi_update   their cost-weighted average         (the same)
@@ -1097,6 +1099,76 @@ typedef struct cs_rollout_lqg_io {
   uint8_t* ok_dev;             /* [N] */
 } cs_rollout_lqg_io;
 int cs_rollout_lqg(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_lqg_io* lio, void* stream);
+
+/* An unscented Kalman filter over the env step, on the device: K predict / update steps per env
+ * in one call, between cs_rollout_ekf (one Jacobian at the mean's own branch) and cs_rollout_pf (64 to 1 024 sampled
+ * particles): 2 * 12 + 1 = 25 deterministic sigma points per env, each through the step's own physics, no Jacobian.
+ * The filter's state -- the mean xhat [12], the covariance P [12,12] and the flight status of the mean -- is the
+ * CALLER's: no env state is read except the context's constants and vehicle table, and none is written.  The measurement
+ * model, the process noise, io's fields and the update are cs_rollout_ekf's.  Upstream lines: those of cs_rollout_states,
+ * per point.
+ *
+ * From io: as cs_rollout_ekf (num_steps, actions_dev, start_x_dev = xhat_0, start_status_dev; x_dev and status_dev
+ * receive the filtered means and the status of the mean; everything else NULL).
+ * From uio: num_meas, H_dev, r_dev, Q_dev, P0_dev, z_dev as cs_rollout_ekf's (P0 must be positive definite and Q should
+ * be: the covariance is factored at every step), and the points' spread and weights
+ *   gamma  finite, > 0     wm0, wc0, wi  finite (else CS_ERR_ARG)
+ * For the scaled transform of (alpha, beta, kappa): lambda = alpha^2 (12 + kappa) - 12, gamma = sqrt(12 + lambda),
+ * wm0 = lambda / (12 + lambda), wc0 = wm0 + 1 - alpha^2 + beta, wi = 1 / (2 (12 + lambda)); the call knows nothing of
+ * them.  The prior's covariance below is the weighted covariance about the weighted mean when wm0 + 24 wi = 1, which
+ * the scaled transform guarantees.
+ * Per step k = 1..K and env, in float64 without contraction (the arithmetic of gym_copter_amd/csrc/ukf_points.h, which
+ * tests/ukf_ref.py restates):
+ *   landed    if the status of the mean is LANDED no points are made: x- = xhat, P- = P + Q with one add per entry.
+ *   factor    else P = L L^T, L = U^T of cs_rollout_rts' Cholesky factorisation (column by column, the reciprocal root
+ *             of a pivot kept; L[j][j] = 1 / that).  A pivot that is <= 0 or not finite clears the env's ok; the
+ *             arithmetic is carried through and every output is written regardless.
+ *   points    point 0 = xhat, point 1+j = xhat + gamma L[:,j], point 13+j = xhat - gamma L[:,j], j = 0 .. 11 (entries
+ *             above the column's diagonal are xhat's own).
+ *   propagate each point through the physics of step k under actions[k-1] from (the point, the status of the mean), as
+ *             cs_rollout_ekf's mean goes: no storage rounding, no pending perturbation, a status variable of its own.
+ *             In float64 storage a propagated point is cs_rollout_states' row from that explicit start bit for bit.  The
+ *             filter's status after the step is point 0's.
+ *   moments   with y_i the propagated points, sy = y_1 + .. + y_24 and S = sum_{i=1..24} (y_i - y_0)(y_i - y_0)^T summed
+ *             in that order from zero:  x- = wm0 y_0 + wi sy;  m = x- - y_0;
+ *             P- = (wi S - (2 - (wc0 + 24 wi)) m m^T) + Q, the upper triangle, Q last with one add per entry.
+ *   update    cs_rollout_ekf's, with its nis, loglik and ok.
+ * Outputs, each may be NULL; x_pred, P, P_tape, var, nis, loglik and ok as cs_rollout_ekf's (out_dtype likewise), and
+ *   spread_dev       [K,N] uint8        how many of the 25 points ended the step with another status than point 0's
+ *                                       (0 on a LANDED step)
+ *   points_dev       [K,N,25,12] float64  the points before the physics      (for tests and diagnosis; on a LANDED
+ *   points_pred_dev  [K,N,25,12] float64  ... and after it                    step all 25 rows hold xhat and the
+ *   point_status_dev [K,N,25] uint8       their statuses after it             statuses are LANDED)
+ * Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32.  Asynchronous on `stream`; uio->struct_size must be
+ * sizeof(cs_rollout_ukf_io) (else CS_ERR_ABI); both blocks are checked before the context, with cs_rollout_ekf's
+ * alignment rules. */
+typedef struct cs_rollout_ukf_io {
+  uint32_t struct_size;        /* sizeof(cs_rollout_ukf_io) */
+  uint32_t out_dtype;          /* CS_JAC_F64 / CS_JAC_F32: P_dev, P_tape_dev, var_dev, nis_dev, loglik_dev */
+  int32_t num_meas;            /* M, 1 .. CS_EKF_MAX_MEAS */
+  uint32_t reserved_;          /* 0 */
+  double gamma;                /* the points' spread, finite and > 0 */
+  double wm0;                  /* the centre point's weight in the mean, finite */
+  double wc0;                  /* the centre point's weight in the covariance, finite */
+  double wi;                   /* every other point's weight, finite */
+  const double* H_dev;         /* [M,12], required */
+  const double* r_dev;         /* [M], required */
+  const double* Q_dev;         /* [12,12], required */
+  const double* P0_dev;        /* [N,12,12], required, positive definite */
+  const double* z_dev;         /* [K,N,M], required */
+  double* x_pred_dev;          /* [K,N,12] */
+  void* P_dev;                 /* [N,12,12] */
+  void* P_tape_dev;            /* [K,N,12,12] */
+  void* var_dev;               /* [K,N,12] */
+  void* nis_dev;               /* [K,N] */
+  void* loglik_dev;            /* [N] */
+  uint8_t* spread_dev;         /* [K,N] */
+  uint8_t* ok_dev;             /* [N] */
+  double* points_dev;          /* [K,N,25,12] */
+  double* points_pred_dev;     /* [K,N,25,12] */
+  uint8_t* point_status_dev;   /* [K,N,25] */
+} cs_rollout_ukf_io;
+int cs_rollout_ukf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_ukf_io* uio, void* stream);
 
 /* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
  * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,

@@ -12,7 +12,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_ekf > profiles/rollout_ekf_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_rts > profiles/rollout_rts_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_pf > profiles/rollout_pf_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_lqg > profiles/rollout_lqg_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_lqg > profiles/rollout_lqg_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_ukf > profiles/rollout_ukf_resources.txt"""
 import re
 import sys
 
@@ -77,7 +78,10 @@ HEADS = {"rollout_mlp": """\
 # section 21).""", "rollout_lqg": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_lqg.hip: the output-feedback rollout
 # rollout_lqg_kernel<TASK, MODE, GYRO> (the filter's covariance, W = A P and means and the parked true state in
-# lane-private LDS columns, 265 rows: one wavefront per CU; DESIGN.md section 22)."""}
+# lane-private LDS columns, 265 rows: one wavefront per CU; DESIGN.md section 22).""", "rollout_ukf": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_ukf.hip: the unscented Kalman filter
+# rollout_ukf_kernel<TASK, MODE, GYRO> (the covariance, its factor, the moment sum, the mean and the propagated centre
+# point in lane-private LDS columns, 258 rows: one wavefront per CU; DESIGN.md section 23)."""}
 
 
 def main(path, which="rollout_mlp"):
