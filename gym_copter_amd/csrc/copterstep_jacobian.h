@@ -39,6 +39,11 @@ struct FilterExt {
 // is set, else nullptr); out_dtype is known.
 int check_filter_io(const cs_rollout_io* io, const char* who, const FilterExt& ext, const char* start_missing,
                     const char* must_be_null);
+// The model checks of cs_rollout_ekf, cs_rollout_ukf and cs_rollout_lqg, in the order they always made them: num_meas
+// is 1 .. CS_EKF_MAX_MEAS; `own_failed` (the entry point's text if a check of its own that stands here fails, else
+// nullptr); none of `required` (`required_names` in the message) is NULL.
+int check_filter_model(const char* who, int32_t num_meas, const char* own_failed,
+                       std::initializer_list<const void*> required, const char* required_names);
 // After the entry point's own checks: the float64 arrays are 8-B aligned, the out_dtype arrays to their element, the
 // 32-bit ones (`w32_names` in the message) to 4 B; then enter_context, and the float32 motor law is refused.
 int enter_filter_context(cs_ctx* ctx, const char* who, void* stream, uint32_t out_dtype,

@@ -10,6 +10,8 @@
 //   covariance  P- = A P A^T + Q by cov_predict (cov_tile.h: jacobian_block with zero wrench tangents -- the actions are
 //               known -- in two passes of 6 blocks of 2 directions), the function the smoother calls for the same prior
 //   update      M sequential scalar updates (ekf_update.h)
+// The kernel is a start, a loop of predict / update / store and an end, every piece of it filter_step.h's: the functions
+// copterstep_rollout_lqg.hip calls for its filter and, but for the predict, copterstep_rollout_ukf.hip for its own.
 // P (78 rows, packed upper triangle), W (144 rows and one row of stage padding behind it), the mean at the start of the
 // step (12 rows) and the prior / posterior mean (12 rows) live in lane-private LDS columns (element j of a lane at
 // [j * 64 + lane], as section 13's): 247 rows x 512 B = 123.5 KiB, one wavefront per CU
@@ -35,6 +37,7 @@
 #include "rollout_sweep.h"
 #include "ekf_update.h"
 #include "cov_tile.h"
+#include "filter_step.h"
 #include "dev_launch.h"
 
 namespace cs {
@@ -64,7 +67,7 @@ __global__ __launch_bounds__(kBlock) void rollout_ekf_kernel(const DevConst c, c
   const uint32_t ii = ro.valid ? i : 0u;  // (padding lanes filter env 0 and store nothing)
   const int K = io.num_steps;
   const int M = e.num_meas;
-  const uint32_t f32 = e.out_dtype == CS_JAC_F32 ? 1u : 0u;
+  const FilterTapes t = filter_tapes(io, e);
 
   Coef q = uniform_coef(c);
   if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
@@ -75,106 +78,25 @@ __global__ __launch_bounds__(kBlock) void rollout_ekf_kernel(const DevConst c, c
   double* const stage = lds + kRowW * kBlock;
 
   // ---- the caller's filter state: xhat_0, its status, the upper triangle of P0 ----
-#pragma unroll
-  for (int j = 0; j < 12; ++j) X[j * kBlock] = io.start_x_dev[(size_t)j * n + ii];
-  int fs = (int)io.start_status_dev[ii];
-  {
-    const double* p0 = e.P0_dev + (size_t)ii * 144;
-#pragma clang loop unroll(disable)
-    for (int j = 0; j < 12; ++j) {
-#pragma clang loop unroll(disable)
-      for (int a = 0; a <= j; ++a) P[(j * (j + 1) / 2 + a) * kBlock] = p0[a * 12 + j];
-    }
-  }
+  int fs = filter_load_start(X, P, io.start_x_dev, io.start_status_dev, e.P0_dev, n, ii);
   EkfStats st{0.0, 0.0, true};
 
 #pragma clang loop unroll(disable)
   for (int k = 0; k < K; ++k) {
     const size_t row = (size_t)k * n;  // 64-bit: K x N x 144 doubles pass 4 GiB at 1 M envs
     const float4 act = load_action_at<TASK>(io.actions_dev + (row + ii) * A);
-    bool clipped;
-    const Wrench w = step_wrench(q, act, &clipped);
-    const int fs0 = fs;
-    uint32_t bits = (fs0 == CS_STATUS_LANDED ? (uint32_t)kJacLanded : 0u) | (clipped ? (uint32_t)kJacClipped : 0u);
-
-    // ---- the mean: rollout_step's physics from (xhat, status), no storage rounding; xhat is kept as the Jacobian's
-    //      point ----
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) {
-        x[j] = X[j * kBlock];
-        X0[j * kBlock] = x[j];
-      }
-      if (fs0 != CS_STATUS_LANDED) {
-        bool pend = false;
-        physics_substeps<FULL, GYRO, false, true>(c, q, w, x, fs, pend, -0.0, -0.0, -0.0);
-      }
-#pragma unroll
-      for (int j = 0; j < 12; ++j) X[j * kBlock] = x[j];
-    }
-
-    // ---- the covariance: P- = A P A^T + Q at the mean the step started from ----
-    bits |= cov_predict<FULL, GYRO>(c, q, w, fs0, X0, kBlock, P, W, e.Q_dev);
-
-    // ---- the prior mean out (W is dead: its rows are the stage) ----
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) x[j] = X[j * kBlock];
-      wave_sync();
-      if (e.x_pred_dev != nullptr) store_x_row(stage, e.x_pred_dev, row, ro, x);
-    }
-
-    // ---- the update: M scalar measurements in order ----
-    st.nis = 0.0;
-    {
-      const double* zr = e.z_dev + (row + ii) * (size_t)M;
-#pragma clang loop unroll(disable)
-      for (int m = 0; m < M; ++m) ekf_scalar_update(X, P, kBlock, e.H_dev + m * 12, e.r_dev[m], zr[m], st);
-    }
-
-    // ---- the tapes of row k ----
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) x[j] = X[j * kBlock];
-      if (io.x_dev != nullptr) store_x_row(stage, io.x_dev, row, ro, x);
-    }
-    const bool last = k == K - 1;
-    if (e.P_tape_dev != nullptr || (last && e.P_dev != nullptr)) {
-      stage_triangle(stage + lane * kStageStride, P);
-      wave_sync();
-      if (e.P_tape_dev != nullptr) store_matrix(e.P_tape_dev, row, stage, ro, f32);
-      if (last && e.P_dev != nullptr) store_matrix(e.P_dev, 0, stage, ro, f32);
-      wave_sync();  // (the next step's W is written over the stage)
-    }
-    if (ro.valid) {
-      if (e.var_dev != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) store_out(e.var_dev, (row + i) * 12 + j, P[(j * (j + 1) / 2 + j) * kBlock], f32);
-      }
-      if (e.nis_dev != nullptr) store_out(e.nis_dev, row + i, st.nis, f32);
-      if (io.status_dev != nullptr) io.status_dev[row + i] = (uint8_t)fs;
-      if (e.branch_dev != nullptr) e.branch_dev[row + i] = (uint8_t)bits;
-    }
+    const uint32_t bits = ekf_predict<FULL, GYRO>(c, q, act, fs, X, X0, P, W, e.Q_dev, stage, t.x_pred, row, ro);
+    const double* zr = e.z_dev + (row + ii) * (size_t)M;
+    filter_update(X, P, e.H_dev, e.r_dev, M, st, [zr](int m) { return zr[m]; });
+    filter_store_row<false>(t, stage, X, P, row, ro, k == K - 1, fs, bits, st.nis);
   }
-
-  if (ro.valid) {
-    if (e.loglik_dev != nullptr) store_out(e.loglik_dev, i, st.loglik, f32);
-    if (e.ok_dev != nullptr) e.ok_dev[i] = st.ok ? 1 : 0;
-  }
+  filter_store_end(t, ro, st);
 }
 
 template <int TASK, int MODE>
 hipError_t ekf_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const cs_rollout_ekf_io& e,
                  hipStream_t stream) {
-  const dim3 grid(grid_for(s.n)), block(kBlock);
-  if (c.gyro)
-    hipLaunchKernelGGL((rollout_ekf_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, e);
-  else
-    hipLaunchKernelGGL((rollout_ekf_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, e);
-  return hipGetLastError();
+  CS_GYRO_LAUNCH(rollout_ekf_kernel, io, e);
 }
 
 hipError_t launch_rollout_ekf(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
@@ -197,11 +119,10 @@ extern "C" int cs_rollout_ekf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rol
                                     no_start ? "start_x_dev (the mean) and start_status_dev are required" : nullptr,
                                     extra ? "the reward, flag, cotangent and gradient pointers must be NULL" : nullptr))
     return rc_;
-  if (eio->num_meas < 1 || eio->num_meas > CS_EKF_MAX_MEAS)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: num_meas must be 1 .. CS_EKF_MAX_MEAS");
-  if (eio->H_dev == nullptr || eio->r_dev == nullptr || eio->Q_dev == nullptr || eio->P0_dev == nullptr ||
-      eio->z_dev == nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_ekf: H_dev, r_dev, Q_dev, P0_dev and z_dev are required");
+  if (int rc_ = cs::check_filter_model(who, eio->num_meas, nullptr,
+                                       {eio->H_dev, eio->r_dev, eio->Q_dev, eio->P0_dev, eio->z_dev},
+                                       "H_dev, r_dev, Q_dev, P0_dev and z_dev"))
+    return rc_;
   cs::ContextView v;
   if (int rc_ = cs::enter_filter_context(
           ctx, who, stream, eio->out_dtype,

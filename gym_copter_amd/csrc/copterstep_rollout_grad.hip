@@ -288,6 +288,17 @@ int check_filter_io(const cs_rollout_io* io, const char* who, const FilterExt& e
   return CS_OK;
 }
 
+int check_filter_model(const char* who, int32_t num_meas, const char* own_failed,
+                       std::initializer_list<const void*> required, const char* required_names) {
+  const std::string w(who);
+  if (num_meas < 1 || num_meas > CS_EKF_MAX_MEAS)
+    return report_error(CS_ERR_ARG, (w + ": num_meas must be 1 .. CS_EKF_MAX_MEAS").c_str());
+  if (own_failed != nullptr) return report_error(CS_ERR_ARG, (w + ": " + own_failed).c_str());
+  for (const void* p : required)
+    if (p == nullptr) return report_error(CS_ERR_ARG, (w + ": " + required_names + " are required").c_str());
+  return CS_OK;
+}
+
 int enter_filter_context(cs_ctx* ctx, const char* who, void* stream, uint32_t out_dtype,
                          std::initializer_list<const void*> f64s, std::initializer_list<const void*> outs,
                          std::initializer_list<const void*> w32s, const char* w32_names, ContextView* out) {

@@ -10,8 +10,9 @@
 // One lane per env on the tile layout of the step kernels (tile t -> workgroup t).  Per step:
 //   law      lqg_law.h at the posterior mean of the step before (the lane's LDS column X)
 //   truth    rollout_step / next_perturbation (rollout_step.h) from the lane's parked truth, as rollout_forward makes it
-//   filter   copterstep_rollout_ekf.hip's step: step_wrench, physics_substeps, cov_predict (cov_tile.h), then M times
-//            lqg_measure (lqg_law.h) on the parked true state and ekf_scalar_update (ekf_update.h)
+//   filter   the calls copterstep_rollout_ekf.hip makes (filter_step.h): ekf_predict, filter_update -- its measurement
+//            lqg_measure (lqg_law.h) on the parked true state, not a tape's entry -- and filter_store_row; the filter is
+//            cs_rollout_ekf's by construction, not by two texts that agree
 // The filter's LDS rows are copterstep_rollout_ekf.hip's (P 78, W 144 + 1, the step's start mean 12, the mean 12); the
 // truth does not fit in registers across cov_predict and is parked behind them in 18 more lane-private rows (x 12, the
 // pending force 3, prev_shaping, and two rows of packed integers) between its step and the next: 265 rows x 512 B =
@@ -38,6 +39,7 @@
 #include "ekf_update.h"
 #include "lqg_law.h"
 #include "cov_tile.h"
+#include "filter_step.h"
 #include "dev_launch.h"
 
 namespace cs {
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void rollout_lqg_kernel(const DevConst c, c
   const uint32_t ii = ro.valid ? i : 0u;  // (padding lanes read env 0's inputs and store nothing)
   const int K = io.num_steps;
   const int M = g.num_meas;
-  const uint32_t f32 = g.out_dtype == CS_JAC_F32 ? 1u : 0u;
+  const FilterTapes t = filter_tapes(io, g);
 
   Coef q = uniform_coef(c);
   if (s.veh != nullptr) q = load_coef(s.veh, s.veh_stride, ii);
@@ -134,17 +136,7 @@ __global__ __launch_bounds__(kBlock) void rollout_lqg_kernel(const DevConst c, c
   }
 
   // ---- the caller's filter state: xhat_0, its status, the upper triangle of P0 ----
-#pragma unroll
-  for (int j = 0; j < 12; ++j) X[j * kBlock] = g.xhat0_dev[(size_t)j * n + ii];
-  int fs = (int)g.status0_dev[ii];
-  {
-    const double* p0 = g.P0_dev + (size_t)ii * 144;
-#pragma clang loop unroll(disable)
-    for (int j = 0; j < 12; ++j) {
-#pragma clang loop unroll(disable)
-      for (int a = 0; a <= j; ++a) P[(j * (j + 1) / 2 + a) * kBlock] = p0[a * 12 + j];
-    }
-  }
+  int fs = filter_load_start(X, P, g.xhat0_dev, g.status0_dev, g.P0_dev, n, ii);
   EkfStats st{0.0, 0.0, true};
 
 #pragma clang loop unroll(disable)
@@ -193,93 +185,24 @@ __global__ __launch_bounds__(kBlock) void rollout_lqg_kernel(const DevConst c, c
       }
     }
 
-    // ---- the filter's step under the same action, as copterstep_rollout_ekf.hip makes it ----
-    bool clipped;
-    const Wrench w = step_wrench(q, act, &clipped);
-    const int fs0 = fs;
-    uint32_t bits = (fs0 == CS_STATUS_LANDED ? (uint32_t)kJacLanded : 0u) | (clipped ? (uint32_t)kJacClipped : 0u);
-
-    // the mean: rollout_step's physics from (xhat, status), no storage rounding; xhat is kept as the Jacobian's point
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) {
-        x[j] = X[j * kBlock];
-        X0[j * kBlock] = x[j];
-      }
-      if (fs0 != CS_STATUS_LANDED) {
-        bool pend = false;
-        physics_substeps<FULL, GYRO, false, true>(c, q, w, x, fs, pend, -0.0, -0.0, -0.0);
-      }
-#pragma unroll
-      for (int j = 0; j < 12; ++j) X[j * kBlock] = x[j];
-    }
-
-    // the covariance: P- = A P A^T + Q at the mean the step started from
-    bits |= cov_predict<FULL, GYRO>(c, q, w, fs0, X0, kBlock, P, W, g.Q_dev);
-
-    // the prior mean out (W is dead again)
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) x[j] = X[j * kBlock];
-      wave_sync();
-      if (g.x_pred_dev != nullptr) store_x_row(stage, g.x_pred_dev, row, ro, x);
-    }
-
-    // ---- the measurement of the parked true state and its update, M scalars in order ----
-    st.nis = 0.0;
-    {
-      const double* er = g.e_dev + (row + ii) * (size_t)M;
-#pragma clang loop unroll(disable)
-      for (int m = 0; m < M; ++m) {
-        const double z = lqg_measure(g.H_dev + m * 12, T, kBlock, er[m]);
-        if (g.z_dev != nullptr && ro.valid) g.z_dev[(row + i) * (size_t)M + m] = z;
-        ekf_scalar_update(X, P, kBlock, g.H_dev + m * 12, g.r_dev[m], z, st);
-      }
-    }
-
-    // ---- the filter's tapes of row k ----
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) x[j] = X[j * kBlock];
-      if (g.xhat_dev != nullptr) store_x_row(stage, g.xhat_dev, row, ro, x);
-    }
-    const bool last = k == K - 1;
-    if (g.P_tape_dev != nullptr || (last && g.P_dev != nullptr)) {
-      stage_triangle(stage + lane * kStageStride, P);
-      wave_sync();
-      if (g.P_tape_dev != nullptr) store_matrix(g.P_tape_dev, row, stage, ro, f32);
-      if (last && g.P_dev != nullptr) store_matrix(g.P_dev, 0, stage, ro, f32);
-      wave_sync();  // (the next step's x row and W are written over the stage)
-    }
-    if (ro.valid) {
-      if (g.var_dev != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) store_out(g.var_dev, (row + i) * 12 + j, P[(j * (j + 1) / 2 + j) * kBlock], f32);
-      }
-      if (g.nis_dev != nullptr) store_out(g.nis_dev, row + i, st.nis, f32);
-      if (g.fstatus_dev != nullptr) g.fstatus_dev[row + i] = (uint8_t)fs;
-      if (g.branch_dev != nullptr) g.branch_dev[row + i] = (uint8_t)bits;
-    }
+    // ---- the filter's step under the same action: copterstep_rollout_ekf.hip's calls (filter_step.h), the measurement
+    //      formed from the parked true state and written out on the way ----
+    const uint32_t bits = ekf_predict<FULL, GYRO>(c, q, act, fs, X, X0, P, W, g.Q_dev, stage, t.x_pred, row, ro);
+    const double* er = g.e_dev + (row + ii) * (size_t)M;
+    filter_update(X, P, g.H_dev, g.r_dev, M, st, [&](int m) {
+      const double z = lqg_measure(g.H_dev + m * 12, T, kBlock, er[m]);
+      if (g.z_dev != nullptr && ro.valid) g.z_dev[(row + i) * (size_t)M + m] = z;
+      return z;
+    });
+    filter_store_row<false>(t, stage, X, P, row, ro, k == K - 1, fs, bits, st.nis);
   }
-
-  if (ro.valid) {
-    if (g.loglik_dev != nullptr) store_out(g.loglik_dev, i, st.loglik, f32);
-    if (g.ok_dev != nullptr) g.ok_dev[i] = st.ok ? 1 : 0;
-  }
+  filter_store_end(t, ro, st);
 }
 
 template <int TASK, int MODE>
 hipError_t lqg_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const cs_rollout_lqg_io& g,
                  hipStream_t stream) {
-  const dim3 grid(grid_for(s.n)), block(kBlock);
-  if (c.gyro)
-    hipLaunchKernelGGL((rollout_lqg_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, g);
-  else
-    hipLaunchKernelGGL((rollout_lqg_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, g);
-  return hipGetLastError();
+  CS_GYRO_LAUNCH(rollout_lqg_kernel, io, g);
 }
 
 hipError_t launch_rollout_lqg(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
@@ -302,14 +225,13 @@ extern "C" int cs_rollout_lqg(cs_ctx* ctx, const cs_rollout_io* io, const cs_rol
     return report_error(CS_ERR_ARG, "cs_rollout_lqg: the cotangent and gradient pointers must be NULL");
   if (lio->out_dtype != CS_JAC_F64 && lio->out_dtype != CS_JAC_F32)
     return report_error(CS_ERR_ARG, "cs_rollout_lqg: unknown lio->out_dtype (CS_JAC_F64 or CS_JAC_F32)");
-  if (lio->num_meas < 1 || lio->num_meas > CS_EKF_MAX_MEAS)
-    return report_error(CS_ERR_ARG, "cs_rollout_lqg: num_meas must be 1 .. CS_EKF_MAX_MEAS");
-  if (lio->K_dev == nullptr || lio->xbar_dev == nullptr || lio->e_dev == nullptr || lio->actions_out_dev == nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_lqg: K_dev, xbar_dev, e_dev and actions_out_dev are required");
-  if (lio->H_dev == nullptr || lio->r_dev == nullptr || lio->Q_dev == nullptr || lio->P0_dev == nullptr ||
-      lio->xhat0_dev == nullptr || lio->status0_dev == nullptr)
-    return report_error(CS_ERR_ARG,
-                        "cs_rollout_lqg: H_dev, r_dev, Q_dev, P0_dev, xhat0_dev and status0_dev are required");
+  const bool no_law =
+      lio->K_dev == nullptr || lio->xbar_dev == nullptr || lio->e_dev == nullptr || lio->actions_out_dev == nullptr;
+  if (int rc_ = cs::check_filter_model(
+          who, lio->num_meas, no_law ? "K_dev, xbar_dev, e_dev and actions_out_dev are required" : nullptr,
+          {lio->H_dev, lio->r_dev, lio->Q_dev, lio->P0_dev, lio->xhat0_dev, lio->status0_dev},
+          "H_dev, r_dev, Q_dev, P0_dev, xhat0_dev and status0_dev"))
+    return rc_;
   cs::ContextView v;
   if (int rc_ = cs::enter_filter_context(
           ctx, who, stream, lio->out_dtype,

@@ -442,12 +442,7 @@ __global__ __launch_bounds__(kBlock) void rollout_feedback_kernel(const DevConst
 
 template <int TASK, int MODE>
 hipError_t lqr_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const LqrArgs& l, hipStream_t stream) {
-  const dim3 grid(grid_for(s.n)), block(kBlock);
-  if (c.gyro)
-    hipLaunchKernelGGL((rollout_lqr_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, l);
-  else
-    hipLaunchKernelGGL((rollout_lqr_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, l);
-  return hipGetLastError();
+  CS_GYRO_LAUNCH(rollout_lqr_kernel, io, l);
 }
 
 template <int TASK, int MODE>

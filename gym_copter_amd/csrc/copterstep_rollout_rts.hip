@@ -187,12 +187,7 @@ __global__ __launch_bounds__(kBlock) void rollout_rts_kernel(const DevConst c, c
 template <int TASK, int MODE>
 hipError_t rts_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const cs_rollout_rts_io& r,
                  hipStream_t stream) {
-  const dim3 grid(grid_for(s.n)), block(kBlock);
-  if (c.gyro)
-    hipLaunchKernelGGL((rollout_rts_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, r);
-  else
-    hipLaunchKernelGGL((rollout_rts_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, r);
-  return hipGetLastError();
+  CS_GYRO_LAUNCH(rollout_rts_kernel, io, r);
 }
 
 hipError_t launch_rollout_rts(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,

@@ -12,6 +12,9 @@
 //               (the point, the status of the mean), ukf_moments_add -- the points are never stored
 //   prior       ukf_moments_finish: x-, P- = the weighted moments + Q
 //   update      M sequential scalar updates (ekf_update.h)
+// The start, the prior-mean store, the update, the tapes of a row and the closing stores are filter_step.h's, the
+// functions copterstep_rollout_ekf.hip calls: the update and the tapes are the EKF's by construction.  What is written
+// here is the UKF's own: the factor, the points, the moments, the point tapes and the LANDED shortcut.
 // P (78 rows, packed upper triangle), its factor U (78 rows), the moment sum S (78 rows, with U the stage of cov_tile.h's
 // 12 x 12 stores once the prior is formed: 156 >= 145 rows), the mean (12 rows) and the propagated point 0 (12 rows)
 // live in lane-private LDS columns (element j of a lane at [j * 64 + lane]): 258 rows x 512 B = 129 KiB, one wavefront
@@ -38,6 +41,7 @@
 #include "rts_solve.h"
 #include "ukf_points.h"
 #include "cov_tile.h"
+#include "filter_step.h"
 #include "dev_launch.h"
 
 namespace cs {
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(kBlock) void rollout_ukf_kernel(const DevConst c, c
   const uint32_t ii = ro.valid ? i : 0u;  // (padding lanes filter env 0 and store nothing)
   const int K = io.num_steps;
   const int M = u.num_meas;
-  const uint32_t f32 = u.out_dtype == CS_JAC_F32 ? 1u : 0u;
+  const FilterTapes t = filter_tapes(io, u);
   const UkfWeights wt{u.gamma, u.wm0, u.wc0, u.wi};
 
   Coef q = uniform_coef(c);
@@ -82,17 +86,7 @@ __global__ __launch_bounds__(kBlock) void rollout_ukf_kernel(const DevConst c, c
   double* const stage = lds + kRowU * kBlock;
 
   // ---- the caller's filter state: xhat_0, its status, the upper triangle of P0 ----
-#pragma unroll
-  for (int j = 0; j < 12; ++j) X[j * kBlock] = io.start_x_dev[(size_t)j * n + ii];
-  int fs = (int)io.start_status_dev[ii];
-  {
-    const double* p0 = u.P0_dev + (size_t)ii * 144;
-#pragma clang loop unroll(disable)
-    for (int j = 0; j < 12; ++j) {
-#pragma clang loop unroll(disable)
-      for (int a = 0; a <= j; ++a) P[(j * (j + 1) / 2 + a) * kBlock] = p0[a * 12 + j];
-    }
-  }
+  int fs = filter_load_start(X, P, io.start_x_dev, io.start_status_dev, u.P0_dev, n, ii);
   EkfStats st{0.0, 0.0, true};
   const bool tapes = u.points_dev != nullptr || u.points_pred_dev != nullptr || u.point_status_dev != nullptr;
 
@@ -159,64 +153,20 @@ __global__ __launch_bounds__(kBlock) void rollout_ukf_kernel(const DevConst c, c
       ukf_moments_finish(wt, Y0, sy, S, u.Q_dev, X, P, kBlock);
     }
 
-    // ---- the prior mean out (U and S are dead: their rows are the stage) ----
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) x[j] = X[j * kBlock];
-      wave_sync();
-      if (u.x_pred_dev != nullptr) store_x_row(stage, u.x_pred_dev, row, ro, x);
-    }
-
-    // ---- the update: M scalar measurements in order ----
-    st.nis = 0.0;
-    {
-      const double* zr = u.z_dev + (row + ii) * (size_t)M;
-#pragma clang loop unroll(disable)
-      for (int m = 0; m < M; ++m) ekf_scalar_update(X, P, kBlock, u.H_dev + m * 12, u.r_dev[m], zr[m], st);
-    }
-
-    // ---- the tapes of row k ----
-    {
-      double x[12];
-#pragma unroll
-      for (int j = 0; j < 12; ++j) x[j] = X[j * kBlock];
-      if (io.x_dev != nullptr) store_x_row(stage, io.x_dev, row, ro, x);
-    }
-    const bool last = k == K - 1;
-    if (u.P_tape_dev != nullptr || (last && u.P_dev != nullptr)) {
-      stage_triangle(stage + lane * kStageStride, P);
-      wave_sync();
-      if (u.P_tape_dev != nullptr) store_matrix(u.P_tape_dev, row, stage, ro, f32);
-      if (last && u.P_dev != nullptr) store_matrix(u.P_dev, 0, stage, ro, f32);
-    }
-    wave_sync();  // (the next step's factor and moment sum are written over the stage)
-    if (ro.valid) {
-      if (u.var_dev != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) store_out(u.var_dev, (row + i) * 12 + j, P[(j * (j + 1) / 2 + j) * kBlock], f32);
-      }
-      if (u.nis_dev != nullptr) store_out(u.nis_dev, row + i, st.nis, f32);
-      if (io.status_dev != nullptr) io.status_dev[row + i] = (uint8_t)fs;
-      if (u.spread_dev != nullptr) u.spread_dev[row + i] = (uint8_t)spread;
-    }
+    // ---- the prior mean out (U and S are dead: their rows are the stage), then copterstep_rollout_ekf.hip's update and
+    //      tapes (filter_step.h) ----
+    filter_store_prior(X, stage, t.x_pred, row, ro);
+    const double* zr = u.z_dev + (row + ii) * (size_t)M;
+    filter_update(X, P, u.H_dev, u.r_dev, M, st, [zr](int m) { return zr[m]; });
+    filter_store_row<true>(t, stage, X, P, row, ro, k == K - 1, fs, (uint32_t)spread, st.nis);
   }
-
-  if (ro.valid) {
-    if (u.loglik_dev != nullptr) store_out(u.loglik_dev, i, st.loglik, f32);
-    if (u.ok_dev != nullptr) u.ok_dev[i] = st.ok ? 1 : 0;
-  }
+  filter_store_end(t, ro, st);
 }
 
 template <int TASK, int MODE>
 hipError_t ukf_t(const DevConst& c, const DevState& s, const cs_rollout_io& io, const cs_rollout_ukf_io& u,
                  hipStream_t stream) {
-  const dim3 grid(grid_for(s.n)), block(kBlock);
-  if (c.gyro)
-    hipLaunchKernelGGL((rollout_ukf_kernel<TASK, MODE, true>), grid, block, 0, stream, c, s, io, u);
-  else
-    hipLaunchKernelGGL((rollout_ukf_kernel<TASK, MODE, false>), grid, block, 0, stream, c, s, io, u);
-  return hipGetLastError();
+  CS_GYRO_LAUNCH(rollout_ukf_kernel, io, u);
 }
 
 hipError_t launch_rollout_ukf(int task, int mode, const DevConst& c, const DevState& s, const cs_rollout_io& io,
@@ -239,15 +189,14 @@ extern "C" int cs_rollout_ukf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rol
                                     no_start ? "start_x_dev (the mean) and start_status_dev are required" : nullptr,
                                     extra ? "the reward, flag, cotangent and gradient pointers must be NULL" : nullptr))
     return rc_;
-  if (uio->num_meas < 1 || uio->num_meas > CS_EKF_MAX_MEAS)
-    return report_error(CS_ERR_ARG, "cs_rollout_ukf: num_meas must be 1 .. CS_EKF_MAX_MEAS");
-  if (!(uio->gamma > 0.0) || !std::isfinite(uio->gamma))
-    return report_error(CS_ERR_ARG, "cs_rollout_ukf: gamma must be finite and > 0");
-  if (!std::isfinite(uio->wm0) || !std::isfinite(uio->wc0) || !std::isfinite(uio->wi))
-    return report_error(CS_ERR_ARG, "cs_rollout_ukf: the weights wm0, wc0 and wi must be finite");
-  if (uio->H_dev == nullptr || uio->r_dev == nullptr || uio->Q_dev == nullptr || uio->P0_dev == nullptr ||
-      uio->z_dev == nullptr)
-    return report_error(CS_ERR_ARG, "cs_rollout_ukf: H_dev, r_dev, Q_dev, P0_dev and z_dev are required");
+  const char* weights = !(uio->gamma > 0.0) || !std::isfinite(uio->gamma) ? "gamma must be finite and > 0"
+                        : !std::isfinite(uio->wm0) || !std::isfinite(uio->wc0) || !std::isfinite(uio->wi)
+                            ? "the weights wm0, wc0 and wi must be finite"
+                            : nullptr;
+  if (int rc_ = cs::check_filter_model(who, uio->num_meas, weights,
+                                       {uio->H_dev, uio->r_dev, uio->Q_dev, uio->P0_dev, uio->z_dev},
+                                       "H_dev, r_dev, Q_dev, P0_dev and z_dev"))
+    return rc_;
   cs::ContextView v;
   if (int rc_ = cs::enter_filter_context(ctx, who, stream, uio->out_dtype,
                                          {io->start_x_dev, io->x_dev, uio->H_dev, uio->r_dev, uio->Q_dev, uio->P0_dev,

@@ -2,7 +2,8 @@
 // (copterstep_rollout_ekf.hip, copterstep_rollout_rts.hip), the typed store (theirs, copterstep_rollout_pf.hip's and
 // copterstep_rollout_lqr.hip's), the packed-triangle kit of the kernels that keep a 12 x 12 symmetric matrix per lane in
 // LDS columns (element j of a lane at [j * 64 + lane]), and the covariance prediction P- = A P A^T + Q of the filter and
-// its smoother; wave_sync() comes with it (wave_sync.h).  Device code of those translation units (included there,
+// its smoother; wave_sync() comes with it (wave_sync.h), and so does the launch of a <TASK, MODE, GYRO> kernel
+// (CS_GYRO_LAUNCH).  filter_step.h builds the filters' shared step on it.  Device code of those translation units (included there,
 // inside their floating-point-contraction pragma, after rollout_sweep.h); not a stand-alone header.  It is no dev_*.h:
 // those are the step kernels' sources, whose hash stamps the committed profiles.  DESIGN.md sections 13, 19 and 20.
 #pragma once
@@ -17,6 +18,18 @@ namespace {
 // different banks), over W's 144 rows and one row of padding that a kernel keeps behind them
 constexpr int kStageStride = 145;
 static_assert(kStageStride * kWave <= kStageStride * kBlock, "the stage fits W and its padding row");
+
+// The body of a CS_DISPATCH target (dev_launch.h) whose kernel is a template over <TASK, MODE, GYRO>: one lane per env,
+// the instantiation chosen by the configuration's rotor_gyro.  Host code; `c`, `s` and `stream` are the target's own.
+#define CS_GYRO_LAUNCH(KERNEL, ...)                                                               \
+  do {                                                                                            \
+    const dim3 grid(grid_for(s.n)), block(kBlock);                                                \
+    if (c.gyro)                                                                                   \
+      hipLaunchKernelGGL((KERNEL<TASK, MODE, true>), grid, block, 0, stream, c, s, __VA_ARGS__);  \
+    else                                                                                          \
+      hipLaunchKernelGGL((KERNEL<TASK, MODE, false>), grid, block, 0, stream, c, s, __VA_ARGS__); \
+    return hipGetLastError();                                                                     \
+  } while (0)
 
 __device__ __forceinline__ void store_out(void* dst, size_t at, double v, uint32_t f32) {
   if (f32)

@@ -41,13 +41,11 @@ def measure(x_tape, H, r, seed, missing=0.0):
     return z
 
 
-def ekf(env, actions, z, H, r, Q, x0, P0, status0=None, chunk=None):
-    """Run env.rollout_ekf over actions [K,N,A] and z [K,N,M] in chunks of `chunk` steps (None: one call), as a filter
-    whose measurements arrive `chunk` at a time: the mean, the covariance and the status after each chunk start the next.
-    Returns EkfResult with the tapes of all K steps concatenated (P_tape included), P the last posterior, loglik the sum
-    of the chunks' and ok their conjunction -- tensors of their own, not the env's buffers.  Every tape, P and ok are
-    bit-identical to the single call's: a chunk boundary rounds nothing (float64 throughout).  loglik equals the single
-    call's to rounding only: it is the sum of the chunks' sums.  The arguments are rollout_ekf's."""
+def _chunked(actions, z, chunk, taped, state, call, carry):
+    """The chunk loop of ekf(), ukf() and pf(): call(actions' chunk, z's chunk, k0, state) runs the chunk that starts at
+    step k0 from the carried `state` and returns its result (buffers of the env); its fields `taped` are cloned, and
+    carry(result) is the state that starts the next chunk.  Returns (the taped fields concatenated over the chunks, by
+    name; the state after the last chunk; loglik, the sum of the chunks'; ok, their conjunction)."""
     torch = _torch()
     K = int(actions.shape[0])
     chunk = K if chunk is None else int(chunk)
@@ -55,17 +53,35 @@ def ekf(env, actions, z, H, r, Q, x0, P0, status0=None, chunk=None):
         raise ValueError("chunk must be >= 1, got %r" % (chunk,))
     if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] != K:
         raise ValueError("z must be a tensor of shape (K, N, M) with K = %d steps" % K)
-    parts = []
-    x, P, status = x0, P0, status0
+    parts = {name: [] for name in taped}
     loglik, ok = None, None
     for k0 in range(0, K, chunk):
-        res = env.rollout_ekf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, x, P, status0=status, tape=True)
-        parts.append([t.clone() for t in (res.x, res.x_pred, res.var, res.nis, res.status, res.branch, res.P_tape)])
-        x, P, status = res.x[-1].T.contiguous(), res.P.clone(), res.status[-1].clone()
+        res = call(actions[k0:k0 + chunk], z[k0:k0 + chunk], k0, state)
+        for name in taped:
+            parts[name].append(getattr(res, name).clone())
+        state = carry(res)
         loglik = res.loglik.clone() if loglik is None else loglik + res.loglik
         ok = res.ok.clone() if ok is None else ok & res.ok
-    xs, xp, var, nis, st, br, pt = (torch.cat([p[j] for p in parts]) for j in range(7))
-    return EkfResult(xs, xp, P, var, nis, loglik, st, br, ok, pt)
+    return {name: torch.cat(parts[name]) for name in taped}, state, loglik, ok
+
+
+def _carry_gaussian(res):
+    """What a Kalman filter carries from chunk to chunk: the last mean as [12,N], the last covariance and the status."""
+    return res.x[-1].T.contiguous(), res.P.clone(), res.status[-1].clone()
+
+
+def ekf(env, actions, z, H, r, Q, x0, P0, status0=None, chunk=None):
+    """Run env.rollout_ekf over actions [K,N,A] and z [K,N,M] in chunks of `chunk` steps (None: one call), as a filter
+    whose measurements arrive `chunk` at a time: the mean, the covariance and the status after each chunk start the next.
+    Returns EkfResult with the tapes of all K steps concatenated (P_tape included), P the last posterior, loglik the sum
+    of the chunks' and ok their conjunction -- tensors of their own, not the env's buffers.  Every tape, P and ok are
+    bit-identical to the single call's: a chunk boundary rounds nothing (float64 throughout).  loglik equals the single
+    call's to rounding only: it is the sum of the chunks' sums.  The arguments are rollout_ekf's."""
+    cat, (_, P, _), loglik, ok = _chunked(
+        actions, z, chunk, ("x", "x_pred", "var", "nis", "status", "branch", "P_tape"), (x0, P0, status0),
+        lambda a, zc, k0, s: env.rollout_ekf(a, zc, H, r, Q, s[0], s[1], status0=s[2], tape=True), _carry_gaussian)
+    return EkfResult(cat["x"], cat["x_pred"], P, cat["var"], cat["nis"], loglik, cat["status"], cat["branch"], ok,
+                     cat["P_tape"])
 
 
 def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None):

@@ -48,9 +48,8 @@ def rollout_lqg(self, actions, gains, xbar, noise, H, r, Q, xhat0, P0, status0=N
     self._check_open()
     torch = _torch()
     dtype = self._out_dtype(dtype)
-    Hd, rd, Qd = self._filter_model("lqg", (H, r, Q), lambda: (
-        *self._measurement_model(H, r), self._process_noise(Q)))
-    M = int(Hd.shape[0])
+    model = self._kalman_model("lqg", H, r, Q)
+    M = model[3]
     io, K, keep = self._rollout_io(actions, state)
     n, ad, dev = self.num_envs, self.action_dim, self.device
     Kg = getattr(gains, "K", gains)
@@ -61,13 +60,6 @@ def rollout_lqg(self, actions, gains, xbar, noise, H, r, Q, xhat0, P0, status0=N
     Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
     fio = _lib.RolloutIO()               # (only its start_status_dev: _start_status' default and checks)
     self._start_status(fio, status0, keep)
-    lio = _lib.RolloutLqgIO()
-    lio.struct_size = C.sizeof(_lib.RolloutLqgIO)
-    lio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-    lio.num_meas = M
-    lio.K_dev, lio.xbar_dev, lio.e_dev = Kg.data_ptr(), xbar.data_ptr(), et.data_ptr()
-    lio.H_dev, lio.r_dev, lio.Q_dev = Hd.data_ptr(), rd.data_ptr(), Qd.data_ptr()
-    lio.P0_dev, lio.xhat0_dev, lio.status0_dev = Pt.data_ptr(), xt.data_ptr(), fio.start_status_dev
     tape = bool(tape)
     out = self._rollout_cache(("lqg", K, M, dtype, tape), lambda: LqgResult(
         Rollout(torch.empty((K, n, 12), dtype=torch.float64, device=dev),
@@ -77,26 +69,18 @@ def rollout_lqg(self, actions, gains, xbar, noise, H, r, Q, xhat0, P0, status0=N
                 torch.empty((K, n), dtype=torch.uint8, device=dev)),
         torch.empty((K, n, ad), dtype=torch.float32, device=dev),
         torch.empty((K, n, M), dtype=torch.float64, device=dev),
-        EkfResult(
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((n, 12, 12), dtype=dtype, device=dev), torch.empty((K, n, 12), dtype=dtype, device=dev),
-            torch.empty((K, n), dtype=dtype, device=dev), torch.empty(n, dtype=dtype, device=dev),
-            torch.empty((K, n), dtype=torch.uint8, device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev),
-            torch.empty(n, dtype=torch.bool, device=dev),
-            torch.empty((K, n, 12, 12), dtype=dtype, device=dev) if tape else None)))
+        EkfResult(*self._kalman_tensors(K, n, dtype, tape))))
     ro, f = out.rollout, out.filter
     io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in ro)
+    lio = _lib.RolloutLqgIO()
+    self._kalman_wire(lio, dtype, model, Pt, f)
+    lio.K_dev, lio.xbar_dev, lio.e_dev = Kg.data_ptr(), xbar.data_ptr(), et.data_ptr()
+    lio.xhat0_dev, lio.status0_dev = xt.data_ptr(), fio.start_status_dev
     lio.actions_out_dev, lio.z_dev = out.actions.data_ptr(), out.z.data_ptr()
-    lio.xhat_dev, lio.x_pred_dev, lio.P_dev, lio.var_dev = (f.x.data_ptr(), f.x_pred.data_ptr(), f.P.data_ptr(),
-                                                            f.var.data_ptr())
-    lio.nis_dev, lio.loglik_dev = f.nis.data_ptr(), f.loglik.data_ptr()
-    lio.fstatus_dev, lio.branch_dev, lio.ok_dev = f.status.data_ptr(), f.branch.data_ptr(), f.ok.data_ptr()
-    if tape:
-        lio.P_tape_dev = f.P_tape.data_ptr()
+    lio.xhat_dev, lio.fstatus_dev, lio.branch_dev = f.x.data_ptr(), f.status.data_ptr(), f.branch.data_ptr()
     with torch.cuda.device(self.device):
         _lib.check(self._lib.cs_rollout_lqg(self._ctx, C.byref(io), C.byref(lio), self._stream()))
-    self._keep = keep + [Hd, rd, Qd, Kg, xbar]
+    self._keep = keep + list(model[:3]) + [Kg, xbar]
     return out
 
 

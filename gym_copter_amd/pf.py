@@ -155,28 +155,16 @@ def pf(env, actions, z, H, r, Q, x0, P0, particles, nonce=0, ess_frac=0.5, statu
     of the chunks' and ok their conjunction -- tensors of their own, not the env's buffers.  Every tape, the carried
     state, P and ok are bit-identical to the single call's: a chunk boundary rounds nothing (float64 throughout).  loglik
     equals the single call's to rounding only: it is the sum of the chunks' sums.  The other arguments are rollout_pf's."""
-    import torch
-    K = int(actions.shape[0])
-    chunk = K if chunk is None else int(chunk)
-    if chunk < 1:
-        raise ValueError("chunk must be >= 1, got %r" % (chunk,))
-    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] != K:
-        raise ValueError("z must be a tensor of shape (K, N, M) with K = %d steps" % K)
+    from .ekf import _chunked      # (ekf.py imports vecenv.py, which imports this module)
     taped = ("x", "var", "ess", "resampled", "best", "status") + \
         (("part_tape", "pstatus_tape", "lw_tape", "wq_tape", "anc_tape") if tape else ())
-    parts = {name: [] for name in taped}
-    res, loglik, ok = None, None, None
-    for k0 in range(0, K, chunk):
+
+    def call(a, zc, k0, prev):      # the carried state is the chunk before's result itself (None: the Gaussian start)
         kw = dict(particles=particles, nonce=nonce, ess_frac=ess_frac, first_step=k0 + 1, tape=tape)
-        if res is None:
-            res = env.rollout_pf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, x0, P0, status0=status0, **kw)
-        else:
-            res = env.rollout_pf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, start=res, **kw)
-        for name in taped:
-            parts[name].append(getattr(res, name).clone())
-        loglik = res.loglik.clone() if loglik is None else loglik + res.loglik
-        ok = res.ok.clone() if ok is None else ok & res.ok
-    cat = {name: torch.cat(parts[name]) for name in taped}
+        if prev is None:
+            return env.rollout_pf(a, zc, H, r, Q, x0, P0, status0=status0, **kw)
+        return env.rollout_pf(a, zc, H, r, Q, start=prev, **kw)
+    cat, res, loglik, ok = _chunked(actions, z, chunk, taped, None, call, lambda res: res)
     return PfResult(cat["x"], cat["var"], cat["ess"], cat["resampled"], cat["best"], cat["status"], res.P.clone(), loglik,
                     ok, res.part.clone(), res.pstatus.clone(), res.lw.clone(), cat.get("part_tape"),
                     cat.get("pstatus_tape"), cat.get("lw_tape"), cat.get("wq_tape"), cat.get("anc_tape"))

@@ -77,9 +77,8 @@ def rollout_ukf(self, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta
     torch = _torch()
     dtype = self._out_dtype(dtype)
     gamma, wm0, wc0, wi = weights(alpha, beta, kappa)
-    Hd, rd, Qd = self._filter_model("ukf", (H, r, Q), lambda: (
-        *self._measurement_model(H, r), self._process_noise(Q)))
-    M = int(Hd.shape[0])
+    model = self._kalman_model("ukf", H, r, Q)
+    M = model[3]
     io, K, keep = self._rollout_io(actions, None)
     n, dev = self.num_envs, self.device
     zt = self._ekf_input(z, (K, n, M), "z", keep)
@@ -87,34 +86,22 @@ def rollout_ukf(self, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta
     Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
     self._start_status(io, status0, keep)
     io.start_x_dev = xt.data_ptr()
-    uio = _lib.RolloutUkfIO()
-    uio.struct_size = C.sizeof(_lib.RolloutUkfIO)
-    uio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-    uio.num_meas = M
-    uio.gamma, uio.wm0, uio.wc0, uio.wi = gamma, wm0, wc0, wi
-    uio.H_dev, uio.r_dev, uio.Q_dev = Hd.data_ptr(), rd.data_ptr(), Qd.data_ptr()
-    uio.P0_dev, uio.z_dev = Pt.data_ptr(), zt.data_ptr()
     tape, points = bool(tape), bool(points)
-    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+    pts = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev) if points else None      # noqa: E731
     out = self._rollout_cache(("ukf", K, dtype, tape, points), lambda: UkfResult(
-        e((K, n, 12), torch.float64), e((K, n, 12), torch.float64), e((n, 12, 12), dtype), e((K, n, 12), dtype),
-        e((K, n), dtype), e(n, dtype), e((K, n), torch.uint8), e((K, n), torch.uint8), e(n, torch.bool),
-        e((K, n, 12, 12), dtype) if tape else None,
-        e((K, n, NUM_POINTS, 12), torch.float64) if points else None,
-        e((K, n, NUM_POINTS, 12), torch.float64) if points else None,
-        e((K, n, NUM_POINTS), torch.uint8) if points else None))
+        *self._kalman_tensors(K, n, dtype, tape), pts((K, n, NUM_POINTS, 12), torch.float64),
+        pts((K, n, NUM_POINTS, 12), torch.float64), pts((K, n, NUM_POINTS), torch.uint8)))
+    uio = _lib.RolloutUkfIO()
+    self._kalman_wire(uio, dtype, model, Pt, out)
+    uio.gamma, uio.wm0, uio.wc0, uio.wi = gamma, wm0, wc0, wi
+    uio.z_dev, uio.spread_dev = zt.data_ptr(), out.spread.data_ptr()
     io.x_dev, io.status_dev = out.x.data_ptr(), out.status.data_ptr()
-    uio.x_pred_dev, uio.P_dev, uio.var_dev = out.x_pred.data_ptr(), out.P.data_ptr(), out.var.data_ptr()
-    uio.nis_dev, uio.loglik_dev = out.nis.data_ptr(), out.loglik.data_ptr()
-    uio.spread_dev, uio.ok_dev = out.spread.data_ptr(), out.ok.data_ptr()
-    if tape:
-        uio.P_tape_dev = out.P_tape.data_ptr()
     if points:
         uio.points_dev, uio.points_pred_dev = out.points.data_ptr(), out.points_pred.data_ptr()
         uio.point_status_dev = out.point_status.data_ptr()
     with torch.cuda.device(self.device):
         _lib.check(self._lib.cs_rollout_ukf(self._ctx, C.byref(io), C.byref(uio), self._stream()))
-    self._keep = keep + [Hd, rd, Qd]
+    self._keep = keep + list(model[:3])
     return out
 
 
@@ -126,26 +113,12 @@ def ukf(env, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta=0.0, kap
     buffers.  Every tape, P and ok are bit-identical to the single call's: a chunk boundary rounds nothing (float64
     throughout).  loglik equals the single call's to rounding only: it is the sum of the chunks' sums.  The other
     arguments are rollout_ukf's."""
-    torch = _torch()
-    K = int(actions.shape[0])
-    chunk = K if chunk is None else int(chunk)
-    if chunk < 1:
-        raise ValueError("chunk must be >= 1, got %r" % (chunk,))
-    if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[0] != K:
-        raise ValueError("z must be a tensor of shape (K, N, M) with K = %d steps" % K)
+    from .ekf import _carry_gaussian, _chunked      # (ekf.py imports vecenv.py, which imports this module)
     taped = ("x", "x_pred", "var", "nis", "status", "spread", "P_tape") + \
         (("points", "points_pred", "point_status") if points else ())
-    parts = {name: [] for name in taped}
-    x, P, status = x0, P0, status0
-    loglik, ok = None, None
-    for k0 in range(0, K, chunk):
-        res = env.rollout_ukf(actions[k0:k0 + chunk], z[k0:k0 + chunk], H, r, Q, x, P, status0=status, alpha=alpha,
-                              beta=beta, kappa=kappa, tape=True, points=points)
-        for name in taped:
-            parts[name].append(getattr(res, name).clone())
-        x, P, status = res.x[-1].T.contiguous(), res.P.clone(), res.status[-1].clone()
-        loglik = res.loglik.clone() if loglik is None else loglik + res.loglik
-        ok = res.ok.clone() if ok is None else ok & res.ok
-    cat = {name: torch.cat(parts[name]) for name in taped}
+    cat, (_, P, _), loglik, ok = _chunked(
+        actions, z, chunk, taped, (x0, P0, status0),
+        lambda a, zc, k0, s: env.rollout_ukf(a, zc, H, r, Q, s[0], s[1], status0=s[2], alpha=alpha, beta=beta,
+                                             kappa=kappa, tape=True, points=points), _carry_gaussian)
     return UkfResult(cat["x"], cat["x_pred"], P, cat["var"], cat["nis"], loglik, cat["status"], cat["spread"], ok,
                      cat["P_tape"], cat.get("points"), cat.get("points_pred"), cat.get("point_status"))

@@ -1523,6 +1523,36 @@ class CopterVecEnv(_VectorEnvBase):
         caches[slot] = (cache[0], cache[1], ident, given if tensors else None)
         return cache[1]
 
+    def _kalman_model(self, slot, H, r, Q):
+        """(Hd, rd, Qd, M): the checked model of rollout_ekf, rollout_lqg and rollout_ukf on the device, from the
+        entry point's cache `slot`."""
+        Hd, rd, Qd = self._filter_model(slot, (H, r, Q), lambda: (
+            *self._measurement_model(H, r), self._process_noise(Q)))
+        return Hd, rd, Qd, int(Hd.shape[0])
+
+    def _kalman_tensors(self, K, n, dtype, tape):
+        """The ten result tensors those three have in common, in EkfResult's order: x, x_pred, P, var, nis, loglik,
+        status, the step's byte (branch or spread), ok, P_tape (None without tape)."""
+        torch = _torch()
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)      # noqa: E731
+        return (e((K, n, 12), torch.float64), e((K, n, 12), torch.float64), e((n, 12, 12), dtype), e((K, n, 12), dtype),
+                e((K, n), dtype), e(n, dtype), e((K, n), torch.uint8), e((K, n), torch.uint8), e(n, torch.bool),
+                e((K, n, 12, 12), dtype) if tape else None)
+
+    @staticmethod
+    def _kalman_wire(fio, dtype, model, P0, res):
+        """The fields cs_rollout_ekf_io, cs_rollout_lqg_io and cs_rollout_ukf_io share by name, into the block `fio`:
+        its size, dtype, the model (_kalman_model's), P0 and the outputs of `res` (an EkfResult or a UkfResult)."""
+        Hd, rd, Qd, M = model
+        fio.struct_size = C.sizeof(type(fio))
+        fio.out_dtype = _lib.JAC_F64 if dtype == _torch().float64 else _lib.JAC_F32
+        fio.num_meas = M
+        fio.H_dev, fio.r_dev, fio.Q_dev, fio.P0_dev = Hd.data_ptr(), rd.data_ptr(), Qd.data_ptr(), P0.data_ptr()
+        fio.x_pred_dev, fio.P_dev, fio.var_dev = res.x_pred.data_ptr(), res.P.data_ptr(), res.var.data_ptr()
+        fio.nis_dev, fio.loglik_dev, fio.ok_dev = res.nis.data_ptr(), res.loglik.data_ptr(), res.ok.data_ptr()
+        if res.P_tape is not None:
+            fio.P_tape_dev = res.P_tape.data_ptr()
+
     @staticmethod
     def _host_array(m, name):
         """m, a tensor or an array of real numbers, as a finite float64 host array."""
@@ -1614,40 +1644,24 @@ class CopterVecEnv(_VectorEnvBase):
         self._check_open()
         torch = _torch()
         dtype = self._out_dtype(dtype)
-        Hd, rd, Qd = self._filter_model("ekf", (H, r, Q), lambda: (
-            *self._measurement_model(H, r), self._process_noise(Q)))
-        M = int(Hd.shape[0])
+        model = self._kalman_model("ekf", H, r, Q)
+        M = model[3]
         io, K, keep = self._rollout_io(actions, None)
-        n, dev = self.num_envs, self.device
+        n = self.num_envs
         zt = self._ekf_input(z, (K, n, M), "z", keep)
         xt = self._ekf_input(x0, (12, n), "x0", keep)
         Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
         self._start_status(io, status0, keep)
         io.start_x_dev = xt.data_ptr()
-        eio = _lib.RolloutEkfIO()
-        eio.struct_size = C.sizeof(_lib.RolloutEkfIO)
-        eio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-        eio.num_meas = M
-        eio.H_dev, eio.r_dev, eio.Q_dev = Hd.data_ptr(), rd.data_ptr(), Qd.data_ptr()
-        eio.P0_dev, eio.z_dev = Pt.data_ptr(), zt.data_ptr()
         tape = bool(tape)
-        out = self._rollout_cache(("ekf", K, dtype, tape), lambda: EkfResult(
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((n, 12, 12), dtype=dtype, device=dev), torch.empty((K, n, 12), dtype=dtype, device=dev),
-            torch.empty((K, n), dtype=dtype, device=dev), torch.empty(n, dtype=dtype, device=dev),
-            torch.empty((K, n), dtype=torch.uint8, device=dev), torch.empty((K, n), dtype=torch.uint8, device=dev),
-            torch.empty(n, dtype=torch.bool, device=dev),
-            torch.empty((K, n, 12, 12), dtype=dtype, device=dev) if tape else None))
+        out = self._rollout_cache(("ekf", K, dtype, tape), lambda: EkfResult(*self._kalman_tensors(K, n, dtype, tape)))
+        eio = _lib.RolloutEkfIO()
+        self._kalman_wire(eio, dtype, model, Pt, out)
+        eio.z_dev, eio.branch_dev = zt.data_ptr(), out.branch.data_ptr()
         io.x_dev, io.status_dev = out.x.data_ptr(), out.status.data_ptr()
-        eio.x_pred_dev, eio.P_dev, eio.var_dev = out.x_pred.data_ptr(), out.P.data_ptr(), out.var.data_ptr()
-        eio.nis_dev, eio.loglik_dev = out.nis.data_ptr(), out.loglik.data_ptr()
-        eio.branch_dev, eio.ok_dev = out.branch.data_ptr(), out.ok.data_ptr()
-        if tape:
-            eio.P_tape_dev = out.P_tape.data_ptr()
         with torch.cuda.device(self.device):
             _lib.check(self._lib.cs_rollout_ekf(self._ctx, C.byref(io), C.byref(eio), self._stream()))
-        self._keep = keep + [Hd, rd, Qd]
+        self._keep = keep + list(model[:3])
         return out
 
     # -- the bootstrap particle filter over the env step: its host side lives with its streaming
