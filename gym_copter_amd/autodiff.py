@@ -3,6 +3,7 @@ as a differentiable function of the actions (and of an explicit start's x, and o
 pending force), its backward CopterVecEnv.rollout_vjp (rollout_vjp_params); differentiable_mlp_rollout(env, params, K,
 hidden) is the closed-loop CopterVecEnv.rollout_mlp_states under an MLP policy, its backward rollout_mlp_vjp.  See
 DESIGN.md sections 10 to 12 and INTEGRATION.md."""
+from .rollout import _vjp
 from .vecenv import MlpRollout, Rollout, _torch
 
 _FN = None
@@ -38,8 +39,8 @@ def _function():
             actions, x, status, vehicle = ctx.saved_tensors
             tape = Rollout(x, None, None, None, status)
             if ctx.params:                                      # the parameter VJP: g_vehicle and g_force as well
-                ga, g0, gv, gf = ctx.env._vjp(actions, tape, gx, gr, ctx.state, torch.float64, params=True,
-                                              vehicle=vehicle, check_vehicle=False)
+                ga, g0, gv, gf = _vjp(ctx.env, actions, tape, gx, gr, ctx.state, torch.float64, params=True,
+                                      vehicle=vehicle, check_vehicle=False)
             else:
                 ga, g0 = ctx.env.rollout_vjp(actions, tape, gx=gx, gr=gr, state=ctx.state, dtype=torch.float64)
                 gv = gf = None

@@ -9,12 +9,123 @@ import collections
 
 import numpy as np
 
+from . import _lib, _wire
+from . import rollout as _rollout
+from ._wire import _torch
+from .rollout import Rollout
+
 IlqrResult = collections.namedtuple("IlqrResult", "actions cost alpha rollout mu")
+# CopterVecEnv.rollout_lqr's result: the time-varying gains K [K,N,A,12] and d [K,N,A], the model's predicted cost change
+# dV [N,2], the value model at the start S0 [N,12,12], s0 [12,N], and ok [N] bool (every Cholesky pivot positive)
+LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
 
 
-def _torch():
-    import torch
-    return torch
+# -- the iLQR backward pass and its line-search forward: CopterVecEnv's methods, bound in vecenv.py --
+def _weight(m, shape, name):
+    """A cost matrix on the host: float64, of `shape`, finite and symmetric."""
+    a = np.asarray(m.detach().cpu() if isinstance(m, _torch().Tensor) else m, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
+    if not np.isfinite(a).all():
+        raise ValueError("%s must be finite" % name)
+    if not (a == a.T).all():
+        raise ValueError("%s must be symmetric" % name)
+    return a
+
+
+def _lqr_weights(env, Q, R, Q_final, definite=True):
+    """Q [12,12], R [A,A], Q_final [12,12] or None, checked on the host (symmetric, finite; R's diagonal > 0, or
+    >= 0 with definite=False: MPPI inverts nothing) and kept on the device: the same values are uploaded once (the
+    iLQR and MPPI drivers pass them every iteration)."""
+    ad = env.action_dim
+    q = _weight(Q, (12, 12), "Q")
+    r = _weight(R, (ad, ad), "R")
+    d = r.diagonal()
+    if definite and not (d > 0).all():
+        raise ValueError("R must be positive definite: its diagonal must be > 0")
+    if not (d >= 0).all():
+        raise ValueError("R must be positive semidefinite: its diagonal must be >= 0")
+    qf = None if Q_final is None else _weight(Q_final, (12, 12), "Q_final")
+    return _wire.uploaded(env, "lqr_weights", lambda: (q, r, qf))
+
+
+def rollout_lqr(self, actions, rollout, Q, R, q=None, r=None, Q_final=None, mu=0.0, state=None, dtype=None):
+    """The iLQR backward pass over a rollout's tape, one kernel: the Riccati recursion of the quadratic model of a
+    cost J = sum_k [l_k(x_k) + m_k(a_k)] around the rollout, with the step Jacobians of step_jacobian (every branch
+    rule of DESIGN section 9) applied on the fly and never stored.  `rollout` is what rollout_states(actions, state)
+    returned for the same actions and start (as rollout_vjp takes it).  q [K,N,12] = grad l_k at rollout.x[k-1],
+    r [K,N,A] = grad m_k at actions[k-1] (None: zero); Q [12,12] symmetric PSD, R [A,A] symmetric PD and Q_final
+    (replaces Q at the last step) are the Hessians, shared by every env and step; mu >= 0 is the Levenberg term
+    added to Quu's diagonal before it is inverted.
+
+    Returns LqrGains(K [K,N,A,12], d [K,N,A], dV [N,2], S0 [N,12,12], s0 [12,N], ok [N] bool): the action
+    a_k + alpha d_k + K_k (x_{k-1} - xbar_{k-1}) (rollout_feedback_states) changes the model's cost by
+    alpha dV[:,0] + alpha^2 dV[:,1]; S0, s0 are the value model at the start; ok is False where a Cholesky pivot was
+    not positive (raise mu).  dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).
+    Asynchronous on the current stream; the tensors are buffers of this env, overwritten by its next call with the
+    same K and dtype.  No env state changes."""
+    self._check_open()
+    torch = _torch()
+    dtype = _wire.out_dtype(dtype)
+    mu = _wire.finite(float(mu), "mu", 0)
+    Qd, Rd, Qfd = _lqr_weights(self, Q, R, Q_final)
+    io, K, keep = _rollout._rollout_io(self, actions, state)
+    n, ad = self.num_envs, self.action_dim
+    _rollout._tape(self, io, rollout, K)
+    lio = _wire.block(_lib.RolloutLqrIO, out_dtype=_wire.dtype_code(dtype), mu=mu, Q_dev=Qd.data_ptr(),
+                      R_dev=Rd.data_ptr(), Q_final_dev=None if Qfd is None else Qfd.data_ptr())
+    if q is not None:
+        lio.q_dev = _wire.tensor(self, q, (K, n, 12), torch.float64, "q", keep, host=False, floating=True,
+                                 foreign=False).data_ptr()
+    if r is not None:
+        lio.r_dev = _wire.tensor(self, r, (K, n, ad), torch.float64, "r", keep, host=False, floating=True,
+                                 foreign=False).data_ptr()
+    out = _wire.rollout_cache(self, ("lqr", K, dtype), lambda: (
+        _wire.empty(self, (K, n, ad, 12), dtype), _wire.empty(self, (K, n, ad), dtype), _wire.empty(self, (n, 2), dtype),
+        _wire.empty(self, (n, 12, 12), dtype), _wire.empty(self, (12, n), dtype), _wire.empty(self, n, torch.bool)))
+    lio.K_dev, lio.d_dev, lio.dV_dev, lio.S0_dev, lio.s0_dev, lio.ok_dev = (t.data_ptr() for t in out)
+    _wire.launch(self, "cs_rollout_lqr", io, lio, keep=keep + [Qd, Rd, Qfd])
+    return LqrGains(*out)
+
+
+def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
+    """rollout_states under the feedback of rollout_lqr, the line search's forward pass: step k takes
+    a_k = float32(actions[k-1] + alpha d_k + K_k (x_{k-1} - rollout.x[k-2])), x_{k-1} the state of THIS rollout
+    before the step (step 1 has no deviation: both rollouts share the start).  The arithmetic is float64 and fixed:
+    one multiply and one add for alpha d, then per state slot in order a subtraction, a multiply and an add, one
+    rounding to float32.  `rollout` is the nominal rollout_states(actions, state) result, `gains` rollout_lqr's
+    (float64), alpha a float or [N] float64 (per env).  Returns (Rollout, actions_out [K,N,A] float32): the Rollout
+    is bit-identical to rollout_states(actions_out, state).  Asynchronous on the current stream; the tensors are
+    buffers of this env, overwritten by its next call with the same K (they are not rollout_states' buffers).  No
+    env state changes."""
+    self._check_open()
+    torch = _torch()
+    io, K, keep = _rollout._rollout_io(self, actions, state)
+    n, ad, dev = self.num_envs, self.action_dim, self.device
+    xbar = getattr(rollout, "x", None)
+    Kg, d = getattr(gains, "K", None), getattr(gains, "d", None)
+    _wire.check_tape(self, "rollout_states", (xbar, "rollout.x", (K, n, 12), torch.float64))
+    _wire.check_tape(self, "rollout_lqr", (Kg, "gains.K", (K, n, ad, 12), torch.float64),
+                     (d, "gains.d", (K, n, ad), torch.float64))
+    if isinstance(alpha, torch.Tensor):
+        if tuple(alpha.shape) not in ((), (n,)) or not alpha.dtype.is_floating_point:
+            raise ValueError("alpha must be a float or a floating-point tensor of shape (%d,)" % n)
+        if alpha.device != dev and alpha.dim() == 1:
+            raise ValueError("alpha must be on %s, got %s" % (dev, alpha.device))
+        al = alpha.detach().to(device=dev, dtype=torch.float64).expand(n).contiguous()
+    else:
+        a = np.asarray(alpha, dtype=np.float64)
+        if a.shape not in ((), (n,)):
+            raise ValueError("alpha must be a float or have shape (%d,), got %s" % (n, a.shape))
+        al = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (n,)))).to(dev)
+    keep.append(al)
+    ro, acts = _wire.rollout_cache(self, ("feedback", K), lambda: (
+        _rollout._rollout_tensors(self, K), _wire.empty(self, (K, n, ad), torch.float32)))
+    _rollout._wire_rollout(io, ro)
+    fio = _wire.block(_lib.RolloutFeedbackIO, xbar_dev=xbar.data_ptr(), K_dev=Kg.data_ptr(), d_dev=d.data_ptr(),
+                      alpha_dev=al.data_ptr(), actions_out_dev=acts.data_ptr())
+    _wire.launch(self, "cs_rollout_feedback_states", io, fio, keep=keep + [xbar, Kg, d])
+    return ro, acts
 
 
 def tracking_cost(x, a, x_ref, a_ref, Q, R, Q_final=None):
@@ -68,8 +179,6 @@ def ilqr(env, actions0, x_ref, Q, R, Q_final=None, a_ref=None, iters=10,
     acts = (actions0.detach() if isinstance(actions0, torch.Tensor) else torch.from_numpy(np.asarray(actions0)))
     acts = acts.to(device=dev, dtype=torch.float32).clone().contiguous()
     n = acts.shape[1]
-    from .vecenv import Rollout
-
     ro = env.rollout_states(acts, state=state)
     x, status = ro.x.clone(), ro.status.clone()      # (the env's buffers are overwritten by its next call)
     cost = tracking_cost(x, acts, xr, ar, Qd, Rd, Qfd)

@@ -7,21 +7,20 @@ lqg(), the small driver that designs the gains at a nominal rollout and flies th
 
 The controller never sees the true state: only the filter's estimate, which in turn is told every action."""
 import collections
-import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _wire
+from . import ekf as _ekf
+from . import rollout as _rollout
+from ._wire import _torch
+from .ekf import EkfResult
+from .ilqr import tracking_gradients
 
 # CopterVecEnv.rollout_lqg's result: rollout, the Rollout of the truth (x [K,N,12], reward, terminated, truncated,
 # status); actions [K,N,A] float32, what the law chose (unclipped); z [K,N,M] float64, the measurements (NaN = none);
 # filter, an EkfResult of the filter's own tapes (its status is that of its estimate, not the truth's)
 LqgResult = collections.namedtuple("LqgResult", "rollout actions z filter")
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def rollout_lqg(self, actions, gains, xbar, noise, H, r, Q, xhat0, P0, status0=None, state=None, tape=False, dtype=None):
@@ -44,43 +43,32 @@ def rollout_lqg(self, actions, gains, xbar, noise, H, r, Q, xhat0, P0, status0=N
     state); actions_out [K,N,A] float32 (unclipped; the step clips); z [K,N,M]; and an EkfResult bit-identical to
     rollout_ekf(actions_out, z, ...).  Not available under action_arith="float32".  Asynchronous on the current stream;
     the tensors are buffers of this env, overwritten by its next call with the same K, M, dtype and tape."""
-    from .vecenv import EkfResult, Rollout
     self._check_open()
     torch = _torch()
-    dtype = self._out_dtype(dtype)
-    model = self._kalman_model("lqg", H, r, Q)
+    dtype = _wire.out_dtype(dtype)
+    model = _ekf._kalman_model(self, "lqg", H, r, Q)
     M = model[3]
-    io, K, keep = self._rollout_io(actions, state)
-    n, ad, dev = self.num_envs, self.action_dim, self.device
+    io, K, keep = _rollout._rollout_io(self, actions, state)
+    n, ad = self.num_envs, self.action_dim
     Kg = getattr(gains, "K", gains)
-    self._check_tape("rollout_lqr", (Kg, "gains", (K, n, ad, 12), torch.float64))
-    self._check_tape("rollout_states", (xbar, "xbar", (K, n, 12), torch.float64))
-    et = self._ekf_input(noise, (K, n, M), "noise", keep)
-    xt = self._ekf_input(xhat0, (12, n), "xhat0", keep)
-    Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
-    fio = _lib.RolloutIO()               # (only its start_status_dev: _start_status' default and checks)
-    self._start_status(fio, status0, keep)
+    _wire.check_tape(self, "rollout_lqr", (Kg, "gains", (K, n, ad, 12), torch.float64))
+    _wire.check_tape(self, "rollout_states", (xbar, "xbar", (K, n, 12), torch.float64))
+    et = _ekf._input(self, noise, (K, n, M), "noise", keep)
+    xt = _ekf._input(self, xhat0, (12, n), "xhat0", keep)
+    Pt = _ekf._input(self, P0, (n, 12, 12), "P0", keep)
+    status0_dev = _ekf._start_status(self, status0, keep)
     tape = bool(tape)
-    out = self._rollout_cache(("lqg", K, M, dtype, tape), lambda: LqgResult(
-        Rollout(torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-                torch.empty((K, n), dtype=torch.float64, device=dev),
-                torch.empty((K, n), dtype=torch.bool, device=dev),
-                torch.empty((K, n), dtype=torch.bool, device=dev),
-                torch.empty((K, n), dtype=torch.uint8, device=dev)),
-        torch.empty((K, n, ad), dtype=torch.float32, device=dev),
-        torch.empty((K, n, M), dtype=torch.float64, device=dev),
-        EkfResult(*self._kalman_tensors(K, n, dtype, tape))))
+    out = _wire.rollout_cache(self, ("lqg", K, M, dtype, tape), lambda: LqgResult(
+        _rollout._rollout_tensors(self, K), _wire.empty(self, (K, n, ad), torch.float32),
+        _wire.empty(self, (K, n, M), torch.float64), EkfResult(*_ekf._kalman_tensors(self, K, n, dtype, tape))))
     ro, f = out.rollout, out.filter
-    io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in ro)
-    lio = _lib.RolloutLqgIO()
-    self._kalman_wire(lio, dtype, model, Pt, f)
+    _rollout._wire_rollout(io, ro)
+    lio = _ekf._kalman_wire(_lib.RolloutLqgIO, dtype, model, Pt, f)
     lio.K_dev, lio.xbar_dev, lio.e_dev = Kg.data_ptr(), xbar.data_ptr(), et.data_ptr()
-    lio.xhat0_dev, lio.status0_dev = xt.data_ptr(), fio.start_status_dev
+    lio.xhat0_dev, lio.status0_dev = xt.data_ptr(), status0_dev
     lio.actions_out_dev, lio.z_dev = out.actions.data_ptr(), out.z.data_ptr()
     lio.xhat_dev, lio.fstatus_dev, lio.branch_dev = f.x.data_ptr(), f.status.data_ptr(), f.branch.data_ptr()
-    with torch.cuda.device(self.device):
-        _lib.check(self._lib.cs_rollout_lqg(self._ctx, C.byref(io), C.byref(lio), self._stream()))
-    self._keep = keep + list(model[:3]) + [Kg, xbar]
+    _wire.launch(self, "cs_rollout_lqg", io, lio, keep=keep + list(model[:3]) + [Kg, xbar])
     return out
 
 
@@ -116,7 +104,6 @@ def lqg(env, actions, x_ref, Qc, Rc, H, r, Qn, xhat0, P0, seed, missing=0.0, sta
     measurement_noise(K, N, r, seed, missing); and rollout_lqg with those gains, H, r and the filter's process noise Qn
     from the estimate (xhat0, P0).  x_ref and a_ref broadcast against [K,N,12] and [K,N,A] (a_ref=None: zero).  Returns
     rollout_lqg's LqgResult (buffers of the env)."""
-    from .ilqr import tracking_gradients
     torch = _torch()
     dev = env.device
     f64 = dict(dtype=torch.float64, device=dev)

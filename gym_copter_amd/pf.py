@@ -7,16 +7,13 @@ for a filter whose measurements arrive a chunk of steps at a time.
 The particles, their statuses and their log-weights are carried from call to call on the device; nothing is read by the
 host.  Synthetic measurements to try it on: gym_copter_amd.measure."""
 import collections
-import ctypes as C
 
 import numpy as np
 
-from . import _lib
-
-
-def _torch():
-    import torch
-    return torch
+from . import _lib, _wire
+from . import ekf as _ekf
+from . import rollout as _rollout
+from ._wire import _torch
 
 
 # CopterVecEnv.rollout_pf's result (DESIGN section 21): the weighted means x [K,N,12] and variances var [K,N,12] before
@@ -68,33 +65,24 @@ def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce
     `start` that is such a buffer is read before it is overwritten)."""
     self._check_open()
     torch = _torch()
-    dtype = self._out_dtype(dtype)
-    Hd, rd, Lqd = self._filter_model("pf", (H, r, Q), lambda: (
-        *self._measurement_model(H, r), _noise_factor(self._host_array(Q, "Q"))))
+    dtype = _wire.out_dtype(dtype)
+    Hd, rd, Lqd = _wire.uploaded(self, "pf", lambda: (
+        *_ekf._measurement_model(H, r), _noise_factor(_ekf._host_array(Q, "Q"))), given=(H, r, Q))
     M = int(Hd.shape[0])
-    P = particles
-    if not isinstance(P, (int, np.integer)) or isinstance(P, bool) or P < _lib.PF_MIN_PARTICLES or \
-            P > _lib.PF_MAX_PARTICLES or P & (P - 1):
-        raise ValueError("particles must be a power of two in %d .. %d, got %r"
-                         % (_lib.PF_MIN_PARTICLES, _lib.PF_MAX_PARTICLES, particles))
-    P = int(P)
-    if not isinstance(nonce, (int, np.integer)) or isinstance(nonce, bool) or not 0 <= int(nonce) < 1 << 32:
-        raise ValueError("nonce must be an int in [0, 2**32), got %r" % (nonce,))
-    nonce = int(nonce)
-    if not isinstance(first_step, (int, np.integer)) or isinstance(first_step, bool) or first_step < 1:
-        raise ValueError("first_step must be an int >= 1, got %r" % (first_step,))
+    P = _wire.int_in(particles, "particles", _lib.PF_MIN_PARTICLES, _lib.PF_MAX_PARTICLES + 1,
+                     "a power of two in %d .. %d" % (_lib.PF_MIN_PARTICLES, _lib.PF_MAX_PARTICLES),
+                     ok=lambda p: not p & (p - 1))
+    nonce = _wire.int_in(nonce, "nonce", 0, _wire.U32, _wire.IN_U32)
+    first_step = _wire.int_in(first_step, "first_step", 1, None, "an int >= 1")
     if not 0.0 <= float(ess_frac) <= 1.0:
         raise ValueError("ess_frac must be in [0, 1], got %r" % (ess_frac,))
-    io, K, keep = self._rollout_io(actions, None)
-    if int(first_step) + K - 1 >= 1 << 32:
+    io, K, keep = _rollout._rollout_io(self, actions, None)
+    if first_step + K - 1 >= _wire.U32:
         raise ValueError("first_step + K - 1 must be below 2**32")
-    n, dev = self.num_envs, self.device
-    zt = self._ekf_input(z, (K, n, M), "z", keep)
-    pio = _lib.RolloutPfIO()
-    pio.struct_size = C.sizeof(_lib.RolloutPfIO)
-    pio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-    pio.num_meas, pio.num_particles, pio.nonce, pio.first_step = M, P, nonce, int(first_step)
-    pio.ess_frac = float(ess_frac)
+    n = self.num_envs
+    zt = _ekf._input(self, z, (K, n, M), "z", keep)
+    pio = _wire.block(_lib.RolloutPfIO, out_dtype=_wire.dtype_code(dtype), num_meas=M, num_particles=P, nonce=nonce,
+                      first_step=first_step, ess_frac=float(ess_frac))
     if (x0 is None) == (start is None):
         raise ValueError("give exactly one start: x0 (with P0, status0) or start (a previous PfResult)")
     if start is not None:
@@ -104,17 +92,17 @@ def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce
             start = (start.part, start.pstatus, start.lw)
         if not isinstance(start, (tuple, list)) or len(start) != 3:
             raise ValueError("start must be a PfResult or its (part, pstatus, lw)")
-        self._check_tape("rollout_pf", (start[0], "start part", (n, P, 12), torch.float64),
+        _wire.check_tape(self, "rollout_pf", (start[0], "start part", (n, P, 12), torch.float64),
                          (start[1], "start pstatus", (n, P), torch.uint8),
                          (start[2], "start lw", (n, P), torch.float64))
         keep.extend(start)
         pio.part_in_dev, pio.pstatus_in_dev, pio.lw_in_dev = (t.data_ptr() for t in start)
     else:
-        xt = self._ekf_input(x0, (12, n), "x0", keep)
+        xt = _ekf._input(self, x0, (12, n), "x0", keep)
         io.start_x_dev = xt.data_ptr()
-        self._start_status(io, status0, keep)
+        io.start_status_dev = _ekf._start_status(self, status0, keep)
         if P0 is not None:
-            Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
+            Pt = _ekf._input(self, P0, (n, 12, 12), "P0", keep)
             try:
                 L0 = torch.linalg.cholesky(Pt).contiguous()
             except RuntimeError as e:          # torch.linalg.LinAlgError
@@ -122,8 +110,8 @@ def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce
             keep.append(L0)
             pio.L0_dev = L0.data_ptr()
     tape = bool(tape)
-    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
-    out = self._rollout_cache(("pf", K, P, dtype, tape), lambda: PfResult(
+    e = lambda shape, dt: _wire.empty(self, shape, dt)      # noqa: E731
+    out = _wire.rollout_cache(self, ("pf", K, P, dtype, tape), lambda: PfResult(
         e((K, n, 12), torch.float64), e((K, n, 12), dtype), e((K, n), dtype), e((K, n), torch.bool),
         e((K, n), torch.int32), e((K, n), torch.uint8), e((n, 12, 12), dtype), e(n, dtype), e(n, torch.bool),
         e((n, P, 12), torch.float64), e((n, P), torch.uint8), e((n, P), torch.float64),
@@ -141,9 +129,7 @@ def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce
         pio.part_tape_dev, pio.pstatus_tape_dev = out.part_tape.data_ptr(), out.pstatus_tape.data_ptr()
         pio.lw_tape_dev, pio.wq_tape_dev = out.lw_tape.data_ptr(), out.wq_tape.data_ptr()
         pio.anc_tape_dev = out.anc_tape.data_ptr()
-    with torch.cuda.device(self.device):
-        _lib.check(self._lib.cs_rollout_pf(self._ctx, C.byref(io), C.byref(pio), self._stream()))
-    self._keep = keep + [Hd, rd, Lqd]
+    _wire.launch(self, "cs_rollout_pf", io, pio, keep=keep + [Hd, rd, Lqd])
     return out
 
 
@@ -155,7 +141,6 @@ def pf(env, actions, z, H, r, Q, x0, P0, particles, nonce=0, ess_frac=0.5, statu
     of the chunks' and ok their conjunction -- tensors of their own, not the env's buffers.  Every tape, the carried
     state, P and ok are bit-identical to the single call's: a chunk boundary rounds nothing (float64 throughout).  loglik
     equals the single call's to rounding only: it is the sum of the chunks' sums.  The other arguments are rollout_pf's."""
-    from .ekf import _chunked      # (ekf.py imports vecenv.py, which imports this module)
     taped = ("x", "var", "ess", "resampled", "best", "status") + \
         (("part_tape", "pstatus_tape", "lw_tape", "wq_tape", "anc_tape") if tape else ())
 
@@ -164,7 +149,7 @@ def pf(env, actions, z, H, r, Q, x0, P0, particles, nonce=0, ess_frac=0.5, statu
         if prev is None:
             return env.rollout_pf(a, zc, H, r, Q, x0, P0, status0=status0, **kw)
         return env.rollout_pf(a, zc, H, r, Q, start=prev, **kw)
-    cat, res, loglik, ok = _chunked(actions, z, chunk, taped, None, call, lambda res: res)
+    cat, res, loglik, ok = _ekf._chunked(actions, z, chunk, taped, None, call, lambda res: res)
     return PfResult(cat["x"], cat["var"], cat["ess"], cat["resampled"], cat["best"], cat["status"], res.P.clone(), loglik,
                     ok, res.part.clone(), res.pstatus.clone(), res.lw.clone(), cat.get("part_tape"),
                     cat.get("pstatus_tape"), cat.get("lw_tape"), cat.get("wq_tape"), cat.get("anc_tape"))

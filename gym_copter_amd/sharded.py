@@ -195,80 +195,9 @@ class ShardedCopterVecEnv:
         raise ValueError("actions must have %d (local) or %d (global) envs in dimension 1, got %d"
                          % (self.n_local, self.total_envs, actions.shape[1]))
 
-    def rollout_vjp(self, actions, rollout, gx=None, gr=None, state=None, dtype=None):
-        """CopterVecEnv.rollout_vjp of this rank's envs: shard-local (rollout, gx, gr: the local envs')."""
-        return self.local.rollout_vjp(self._local_rollout_actions(actions), rollout, gx=gx, gr=gr, state=state,
-                                      dtype=dtype)
-
-    def rollout_states(self, actions, state=None, vehicle=None):
-        """CopterVecEnv.rollout_states of this rank's envs: shard-local, no gather (actions: [K, n_local, A] or the
-        global [K, N, A]; an explicit `state` and a `vehicle` override cover the local envs)."""
-        return self.local.rollout_states(self._local_rollout_actions(actions), state=state, vehicle=vehicle)
-
-    def rollout_vjp_params(self, actions, rollout, gx=None, gr=None, state=None, vehicle=None, dtype=None):
-        """CopterVecEnv.rollout_vjp_params of this rank's envs: shard-local (rollout, gx, gr, vehicle: the local envs');
-        g_vehicle is per local env -- a vehicle shared by every rank sums it over envs and ranks."""
-        return self.local.rollout_vjp_params(self._local_rollout_actions(actions), rollout, gx=gx, gr=gr, state=state,
-                                             vehicle=vehicle, dtype=dtype)
-
-    def rollout_lqr(self, actions, rollout, Q, R, q=None, r=None, Q_final=None, mu=0.0, state=None, dtype=None):
-        """CopterVecEnv.rollout_lqr of this rank's envs: shard-local (rollout, q, r: the local envs')."""
-        return self.local.rollout_lqr(self._local_rollout_actions(actions), rollout, Q, R, q=q, r=r, Q_final=Q_final,
-                                      mu=mu, state=state, dtype=dtype)
-
-    def rollout_ekf(self, actions, z, H, r, Q, x0, P0, status0=None, tape=False, dtype=None):
-        """CopterVecEnv.rollout_ekf of this rank's envs: shard-local (z, x0, P0, status0: the local envs')."""
-        return self.local.rollout_ekf(self._local_rollout_actions(actions), z, H, r, Q, x0, P0, status0=status0,
-                                      tape=tape, dtype=dtype)
-
-    def rollout_lqg(self, actions, gains, xbar, noise, H, r, Q, xhat0, P0, status0=None, state=None, tape=False,
-                    dtype=None):
-        """CopterVecEnv.rollout_lqg of this rank's envs: shard-local (gains, xbar, noise, xhat0, P0, status0, state: the
-        local envs')."""
-        return self.local.rollout_lqg(self._local_rollout_actions(actions), gains, xbar, noise, H, r, Q, xhat0, P0,
-                                      status0=status0, state=state, tape=tape, dtype=dtype)
-
-    def rollout_ukf(self, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta=0.0, kappa=1.0, tape=False,
-                    points=False, dtype=None):
-        """CopterVecEnv.rollout_ukf of this rank's envs: shard-local (z, x0, P0, status0: the local envs')."""
-        return self.local.rollout_ukf(self._local_rollout_actions(actions), z, H, r, Q, x0, P0, status0=status0,
-                                      alpha=alpha, beta=beta, kappa=kappa, tape=tape, points=points, dtype=dtype)
-
-    def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):
-        """CopterVecEnv.rollout_rts of this rank's envs: shard-local (filt, x0, P0, status0, end: the local envs')."""
-        return self.local.rollout_rts(self._local_rollout_actions(actions), filt, Q, x0, P0, status0=status0, end=end,
-                                      tape=tape, dtype=dtype)
-
-    def rollout_pf(self, actions, z, H, r, Q, x0=None, P0=None, particles=256, nonce=0, ess_frac=0.5, status0=None,
-                   start=None, first_step=1, tape=False, dtype=None):
-        """CopterVecEnv.rollout_pf of this rank's envs: shard-local (z, x0, P0, status0, start: the local envs').  The
-        noise is keyed by the global env id, so a sharded batch draws what the unsharded one draws."""
-        return self.local.rollout_pf(self._local_rollout_actions(actions), z, H, r, Q, x0=x0, P0=P0,
-                                     particles=particles, nonce=nonce, ess_frac=ess_frac, status0=status0, start=start,
-                                     first_step=first_step, tape=tape, dtype=dtype)
-
-    def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
-                           stream=0, state=None, knots=None):
-        """CopterVecEnv.rollout_mppi_costs of this rank's envs: shard-local (x_ref, state: the local envs').  The noise
-        is keyed by the global env id, so a sharded batch draws what the unsharded one draws."""
-        return self.local.rollout_mppi_costs(self._local_rollout_actions(actions), sigma, samples, x_ref, Q, R,
-                                             Q_final=Q_final, a_ref=a_ref, reward_weight=reward_weight, stream=stream,
-                                             state=state, knots=knots)
-
-    def rollout_mppi_update(self, actions, costs, sigma, lam, stream=0, knots=None):
-        """CopterVecEnv.rollout_mppi_update of this rank's envs: shard-local (costs, a per-env lam: the local envs')."""
-        return self.local.rollout_mppi_update(self._local_rollout_actions(actions), costs, sigma, lam, stream=stream,
-                                              knots=knots)
-
     def rollout_mppi_temperature(self, costs, ess_target, lam_min=1e-6, lam_max=1e6):
         """CopterVecEnv.rollout_mppi_temperature of this rank's envs: shard-local (costs: the local envs')."""
         return self.local.rollout_mppi_temperature(costs, ess_target, lam_min=lam_min, lam_max=lam_max)
-
-    def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
-        """CopterVecEnv.rollout_feedback_states of this rank's envs: shard-local (rollout, gains, alpha: the local
-        envs')."""
-        return self.local.rollout_feedback_states(self._local_rollout_actions(actions), rollout, gains, alpha,
-                                                  state=state)
 
     def rollout_mlp_states(self, params, num_steps, hidden, offsets=None, state=None):
         """CopterVecEnv.rollout_mlp_states of this rank's envs: shard-local, no gather (params: the policy every rank
@@ -287,6 +216,29 @@ class ShardedCopterVecEnv:
 
     def close(self):
         self.local.close()
+
+
+# The shard-local rollouts whose first argument is the action tape [K, n_local, A] or the global [K, N, A]: every other
+# argument (a rollout, cotangents, a start, a filter's inputs ...) covers the local envs and is passed through as given, so
+# a keyword added to a CopterVecEnv method needs nothing here.  No gather.  (The noise of rollout_pf and
+# rollout_mppi_costs is keyed by the global env id: a sharded batch draws what the unsharded one draws.  g_vehicle of
+# rollout_vjp_params is per local env: a vehicle shared by every rank sums it over envs and ranks.)
+_LOCAL_ROLLOUTS = ("rollout_states", "rollout_vjp", "rollout_vjp_params", "rollout_lqr", "rollout_feedback_states",
+                   "rollout_mppi_costs", "rollout_mppi_update", "rollout_ekf", "rollout_rts", "rollout_pf", "rollout_lqg",
+                   "rollout_ukf")
+
+
+def _local_rollout(name):
+    def method(self, actions, *args, **kwargs):
+        return getattr(self.local, name)(self._local_rollout_actions(actions), *args, **kwargs)
+    method.__name__ = name
+    method.__qualname__ = "ShardedCopterVecEnv." + name
+    method.__doc__ = "CopterVecEnv.%s of this rank's envs: shard-local (every argument but `actions`: the local envs')." % name
+    return method
+
+
+for _name in _LOCAL_ROLLOUTS:
+    setattr(ShardedCopterVecEnv, _name, _local_rollout(_name))
 
 
 class HalfBatchPipeline:

@@ -8,10 +8,12 @@ transform, and ukf(), the streaming driver whose measurements arrive a chunk of 
 It stands between rollout_ekf (one Jacobian, at the branch the mean is on) and rollout_pf (64 to 1 024 sampled
 particles): 25 deterministic points per env, no Jacobian, and a prior that sees every branch the points land on."""
 import collections
-import ctypes as C
 import math
 
-from . import _lib
+from . import _lib, _wire
+from . import ekf as _ekf
+from . import rollout as _rollout
+from ._wire import _torch
 
 # CopterVecEnv.rollout_ukf's result: the filtered means x [K,N,12] and the priors x_pred [K,N,12], the last posterior
 # P [N,12,12], the posteriors' diagonals var [K,N,12], nis [K,N], loglik [N], the status [K,N] of the filter's own mean
@@ -22,11 +24,6 @@ UkfResult = collections.namedtuple(
     "UkfResult", "x x_pred P var nis loglik status spread ok P_tape points points_pred point_status")
 
 NUM_POINTS = 25     # 2 * 12 + 1
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def weights(alpha=1.0, beta=0.0, kappa=1.0):
@@ -75,33 +72,30 @@ def rollout_ukf(self, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta
     tensors are buffers of this env, overwritten by its next call with the same K, dtype, tape and points."""
     self._check_open()
     torch = _torch()
-    dtype = self._out_dtype(dtype)
+    dtype = _wire.out_dtype(dtype)
     gamma, wm0, wc0, wi = weights(alpha, beta, kappa)
-    model = self._kalman_model("ukf", H, r, Q)
+    model = _ekf._kalman_model(self, "ukf", H, r, Q)
     M = model[3]
-    io, K, keep = self._rollout_io(actions, None)
-    n, dev = self.num_envs, self.device
-    zt = self._ekf_input(z, (K, n, M), "z", keep)
-    xt = self._ekf_input(x0, (12, n), "x0", keep)
-    Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
-    self._start_status(io, status0, keep)
+    io, K, keep = _rollout._rollout_io(self, actions, None)
+    n = self.num_envs
+    zt = _ekf._input(self, z, (K, n, M), "z", keep)
+    xt = _ekf._input(self, x0, (12, n), "x0", keep)
+    Pt = _ekf._input(self, P0, (n, 12, 12), "P0", keep)
+    io.start_status_dev = _ekf._start_status(self, status0, keep)
     io.start_x_dev = xt.data_ptr()
     tape, points = bool(tape), bool(points)
-    pts = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev) if points else None      # noqa: E731
-    out = self._rollout_cache(("ukf", K, dtype, tape, points), lambda: UkfResult(
-        *self._kalman_tensors(K, n, dtype, tape), pts((K, n, NUM_POINTS, 12), torch.float64),
+    pts = lambda shape, dt: _wire.empty(self, shape, dt) if points else None      # noqa: E731
+    out = _wire.rollout_cache(self, ("ukf", K, dtype, tape, points), lambda: UkfResult(
+        *_ekf._kalman_tensors(self, K, n, dtype, tape), pts((K, n, NUM_POINTS, 12), torch.float64),
         pts((K, n, NUM_POINTS, 12), torch.float64), pts((K, n, NUM_POINTS), torch.uint8)))
-    uio = _lib.RolloutUkfIO()
-    self._kalman_wire(uio, dtype, model, Pt, out)
+    uio = _ekf._kalman_wire(_lib.RolloutUkfIO, dtype, model, Pt, out)
     uio.gamma, uio.wm0, uio.wc0, uio.wi = gamma, wm0, wc0, wi
     uio.z_dev, uio.spread_dev = zt.data_ptr(), out.spread.data_ptr()
     io.x_dev, io.status_dev = out.x.data_ptr(), out.status.data_ptr()
     if points:
         uio.points_dev, uio.points_pred_dev = out.points.data_ptr(), out.points_pred.data_ptr()
         uio.point_status_dev = out.point_status.data_ptr()
-    with torch.cuda.device(self.device):
-        _lib.check(self._lib.cs_rollout_ukf(self._ctx, C.byref(io), C.byref(uio), self._stream()))
-    self._keep = keep + list(model[:3])
+    _wire.launch(self, "cs_rollout_ukf", io, uio, keep=keep + list(model[:3]))
     return out
 
 
@@ -113,12 +107,11 @@ def ukf(env, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta=0.0, kap
     buffers.  Every tape, P and ok are bit-identical to the single call's: a chunk boundary rounds nothing (float64
     throughout).  loglik equals the single call's to rounding only: it is the sum of the chunks' sums.  The other
     arguments are rollout_ukf's."""
-    from .ekf import _carry_gaussian, _chunked      # (ekf.py imports vecenv.py, which imports this module)
     taped = ("x", "x_pred", "var", "nis", "status", "spread", "P_tape") + \
         (("points", "points_pred", "point_status") if points else ())
-    cat, (_, P, _), loglik, ok = _chunked(
+    cat, (_, P, _), loglik, ok = _ekf._chunked(
         actions, z, chunk, taped, (x0, P0, status0),
         lambda a, zc, k0, s: env.rollout_ukf(a, zc, H, r, Q, s[0], s[1], status0=s[2], alpha=alpha, beta=beta,
-                                             kappa=kappa, tape=True, points=points), _carry_gaussian)
+                                             kappa=kappa, tape=True, points=points), _ekf._carry_gaussian)
     return UkfResult(cat["x"], cat["x_pred"], P, cat["var"], cat["nis"], loglik, cat["status"], cat["spread"], ok,
                      cat["P_tape"], cat.get("points"), cat.get("points_pred"), cat.get("point_status"))

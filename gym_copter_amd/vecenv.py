@@ -18,7 +18,6 @@ PyTorch is used only for device memory and streams.  There is no CPU implementat
 this package: construction fails if libcopterstep.so or a HIP device is missing.
 """
 import atexit
-import collections
 import ctypes as C
 import os
 import weakref
@@ -26,10 +25,28 @@ import weakref
 import numpy as np
 
 from . import _lib
-from . import mlp as _mlp
+from . import rollout as _rollouts
+from . import mlp_rollout as _mlp_rollout
+from . import ilqr as _ilqr
+from . import mppi as _mppi
+from . import es as _es
+from . import ppo as _ppo
+from . import ekf as _ekf
 from . import pf as _pf
 from . import lqg as _lqg
 from . import ukf as _ukf
+from ._wire import _torch  # noqa: F401
+# the families' results and tables, importable from here as before they moved
+from .rollout import Rollout, StepJacobian  # noqa: F401
+from .mlp_rollout import MlpRollout  # noqa: F401
+from .ilqr import LqrGains  # noqa: F401
+from .mppi import MPPI_MAX_KNOT, MppiCosts, MppiTemperature, MppiUpdate, mppi_knots  # noqa: F401
+from .es import Population  # noqa: F401
+from .ppo import PPO_STATS, ActorCritic, PpoGrad  # noqa: F401
+from .ekf import EkfResult, RtsResult  # noqa: F401
+from .pf import PfResult  # noqa: F401
+from .lqg import LqgResult  # noqa: F401
+from .ukf import UkfResult  # noqa: F401
 from .spaces import gymnasium_api
 
 # Envs that hold a device context.  Whatever is still open when the interpreter exits is closed by an exit handler,
@@ -90,67 +107,6 @@ _TASK_KEYS = {"initial_random_force": "initial_random_force",             # task
 PACKED_ROWS_MAX_ENVS = 131072
 
 STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dTheta', 'Psi', 'dPsi']
-
-# CopterVecEnv.step_jacobian's result (device tensors)
-StepJacobian = collections.namedtuple("StepJacobian", "dx du reward_dx reward_du branch")
-# CopterVecEnv.rollout_states' result (device tensors, [K, N, ...])
-Rollout = collections.namedtuple("Rollout", "x reward terminated truncated status")
-# a closed-loop rollout (rollout_mlp_states): Rollout's fields plus the observation and action tapes
-MlpRollout = collections.namedtuple("MlpRollout", "x reward terminated truncated status obs actions")
-# CopterVecEnv.rollout_lqr's result: the time-varying gains K [K,N,A,12] and d [K,N,A], the model's predicted cost change
-# dV [N,2], the value model at the start S0 [N,12,12], s0 [12,N], and ok [N] bool (every Cholesky pivot positive)
-LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
-# CopterVecEnv.rollout_ekf's result: the filtered means x [K,N,12] and the priors x_pred [K,N,12], the
-# last posterior covariance P [N,12,12], its diagonal per step var [K,N,12], nis [K,N], loglik [N], the status [K,N] and
-# step_jacobian branch bits [K,N] of the filter's own mean, ok [N] bool, and P_tape [K,N,12,12] (None without tape=True)
-EkfResult = collections.namedtuple("EkfResult", "x x_pred P var nis loglik status branch ok P_tape")
-# CopterVecEnv.rollout_rts' result: the smoothed means x [K,N,12], their covariances P_tape
-# [K,N,12,12] (None with tape=False) and diagonals var [K,N,12], the smoothed starting point x0 [12,N], P0 [N,12,12], and
-# ok [N] bool (every Cholesky pivot positive and finite)
-RtsResult = collections.namedtuple("RtsResult", "x P_tape var x0 P0 ok")
-PfResult = _pf.PfResult      # CopterVecEnv.rollout_pf's result (pf.py)
-LqgResult = _lqg.LqgResult   # CopterVecEnv.rollout_lqg's result (lqg.py)
-UkfResult = _ukf.UkfResult   # CopterVecEnv.rollout_ukf's result (ukf.py)
-# CopterVecEnv.rollout_mppi_costs' and rollout_mppi_update's results
-MppiCosts = collections.namedtuple("MppiCosts", "costs best")
-MppiUpdate = collections.namedtuple("MppiUpdate", "actions ess cost_min")
-# CopterVecEnv.rollout_mppi_temperature's result
-MppiTemperature = collections.namedtuple("MppiTemperature", "lam ess")
-# CopterVecEnv.rollout_mlp_population's result
-Population = collections.namedtuple("Population", "returns lengths end_flags end_status member_returns")
-# CopterVecEnv.rollout_actor_critic's result
-ActorCritic = collections.namedtuple("ActorCritic", "obs actions means logp values reward terminated truncated live")
-# ppo_grad: grad [P + Pv + A] float64 (actor | critic | log_std), stats [8] float64 (PPO_STATS)
-PpoGrad = collections.namedtuple("PpoGrad", "grad stats")
-PPO_STATS = ("live_samples", "policy_loss", "value_loss", "entropy", "loss", "approx_kl", "clip_fraction",
-             "max_ratio_error")
-MPPI_MAX_KNOT = 16384                                        # knot + 1 <= 16 384: the noise keys stay distinct
-
-
-def mppi_knots(K, hold):
-    """The knot table of K steps for normalised linear interpolation over holds of `hold` steps, as rollout_mppi_costs /
-    rollout_mppi_update take it (knots=): (knot [K] uint32, w [K,2] float32) with, for step k = 1..K,
-
-        knot[k] = (k - 1) // hold + 1,   t = ((k - 1) % hold) / hold,   w[k] = (1 - t, t) / sqrt((1 - t)^2 + t^2)
-
-    computed in float64 and rounded once: the noise of step k is w[k][0] eps(knot[k]) + w[k][1] eps(knot[k] + 1), of unit
-    variance at every step, and steps inside a hold are correlated.  hold = 1 is the white table (k, 1, 0)."""
-    if not isinstance(K, (int, np.integer)) or isinstance(K, bool) or K < 1:
-        raise ValueError("K must be an int >= 1, got %r" % (K,))
-    if not isinstance(hold, (int, np.integer)) or isinstance(hold, bool) or hold < 1:
-        raise ValueError("hold must be an int >= 1, got %r" % (hold,))
-    k0 = np.arange(int(K), dtype=np.int64)
-    t = (k0 % int(hold)).astype(np.float64) / float(hold)
-    w = np.stack([1.0 - t, t], axis=1) / np.sqrt((1.0 - t) ** 2 + t ** 2)[:, None]
-    knot = k0 // int(hold) + 1
-    if int(knot[-1]) + 1 > MPPI_MAX_KNOT:
-        raise ValueError("K / hold is too large: knot + 1 must be <= %d" % MPPI_MAX_KNOT)
-    return knot.astype(np.uint32), w.astype(np.float32)
-
-
-def _torch():
-    import torch
-    return torch
 
 
 class CopterVecEnv(_VectorEnvBase):
@@ -912,1446 +868,34 @@ class CopterVecEnv(_VectorEnvBase):
         if self.episode_stats:
             self._done["return"] = torch.zeros(n, dtype=torch.float32, device=dev)
 
-    # -- Dynamics-level access (reference dynamics/__init__.py public methods) ---------
-    def step_jacobian(self, actions, state=None, dtype=None):
-        """Jacobians of the step that step(actions) would take, for every env, as device tensors; NO env state
-        changes.  Returns StepJacobian(dx [N,12,12] = d x' / d x, du [N,12,A] = d x' / d actions (the actions as
-        step() receives them, before the clip to [0, 1]; the clip's derivative is 1 on [0, 1] and 0 outside),
-        reward_dx [N,12], reward_du [N,A] = the gradient of the step's reward, branch [N] uint8 = the CS_JAC_*
-        bits of the branches the step takes).  x is the full state in upstream slot order (STATE_NAMES_12); an
-        observation is a slice of x', so its Jacobian is the matching rows of dx / du.
-
-        The transition differentiated is the physics + reward of the step with auto-reset DISABLED: a termination
-        in this step and the auto-reset behind it do not enter (a NEXT_STEP reset already pending gives
-        dx = du = 0).  The physics is the float64 arithmetic of the step kernels (per-env vehicles, both thrust
-        laws, the rotor-gyro term, `substeps` calls with the pending perturbation in the first); under
-        action_arith="float32" it is still the float64 motor law.
-
-        state=None linearises at the stored state the next step() starts from (float32 storage modes: the decoded
-        words get_state() reports).  state={"x": [12,N] float64, "status": [N] uint8, "force": [3,N] newtons
-        (optional, pending)} -- the keys and shapes of get_state() / set_state() -- linearises at that point instead
-        (hover, a planned trajectory).  dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).
-        Asynchronous on the current stream; the returned tensors are buffers of this env, overwritten by the next
-        call with the same dtype."""
-        self._check_open()
-        torch = _torch()
-        dtype = self._out_dtype(dtype)
-        n, ad = self.num_envs, self.action_dim
-        a, _ = self._dev_f32(actions, (n, ad), "actions")
-        io = _lib.JacobianIO()
-        io.struct_size = C.sizeof(_lib.JacobianIO)
-        io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-        io.actions_dev = a.data_ptr()
-        keep = [a]
-        if state is not None:
-            unknown = set(state) - {"x", "status", "force"}
-            if unknown or "x" not in state or "status" not in state:
-                raise ValueError("state needs the keys 'x' and 'status' (and optionally 'force'), got %s"
-                                 % sorted(state))
-            io.x_dev = self._state_dev(state["x"], (12, n), torch.float64, "x", keep)
-            io.status_dev = self._state_dev(state["status"], (n,), torch.uint8, "status", keep)
-            if state.get("force") is not None:
-                io.force_dev = self._state_dev(state["force"], (3, n), torch.float64, "force", keep)
-        cache = getattr(self, "_jac_out", None)
-        if cache is None:
-            cache = self._jac_out = {}
-        out = cache.get(dtype)
-        if out is None:
-            out = cache[dtype] = StepJacobian(
-                torch.empty((n, 12, 12), dtype=dtype, device=self.device),
-                torch.empty((n, 12, ad), dtype=dtype, device=self.device),
-                torch.empty((n, 12), dtype=dtype, device=self.device),
-                torch.empty((n, ad), dtype=dtype, device=self.device),
-                torch.empty(n, dtype=torch.uint8, device=self.device))
-        io.dx_dev, io.du_dev, io.reward_dx_dev, io.reward_du_dev, io.branch_dev = (t.data_ptr() for t in out)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_step_jacobian(self._ctx, C.byref(io), self._stream()))
-        self._keep = keep
-        return out
-
-    def _rollout_io(self, actions, state, num_steps=None):
-        """The cs_rollout_io of rollout_states / rollout_vjp: actions [K,N,A] and the start point; returns (io, K, the
-        tensors the call reads).  actions=None (the closed-loop calls): no actions, K = num_steps."""
-        torch = _torch()
-        n, ad = self.num_envs, self.action_dim
-        io = _lib.RolloutIO()
-        io.struct_size = C.sizeof(_lib.RolloutIO)
-        keep = []
-        if actions is None:
-            K = num_steps
-        else:
-            shape = tuple(actions.shape) if hasattr(actions, "shape") else np.shape(actions)
-            if len(shape) != 3 or shape[0] < 1:
-                raise ValueError("actions must have shape (K, %d, %d) with K >= 1, got %s" % (n, ad, tuple(shape)))
-            K = int(shape[0])
-            a, _ = self._dev_f32(actions, (K, n, ad), "actions")
-            io.actions_dev = a.data_ptr()
-            keep.append(a)
-        io.num_steps = K
-        if state is not None:
-            unknown = set(state) - {"x", "status", "force", "prev_shaping"}
-            if unknown or "x" not in state or "status" not in state:
-                raise ValueError("state needs the keys 'x' and 'status' (and optionally 'force', 'prev_shaping'), got %s"
-                                 % sorted(state))
-            io.start_x_dev = self._state_dev(state["x"], (12, n), torch.float64, "x", keep)
-            io.start_status_dev = self._state_dev(state["status"], (n,), torch.uint8, "status", keep)
-            if state.get("force") is not None:
-                io.start_force_dev = self._state_dev(state["force"], (3, n), torch.float64, "force", keep)
-            if state.get("prev_shaping") is not None:
-                io.start_prev_shaping_dev = self._state_dev(state["prev_shaping"], (n,), torch.float64, "prev_shaping",
-                                                            keep)
-        return io, K, keep
-
-    def _state_dev(self, v, shape, dt, name, keep):
-        """state[name] of step_jacobian or a rollout as a contiguous device tensor of dtype dt, kept alive in `keep`;
-        returns its data pointer."""
-        torch = _torch()
-        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-        if tuple(t.shape) != shape:
-            raise ValueError("state[%r] must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-        t = t.detach().to(device=self.device, dtype=dt, non_blocking=True).contiguous()
-        keep.append(t)
-        return t.data_ptr()
-
-    @staticmethod
-    def _out_dtype(dtype):
-        """The dtype of a derivative's outputs: torch.float64 (None) or torch.float32."""
-        torch = _torch()
-        dtype = torch.float64 if dtype is None else dtype
-        if dtype not in (torch.float64, torch.float32):
-            raise ValueError("dtype must be torch.float64 or torch.float32")
-        return dtype
-
-    def _check_tape(self, source, *tapes):
-        """A backward's tape, (tensor, name, shape, dtype) each: contiguous device tensors as `source` returned them."""
-        torch = _torch()
-        for t, name, shape, dt in tapes:
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("%s must be a device tensor of shape %s (%s' result)" % (name, shape, source))
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous %s tensor on %s" % (name, dt, self.device))
-
-    def _cotangents(self, io, gx, gr, K, keep):
-        """io.gx_dev and io.gr_dev of a backward: gx [K,N,12] and gr [K,N] (None: zero) as float64 device tensors, kept
-        alive in `keep`."""
-        torch = _torch()
-        n = self.num_envs
-
-        def cot(v, shape, name):
-            t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(v)))
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(t.shape)))
-            if not t.dtype.is_floating_point:
-                raise ValueError("%s must be a floating-point array" % name)
-            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        if gx is not None:
-            io.gx_dev = cot(gx, (K, n, 12), "gx")
-        if gr is not None:
-            io.gr_dev = cot(gr, (K, n), "gr")
-
-    def _grad_out(self, io, prefix, K, dtype, explicit):
-        """A backward's outputs, set in io: g_actions [K,N,A] and, for an explicit start, g_x0 [12,N] (else None) -- buffers
-        of this env cached under `prefix` (the plain and the closed-loop calls keep their own)."""
-        torch = _torch()
-        n, dev = self.num_envs, self.device
-        ga = self._rollout_cache((prefix + "g_actions", K, dtype),
-                                 lambda: torch.empty((K, n, self.action_dim), dtype=dtype, device=dev))
-        io.g_actions_dev = ga.data_ptr()
-        g0 = None
-        if explicit:
-            g0 = self._rollout_cache((prefix + "g_x0", dtype), lambda: torch.empty((12, n), dtype=dtype, device=dev))
-            io.g_x0_dev = g0.data_ptr()
-        return ga, g0
-
-    def _rollout_cache(self, key, make):
-        cache = getattr(self, "_rollout_out", None)
-        if cache is None:
-            cache = self._rollout_out = {}
-        out = cache.get(key)
-        if out is None:
-            out = cache[key] = make()
-        return out
-
-    def _param_io(self, vehicle, keep, dtype=None, check=True):
-        """The cs_rollout_param_io of a rollout with a vehicle override and / or parameter gradients: vehicle [12,N]
-        float64 (set_vehicle_params' rows) is checked on the device -- M, Ix, Iy, Iz positive, every value finite; a
-        synchronising reduction, skipped with check=False for a tensor already checked -- and kept alive in `keep`."""
-        torch = _torch()
-        pio = _lib.RolloutParamIO()
-        pio.struct_size = C.sizeof(_lib.RolloutParamIO)
-        pio.out_dtype = _lib.JAC_F32 if dtype == torch.float32 else _lib.JAC_F64
-        if vehicle is not None:
-            n = self.num_envs
-            t = vehicle if isinstance(vehicle, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(vehicle)))
-            rows = len(self.VEHICLE_ROWS)
-            if tuple(t.shape) != (rows, n):
-                raise ValueError("vehicle must have shape (%d, %d) (rows %s), got %s"
-                                 % (rows, n, self.VEHICLE_ROWS, tuple(t.shape)))
-            if not t.dtype.is_floating_point:
-                raise ValueError("vehicle must be a floating-point array")
-            t = t.detach().to(device=self.device, dtype=torch.float64, non_blocking=True).contiguous()
-            # the C ABI cannot check a device table synchronously: one reduction here (M, Ix, Iy, Iz are rows 2, 4, 5, 6)
-            inertia = t[[2, 4, 5, 6]]
-            if check and not bool(torch.isfinite(t).all() & (inertia > 0).all()):
-                raise ValueError("vehicle: M, Ix, Iy, Iz must be positive and every value finite")
-            keep.append(t)
-            pio.vehicle_dev = t.data_ptr()
-        return pio
-
-    def rollout_states(self, actions, state=None, vehicle=None):
-        """K calls of step() with auto-reset DISABLED, as a pure function: Rollout(x [K,N,12] float64, reward [K,N]
-        float64, terminated [K,N] bool, truncated [K,N] bool, status [K,N] uint8) of device tensors; NO env state
-        changes (no words, counters, episode numbers, prev_shaping, statistics or RNG position).  actions [K,N,A]: step
-        k takes actions[k-1], as step() receives them.
-
-        x[k-1] is the decoded stored state after step k in upstream slot order (STATE_NAMES_12; in the float32 storage
-        modes the words get_state() would report), reward[k-1] the value step() rounds to float32.  Both are
-        bit-identical to a twin env with autoreset_mode="disabled" stepped K times.  An observation is a slice of x
-        (STATE_NAMES).
-
-        state=None starts from the stored state the next step() starts from: its pending perturbation enters the first
-        substep of step 1, and an env with a NEXT_STEP reset pending performs that reset in step 1 with the draw step()
-        would make.  state={"x": [12,N] float64, "status": [N] uint8, "force": [3,N] newtons (optional, pending),
-        "prev_shaping": [N] float64 (optional; NaN = None: reward 0 in step 1)} -- get_state()'s layout, as
-        step_jacobian takes it -- starts from that point instead; without prev_shaping it is shaping(x0).  The step
-        counter (time-limit truncation) is the env's in both cases.  vehicle=[12,N] float64 (set_vehicle_params' rows
-        VEHICLE_ROWS) rolls out with that vehicle instead of the env's, for this call only: the env's installed vehicle
-        is untouched.  Asynchronous on the current stream (an override is checked with one device
-        reduction, which synchronises); the returned tensors are buffers of this env, overwritten by the next call with
-        the same K."""
-        self._check_open()
-        torch = _torch()
-        io, K, keep = self._rollout_io(actions, state)
-        pio = None if vehicle is None else self._param_io(vehicle, keep)
-        n, dev = self.num_envs, self.device
-        out = self._rollout_cache(("states", K), lambda: Rollout(
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((K, n), dtype=torch.float64, device=dev),
-            torch.empty((K, n), dtype=torch.bool, device=dev),
-            torch.empty((K, n), dtype=torch.bool, device=dev),
-            torch.empty((K, n), dtype=torch.uint8, device=dev)))
-        io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in out)
-        with torch.cuda.device(self.device):
-            if pio is None:
-                _lib.check(self._lib.cs_rollout_states(self._ctx, C.byref(io), self._stream()))
-            else:
-                _lib.check(self._lib.cs_rollout_states_ex(self._ctx, C.byref(io), C.byref(pio), self._stream()))
-        self._keep = keep
-        return out
-
-    def rollout_vjp_params(self, actions, rollout, gx=None, gr=None, state=None, vehicle=None, dtype=None):
-        """rollout_vjp with the gradients with respect to the vehicle and the start's pending force as well: returns
-        (g_actions [K,N,A], g_x0 [12,N] or None, g_vehicle [12,N], g_force [3,N]).  g_vehicle = dL / d the vehicle
-        rows (VEHICLE_ROWS, per env: sum over envs for a shared vehicle; rows that do not enter the configuration are
-        0: B under the lift law, rho and C_L under the B law, Jr without rotor_gyro).  g_force = dL / d state["force"]
-        (newtons), or with the stored start dL / d its pending perturbation; exactly 0 where none is pending (consumed,
-        or a state without "force": pass zeros for the sensitivity at F = 0), where it never integrates, and for an env
-        whose NEXT_STEP reset is pending (the new episode's draw is a constant).  `vehicle`
-        is the override rollout_states(..., vehicle=) was given (None: the env's own).  g_actions and g_x0 are
-        rollout_vjp's, bit for bit.  DESIGN section 11.  Same buffers and stream rules as rollout_vjp; not available
-        with action_arith="float32"."""
-        return self._vjp(actions, rollout, gx, gr, state, dtype, params=True, vehicle=vehicle)
-
-    def rollout_vjp(self, actions, rollout, gx=None, gr=None, state=None, dtype=None):
-        """Reverse-mode gradient of a rollout: given the cotangents gx [K,N,12] (on rollout.x) and gr [K,N] (on
-        rollout.reward) -- either may be None (zero) -- returns (g_actions [K,N,A] = dL / d actions, the actions as
-        step() receives them (the clip's derivative is 1 on [0, 1] and 0 outside), g_x0 [12,N] = dL / d state["x"] for an
-        explicit start, None for the stored one).  `rollout` is what rollout_states(actions, state) returned for the
-        same actions and start (its x and status are the tape the backward recomputes each step from); with the stored
-        start the env must not have been stepped, reset or set since.  The derivative rules are step_jacobian's (DESIGN
-        section 9) plus the prev_shaping term: reward_k = shaping(x_k) - shaping(x_{k-1}), and without a given
-        prev_shaping the first step's differentiates shaping(x0).  The perturbation force and the vehicle are constants.
-        dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).  Asynchronous on the current
-        stream; the returned tensors are buffers of this env, overwritten by the next call with the same K and dtype.
-        rollout_vjp_params differentiates with respect to the vehicle and the force as well."""
-        return self._vjp(actions, rollout, gx, gr, state, dtype)
-
-    def _vjp(self, actions, rollout, gx, gr, state, dtype, params=False, vehicle=None, check_vehicle=True):
-        self._check_open()
-        torch = _torch()
-        dtype = self._out_dtype(dtype)
-        io, K, keep = self._rollout_io(actions, state)
-        n = self.num_envs
-        io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-        x, status = getattr(rollout, "x", None), getattr(rollout, "status", None)
-        self._check_tape("rollout_states", (x, "rollout.x", (K, n, 12), torch.float64),
-                         (status, "rollout.status", (K, n), torch.uint8))
-        io.x_dev, io.status_dev = x.data_ptr(), status.data_ptr()
-        self._cotangents(io, gx, gr, K, keep)
-        ga, g0 = self._grad_out(io, "", K, dtype, state is not None)
-        if not params:
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.cs_rollout_vjp(self._ctx, C.byref(io), self._stream()))
-            self._keep = keep
-            return ga, g0
-        pio = self._param_io(vehicle, keep, dtype, check=check_vehicle)
-        dev = self.device
-        gv = self._rollout_cache(("g_vehicle", dtype), lambda: torch.empty((len(self.VEHICLE_ROWS), n), dtype=dtype,
-                                                                           device=dev))
-        gf = self._rollout_cache(("g_force", dtype), lambda: torch.empty((3, n), dtype=dtype, device=dev))
-        pio.g_vehicle_dev, pio.g_force_dev = gv.data_ptr(), gf.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_vjp_ex(self._ctx, C.byref(io), C.byref(pio), self._stream()))
-        self._keep = keep
-        return ga, g0, gv, gf
-
-    def _mlp_io(self, params, hidden, num_steps, offsets, keep):
-        """The cs_rollout_mlp_io of rollout_mlp_states / rollout_mlp_vjp (its tapes not yet set) and the device params."""
-        torch = _torch()
-        if not isinstance(num_steps, int) or isinstance(num_steps, bool) or num_steps < 1:
-            raise ValueError("num_steps must be an int >= 1, got %r" % (num_steps,))
-        P = _mlp.num_params(self.obs_dim, self.action_dim, hidden)    # (checks hidden)
-        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.dim() != 1:
-            raise ValueError("params must be a 1-D float32 torch tensor of %d values (gym_copter_amd.mlp), got %s"
-                             % (P, getattr(params, "dtype", type(params).__name__)))
-        if params.shape[0] != P:
-            raise ValueError("params must have %d values for obs_dim %d, action_dim %d, hidden %d, got %d"
-                             % (P, self.obs_dim, self.action_dim, hidden, params.shape[0]))
-        p = params.detach().to(self.device).contiguous()
-        keep.append(p)
-        mio = _lib.RolloutMlpIO()
-        mio.struct_size = C.sizeof(_lib.RolloutMlpIO)
-        mio.hidden = hidden
-        mio.params_dev = p.data_ptr()
-        if offsets is not None:
-            u, _ = self._dev_f32(offsets, (num_steps, self.num_envs, self.action_dim), "offsets")
-            keep.append(u)
-            mio.offsets_dev = u.data_ptr()
-        return mio, p
-
-    def rollout_mlp_states(self, params, num_steps, hidden, offsets=None, state=None):
-        """K = num_steps calls of step() with auto-reset DISABLED under a fused MLP policy, as a pure function (DESIGN
-        section 12): step k takes a_k = float32(pi(o_{k-1}) + offsets[k-1]), where o_{k-1} is the float32 observation
-        step() returns for the state before step k (the start's for k = 1) and pi the MLP of `params` ([P] float32, the
-        layout of gym_copter_amd.mlp; hidden = 0 is linear, 1..64 one tanh layer).  offsets [K,N,A] (None = 0) is an
-        open-loop term added to the policy's action.  The start point, the pending perturbation, a pending NEXT_STEP
-        reset, prev_shaping and the step counter are rollout_states'; no env state changes.
-
-        Returns MlpRollout(x, reward, terminated, truncated, status -- rollout_states' fields, bit-identical to a twin
-        env stepped with `actions` --, obs [K,N,OBS] float32 (o_{k-1}), actions [K,N,A] float32 (a_k)).  Asynchronous on
-        the current stream; the tensors are buffers of this env, overwritten by its next call with the same K."""
-        self._check_open()
-        torch = _torch()
-        keep = []
-        mio, _ = self._mlp_io(params, hidden, num_steps, offsets, keep)
-        io, K, k2 = self._rollout_io(None, state, num_steps)
-        keep += k2
-        n, dev = self.num_envs, self.device
-        out = self._rollout_cache(("mlp_states", K), lambda: MlpRollout(
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((K, n), dtype=torch.float64, device=dev),
-            torch.empty((K, n), dtype=torch.bool, device=dev),
-            torch.empty((K, n), dtype=torch.bool, device=dev),
-            torch.empty((K, n), dtype=torch.uint8, device=dev),
-            torch.empty((K, n, self.obs_dim), dtype=torch.float32, device=dev),
-            torch.empty((K, n, self.action_dim), dtype=torch.float32, device=dev)))
-        io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in out[:5])
-        mio.obs_out_dev, mio.actions_out_dev = out.obs.data_ptr(), out.actions.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_mlp_states(self._ctx, C.byref(io), C.byref(mio), self._stream()))
-        self._keep = keep
-        return out
-
-    def mlp_param_grad(self, params, hidden, obs, g_actions, out=None):
-        """g_params [P] float64 = sum_{k,n} J_params pi(obs[k,n])^T g_actions[k,n], reduced ON THE DEVICE by one HIP
-        kernel (cs_mlp_param_grad): the device counterpart of gym_copter_amd.mlp.param_grad, the
-        same sums term by term in float64 (h recomputed with the device library's tanh), in an order of its own that
-        is fixed -- the same inputs give the same bits on every call.  obs [K,N,OBS] float32 is the forward's obs tape,
-        g_actions [K,N,A] float64 or float32 what rollout_mlp_vjp returned; both contiguous tensors on this env's
-        device.  Asynchronous on the current stream; the result is written (not accumulated) into `out`, a contiguous
-        [P] float64 tensor on this env's device, or into a new tensor."""
-        self._check_open()
-        torch = _torch()
-        keep = []
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[0] < 1:
-            raise ValueError("obs must be the [K,%d,%d] obs tape of rollout_mlp_states" % (self.num_envs, self.obs_dim))
-        K = int(obs.shape[0])
-        _, p = self._mlp_io(params, hidden, K, None, keep)
-        n = self.num_envs
-        self._check_tape("rollout_mlp_states", (obs, "obs", (K, n, self.obs_dim), torch.float32))
-        if not isinstance(g_actions, torch.Tensor) or g_actions.dtype not in (torch.float64, torch.float32):
-            raise ValueError("g_actions must be a float64 or float32 device tensor of shape (%d, %d, %d)"
-                             % (K, n, self.action_dim))
-        self._check_tape("rollout_mlp_vjp", (g_actions, "g_actions", (K, n, self.action_dim), g_actions.dtype))
-        if out is None:
-            out = torch.empty(p.shape[0], dtype=torch.float64, device=self.device)
-        else:
-            self._check_tape("mlp_param_grad", (out, "out", (p.shape[0],), torch.float64))
-        gio = _lib.MlpGradIO()
-        gio.struct_size = C.sizeof(_lib.MlpGradIO)
-        gio.ga_dtype = _lib.JAC_F32 if g_actions.dtype == torch.float32 else _lib.JAC_F64
-        gio.hidden, gio.num_steps = hidden, K
-        gio.params_dev, gio.obs_dev = p.data_ptr(), obs.data_ptr()
-        gio.g_actions_dev, gio.g_params_dev = g_actions.data_ptr(), out.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_mlp_param_grad(self._ctx, C.byref(gio), self._stream()))
-        self._keep = keep + [obs, g_actions]
-        return out
-
-    def rollout_mlp_vjp(self, params, rollout, gx=None, gr=None, state=None, hidden=None, offsets=None, dtype=None,
-                        param_grad=True, g_actions_in=None, reduce="torch"):
-        """Reverse-mode gradient of a closed-loop rollout: given the cotangents gx [K,N,12] (on rollout.x) and gr [K,N]
-        (on rollout.reward), either None (zero), returns (g_params [P] float64, g_actions [K,N,A], g_x0 [12,N] or None).
-
-        g_actions = dL / d a_k including every later step's dependence on a_k through the policy -- which is also
-        dL / d offsets; g_x0 = dL / d state["x"] of an explicit start (including the path through o_0), None for the
-        stored one; g_params = sum over envs and steps of J_params pi^T g_actions, reduced by torch from rollout.obs
-        (gym_copter_amd.mlp.param_grad; param_grad=False skips it and returns None).  `rollout` is what
-        rollout_mlp_states(params, K, hidden, offsets, state) returned (its x, status, obs and actions are the tape;
-        with the stored start the env must not have been stepped since); `hidden` must be that call's.  The float32
-        rounding of o and a is straight-through.  dtype: torch.float64 (default) or torch.float32 for g_actions and
-        g_x0.  Asynchronous on the current stream; g_actions and g_x0 are buffers of this env, overwritten by its next
-        call with the same K and dtype.  (`offsets` is accepted for symmetry with the forward; the backward reads the
-        action tape, not the offsets.)
-
-        g_actions_in [K,N,A] (None = zero) is a cotangent taken directly on the action tape rollout.actions -- a loss on
-        the actions themselves, such as a control-effort penalty: a_k is the action as step() receives it, before the
-        clip, so it adds to the step's own g_a_k without a mask, and the total is what g_actions returns, what the
-        policy carries back into the state and what g_params is reduced from.  An env that resets in step 1 returns
-        g_actions[0] = g_actions_in[0].  reduce="torch" (default) makes g_params with gym_copter_amd.mlp.param_grad,
-        reduce="device" with mlp_param_grad (one HIP kernel; the same sums in another, fixed, order)."""
-        self._check_open()
-        torch = _torch()
-        if hidden is None:
-            raise ValueError("hidden is required (the forward's)")
-        if reduce not in ("torch", "device"):
-            raise ValueError("reduce must be 'torch' or 'device', got %r" % (reduce,))
-        dtype = self._out_dtype(dtype)
-        n, ad, od = self.num_envs, self.action_dim, self.obs_dim
-        acts = getattr(rollout, "actions", None)
-        if not isinstance(acts, torch.Tensor) or acts.dim() != 3:
-            raise ValueError("rollout.actions must be the [K,N,A] action tape of rollout_mlp_states")
-        K = int(acts.shape[0])
-        keep = []
-        mio, p = self._mlp_io(params, hidden, K, None, keep)
-        io, _, k2 = self._rollout_io(None, state, K)
-        keep += k2
-        io.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-        obs = getattr(rollout, "obs", None)
-        self._check_tape("rollout_mlp_states", (rollout.x, "rollout.x", (K, n, 12), torch.float64),
-                         (rollout.status, "rollout.status", (K, n), torch.uint8),
-                         (acts, "rollout.actions", (K, n, ad), torch.float32),
-                         (obs, "rollout.obs", (K, n, od), torch.float32))
-        io.x_dev, io.status_dev = rollout.x.data_ptr(), rollout.status.data_ptr()
-        mio.actions_out_dev = acts.data_ptr()
-        self._cotangents(io, gx, gr, K, keep)
-        xio = None
-        if g_actions_in is not None:
-            gin = g_actions_in
-            if not isinstance(gin, torch.Tensor) or not gin.dtype.is_floating_point:
-                raise ValueError("g_actions_in must be a floating-point torch tensor of shape (%d, %d, %d)" % (K, n, ad))
-            if tuple(gin.shape) != (K, n, ad):
-                raise ValueError("g_actions_in must have shape %s, got %s" % ((K, n, ad), tuple(gin.shape)))
-            if gin.device != self.device:
-                raise ValueError("g_actions_in must be on %s, got %s" % (self.device, gin.device))
-            gin = gin.detach().to(torch.float64).contiguous()
-            keep.append(gin)
-            xio = _lib.RolloutMlpExIO()
-            xio.struct_size = C.sizeof(_lib.RolloutMlpExIO)
-            xio.g_actions_in_dev = gin.data_ptr()
-        ga, g0 = self._grad_out(io, "mlp_", K, dtype, state is not None)
-        with torch.cuda.device(self.device):
-            # (xio = None is a NULL block: exactly cs_rollout_mlp_vjp)
-            _lib.check(self._lib.cs_rollout_mlp_vjp_ex(self._ctx, C.byref(io), C.byref(mio),
-                                                       None if xio is None else C.byref(xio), self._stream()))
-            gp = None
-            if param_grad:
-                gp = self.mlp_param_grad(p, hidden, obs, ga) if reduce == "device" else _mlp.param_grad(p, hidden, obs, ga)
-        self._keep = keep
-        return gp, ga, g0
-
-    # -- the iLQR backward pass and its line-search forward (DESIGN section 13) --------
-    def _lqr_weights(self, Q, R, Q_final, definite=True):
-        """Q [12,12], R [A,A], Q_final [12,12] or None, checked on the host (symmetric, finite; R's diagonal > 0, or
-        >= 0 with definite=False: MPPI inverts nothing) and kept on the device: the same values are uploaded once (the
-        iLQR and MPPI drivers pass them every iteration)."""
-        torch = _torch()
-        ad = self.action_dim
-
-        def host(m, shape, name):
-            a = np.asarray(m.detach().cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float64)
-            if a.shape != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
-            if not np.isfinite(a).all():
-                raise ValueError("%s must be finite" % name)
-            if not np.array_equal(a, a.T):
-                raise ValueError("%s must be symmetric" % name)
-            return np.ascontiguousarray(a)
-        q = host(Q, (12, 12), "Q")
-        r = host(R, (ad, ad), "R")
-        if definite and not (np.diag(r) > 0).all():
-            raise ValueError("R must be positive definite: its diagonal must be > 0")
-        if not (np.diag(r) >= 0).all():
-            raise ValueError("R must be positive semidefinite: its diagonal must be >= 0")
-        qf = None if Q_final is None else host(Q_final, (12, 12), "Q_final")
-        key = (q.tobytes(), r.tobytes(), None if qf is None else qf.tobytes())
-        cache = getattr(self, "_lqr_w", None)
-        if cache is None or cache[0] != key:
-            dev = [None if m is None else torch.from_numpy(m).to(self.device) for m in (q, r, qf)]
-            cache = self._lqr_w = (key, dev)
-        return cache[1]
-
-    def rollout_lqr(self, actions, rollout, Q, R, q=None, r=None, Q_final=None, mu=0.0, state=None, dtype=None):
-        """The iLQR backward pass over a rollout's tape, one kernel: the Riccati recursion of the quadratic model of a
-        cost J = sum_k [l_k(x_k) + m_k(a_k)] around the rollout, with the step Jacobians of step_jacobian (every branch
-        rule of DESIGN section 9) applied on the fly and never stored.  `rollout` is what rollout_states(actions, state)
-        returned for the same actions and start (as rollout_vjp takes it).  q [K,N,12] = grad l_k at rollout.x[k-1],
-        r [K,N,A] = grad m_k at actions[k-1] (None: zero); Q [12,12] symmetric PSD, R [A,A] symmetric PD and Q_final
-        (replaces Q at the last step) are the Hessians, shared by every env and step; mu >= 0 is the Levenberg term
-        added to Quu's diagonal before it is inverted.
-
-        Returns LqrGains(K [K,N,A,12], d [K,N,A], dV [N,2], S0 [N,12,12], s0 [12,N], ok [N] bool): the action
-        a_k + alpha d_k + K_k (x_{k-1} - xbar_{k-1}) (rollout_feedback_states) changes the model's cost by
-        alpha dV[:,0] + alpha^2 dV[:,1]; S0, s0 are the value model at the start; ok is False where a Cholesky pivot was
-        not positive (raise mu).  dtype: torch.float64 (default) or torch.float32 (the float64 values rounded).
-        Asynchronous on the current stream; the tensors are buffers of this env, overwritten by its next call with the
-        same K and dtype.  No env state changes."""
-        self._check_open()
-        torch = _torch()
-        dtype = self._out_dtype(dtype)
-        mu = float(mu)
-        if not (mu >= 0.0) or mu == float("inf"):
-            raise ValueError("mu must be finite and >= 0, got %r" % (mu,))
-        Qd, Rd, Qfd = self._lqr_weights(Q, R, Q_final)
-        io, K, keep = self._rollout_io(actions, state)
-        n, ad, dev = self.num_envs, self.action_dim, self.device
-        x, status = getattr(rollout, "x", None), getattr(rollout, "status", None)
-        self._check_tape("rollout_states", (x, "rollout.x", (K, n, 12), torch.float64),
-                         (status, "rollout.status", (K, n), torch.uint8))
-        io.x_dev, io.status_dev = x.data_ptr(), status.data_ptr()
-        lio = _lib.RolloutLqrIO()
-        lio.struct_size = C.sizeof(_lib.RolloutLqrIO)
-        lio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-        lio.mu = mu
-        for v, shape, name in ((q, (K, n, 12), "q"), (r, (K, n, ad), "r")):
-            if v is None:
-                continue
-            if not isinstance(v, torch.Tensor) or not v.dtype.is_floating_point:
-                raise ValueError("%s must be a floating-point torch tensor of shape %s" % (name, shape))
-            if tuple(v.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(v.shape)))
-            if v.device != dev:
-                raise ValueError("%s must be on %s, got %s" % (name, dev, v.device))
-            t = v.detach().to(torch.float64).contiguous()
-            keep.append(t)
-            setattr(lio, name + "_dev", t.data_ptr())
-        lio.Q_dev, lio.R_dev = Qd.data_ptr(), Rd.data_ptr()
-        lio.Q_final_dev = None if Qfd is None else Qfd.data_ptr()
-        out = self._rollout_cache(("lqr", K, dtype), lambda: (
-            torch.empty((K, n, ad, 12), dtype=dtype, device=dev), torch.empty((K, n, ad), dtype=dtype, device=dev),
-            torch.empty((n, 2), dtype=dtype, device=dev), torch.empty((n, 12, 12), dtype=dtype, device=dev),
-            torch.empty((12, n), dtype=dtype, device=dev), torch.empty(n, dtype=torch.bool, device=dev)))
-        lio.K_dev, lio.d_dev, lio.dV_dev, lio.S0_dev, lio.s0_dev, lio.ok_dev = (t.data_ptr() for t in out)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_lqr(self._ctx, C.byref(io), C.byref(lio), self._stream()))
-        self._keep = keep + [Qd, Rd, Qfd]
-        return LqrGains(*out)
-
-    def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
-        """rollout_states under the feedback of rollout_lqr, the line search's forward pass: step k takes
-        a_k = float32(actions[k-1] + alpha d_k + K_k (x_{k-1} - rollout.x[k-2])), x_{k-1} the state of THIS rollout
-        before the step (step 1 has no deviation: both rollouts share the start).  The arithmetic is float64 and fixed:
-        one multiply and one add for alpha d, then per state slot in order a subtraction, a multiply and an add, one
-        rounding to float32.  `rollout` is the nominal rollout_states(actions, state) result, `gains` rollout_lqr's
-        (float64), alpha a float or [N] float64 (per env).  Returns (Rollout, actions_out [K,N,A] float32): the Rollout
-        is bit-identical to rollout_states(actions_out, state).  Asynchronous on the current stream; the tensors are
-        buffers of this env, overwritten by its next call with the same K (they are not rollout_states' buffers).  No
-        env state changes."""
-        self._check_open()
-        torch = _torch()
-        io, K, keep = self._rollout_io(actions, state)
-        n, ad, dev = self.num_envs, self.action_dim, self.device
-        xbar = getattr(rollout, "x", None)
-        Kg, d = getattr(gains, "K", None), getattr(gains, "d", None)
-        self._check_tape("rollout_states", (xbar, "rollout.x", (K, n, 12), torch.float64))
-        self._check_tape("rollout_lqr", (Kg, "gains.K", (K, n, ad, 12), torch.float64),
-                         (d, "gains.d", (K, n, ad), torch.float64))
-        if isinstance(alpha, torch.Tensor):
-            if tuple(alpha.shape) not in ((), (n,)) or not alpha.dtype.is_floating_point:
-                raise ValueError("alpha must be a float or a floating-point tensor of shape (%d,)" % n)
-            if alpha.device != dev and alpha.dim() == 1:
-                raise ValueError("alpha must be on %s, got %s" % (dev, alpha.device))
-            al = alpha.detach().to(device=dev, dtype=torch.float64).expand(n).contiguous()
-        else:
-            a = np.asarray(alpha, dtype=np.float64)
-            if a.shape not in ((), (n,)):
-                raise ValueError("alpha must be a float or have shape (%d,), got %s" % (n, a.shape))
-            al = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (n,)))).to(dev)
-        keep.append(al)
-        out = self._rollout_cache(("feedback", K), lambda: (Rollout(
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((K, n), dtype=torch.float64, device=dev),
-            torch.empty((K, n), dtype=torch.bool, device=dev),
-            torch.empty((K, n), dtype=torch.bool, device=dev),
-            torch.empty((K, n), dtype=torch.uint8, device=dev)),
-            torch.empty((K, n, ad), dtype=torch.float32, device=dev)))
-        ro, acts = out
-        io.x_dev, io.reward_dev, io.terminated_dev, io.truncated_dev, io.status_dev = (t.data_ptr() for t in ro)
-        fio = _lib.RolloutFeedbackIO()
-        fio.struct_size = C.sizeof(_lib.RolloutFeedbackIO)
-        fio.xbar_dev, fio.K_dev, fio.d_dev = xbar.data_ptr(), Kg.data_ptr(), d.data_ptr()
-        fio.alpha_dev, fio.actions_out_dev = al.data_ptr(), acts.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_feedback_states(self._ctx, C.byref(io), C.byref(fio), self._stream()))
-        self._keep = keep + [xbar, Kg, d]
-        return ro, acts
-
-    # -- the filter family (DESIGN sections 19 to 21): the model every env and step shares, and the start's status ----
-    def _filter_model(self, slot, given, check):
-        """The arrays a filter shares among every env and step -- `given`, the caller's (H, r, Q) or (Q,) -- checked on
-        the host and kept on the device: check() returns the float64 host arrays to upload (_host_array's, checked
-        further).  The same values are uploaded once (a streaming filter passes them with every chunk).
-        Host arrays are compared by value; device tensors are recognised by identity and version (the same, unmodified
-        tensors as in the last call cost no device-to-host copy), and checked on the host once when they are new.
-        `slot` names the calling entry point's cache."""
-        torch = _torch()
-        tensors = all(isinstance(m, torch.Tensor) for m in given)
-        ident = tuple((id(m), m._version, m.data_ptr()) for m in given) if tensors else None
-        caches = self.__dict__.setdefault("_filter_m", {})
-        cache = caches.get(slot)
-        if ident is not None and cache is not None and cache[2] == ident:
-            return cache[1]
-        model = [np.ascontiguousarray(a) for a in check()]
-        key = tuple(a.tobytes() for a in model)
-        if cache is None or cache[0] != key:
-            cache = (key, [torch.from_numpy(a).to(self.device) for a in model])
-        # (the caller's tensors are kept alive with their identity, so that an id cannot be reused by another tensor)
-        caches[slot] = (cache[0], cache[1], ident, given if tensors else None)
-        return cache[1]
-
-    def _kalman_model(self, slot, H, r, Q):
-        """(Hd, rd, Qd, M): the checked model of rollout_ekf, rollout_lqg and rollout_ukf on the device, from the
-        entry point's cache `slot`."""
-        Hd, rd, Qd = self._filter_model(slot, (H, r, Q), lambda: (
-            *self._measurement_model(H, r), self._process_noise(Q)))
-        return Hd, rd, Qd, int(Hd.shape[0])
-
-    def _kalman_tensors(self, K, n, dtype, tape):
-        """The ten result tensors those three have in common, in EkfResult's order: x, x_pred, P, var, nis, loglik,
-        status, the step's byte (branch or spread), ok, P_tape (None without tape)."""
-        torch = _torch()
-        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)      # noqa: E731
-        return (e((K, n, 12), torch.float64), e((K, n, 12), torch.float64), e((n, 12, 12), dtype), e((K, n, 12), dtype),
-                e((K, n), dtype), e(n, dtype), e((K, n), torch.uint8), e((K, n), torch.uint8), e(n, torch.bool),
-                e((K, n, 12, 12), dtype) if tape else None)
-
-    @staticmethod
-    def _kalman_wire(fio, dtype, model, P0, res):
-        """The fields cs_rollout_ekf_io, cs_rollout_lqg_io and cs_rollout_ukf_io share by name, into the block `fio`:
-        its size, dtype, the model (_kalman_model's), P0 and the outputs of `res` (an EkfResult or a UkfResult)."""
-        Hd, rd, Qd, M = model
-        fio.struct_size = C.sizeof(type(fio))
-        fio.out_dtype = _lib.JAC_F64 if dtype == _torch().float64 else _lib.JAC_F32
-        fio.num_meas = M
-        fio.H_dev, fio.r_dev, fio.Q_dev, fio.P0_dev = Hd.data_ptr(), rd.data_ptr(), Qd.data_ptr(), P0.data_ptr()
-        fio.x_pred_dev, fio.P_dev, fio.var_dev = res.x_pred.data_ptr(), res.P.data_ptr(), res.var.data_ptr()
-        fio.nis_dev, fio.loglik_dev, fio.ok_dev = res.nis.data_ptr(), res.loglik.data_ptr(), res.ok.data_ptr()
-        if res.P_tape is not None:
-            fio.P_tape_dev = res.P_tape.data_ptr()
-
-    @staticmethod
-    def _host_array(m, name):
-        """m, a tensor or an array of real numbers, as a finite float64 host array."""
-        a = np.asarray(m.detach().cpu() if isinstance(m, _torch().Tensor) else m)
-        if a.dtype.kind not in "fiu":
-            raise ValueError("%s must be a real floating-point array, got dtype %s" % (name, a.dtype))
-        a = np.ascontiguousarray(a, dtype=np.float64)
-        if not np.isfinite(a).all():
-            raise ValueError("%s must be finite" % name)
-        return a
-
-    def _measurement_model(self, H, r):
-        """H [M,12] (1 <= M <= 12) and r [M] > 0 of rollout_ekf and rollout_pf, on the host."""
-        h = self._host_array(H, "H")
-        if h.ndim != 2 or h.shape[1] != 12 or not 1 <= h.shape[0] <= _lib.EKF_MAX_MEAS:
-            raise ValueError("H must have shape (M, 12) with 1 <= M <= %d, got %s" % (_lib.EKF_MAX_MEAS, h.shape))
-        rv = self._host_array(r, "r")
-        if rv.shape != (h.shape[0],):
-            raise ValueError("r must have shape (%d,) (one variance per row of H), got %s" % (h.shape[0], rv.shape))
-        if not (rv > 0).all():
-            raise ValueError("r must be positive: the measurement variances")
-        return h, rv
-
-    def _process_noise(self, Q):
-        """Q [12,12] symmetric of rollout_ekf and rollout_rts, on the host."""
-        q = self._host_array(Q, "Q")
-        if q.shape != (12, 12):
-            raise ValueError("Q must have shape (12, 12), got %s" % (q.shape,))
-        if not np.array_equal(q, q.T):
-            raise ValueError("Q must be symmetric")
-        return q
-
-    def _start_status(self, io, status0, keep):
-        """io.start_status_dev of a filter's start: the caller's status0 [N] uint8, AIRBORNE by default."""
-        torch = _torch()
-        n = self.num_envs
-        if status0 is None:
-            st = torch.full((n,), _lib.STATUS_AIRBORNE, dtype=torch.uint8, device=self.device)
-            keep.append(st)
-            io.start_status_dev = st.data_ptr()
-        else:
-            io.start_status_dev = self._state_dev(status0, (n,), torch.uint8, "status0", keep)
-
-    # -- the extended Kalman filter over the env step (DESIGN section 19) --------
-    def _ekf_input(self, v, shape, name, keep):
-        """A per-env input of rollout_ekf as a contiguous float64 device tensor, kept alive in `keep`: a floating-point
-        tensor on this env's device, or a host array."""
-        torch = _torch()
-        if isinstance(v, torch.Tensor):
-            if tuple(v.shape) != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, tuple(v.shape)))
-            if not v.dtype.is_floating_point:
-                raise ValueError("%s must be a floating-point tensor, got %s" % (name, v.dtype))
-            if v.device != self.device:
-                raise ValueError("%s must be on %s, got %s" % (name, self.device, v.device))
-            t = v.detach().to(torch.float64).contiguous()
-        else:
-            a = np.asarray(v)
-            if a.shape != shape:
-                raise ValueError("%s must have shape %s, got %s" % (name, shape, a.shape))
-            if a.dtype.kind != "f":
-                raise ValueError("%s must be a floating-point array, got dtype %s" % (name, a.dtype))
-            t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.device)
-        keep.append(t)
-        return t
-
-    def rollout_ekf(self, actions, z, H, r, Q, x0, P0, status0=None, tape=False, dtype=None):
-        """An extended Kalman filter over the env step, K predict / update steps per env in one kernel: the mean goes
-        through the step's own physics, the covariance through the step Jacobian of step_jacobian (every branch rule of
-        DESIGN section 9), applied on the fly and never stored.  The filter's state is the caller's: NO env state is read
-        but the configuration and the vehicle, and none changes.
-
-        actions [K,N,A]: step k takes actions[k-1].  z [K,N,M] float64: the measurements z = H x + e, e ~ N(0, diag(r));
-        a NaN entry means "no measurement" and its update is skipped.  H [M,12] (1 <= M <= 12), r [M] > 0 and Q [12,12]
-        symmetric PSD (the process noise added per step) are shared by every env and step.  x0 [12,N] float64 and
-        P0 [N,12,12] (symmetric: its upper triangle is read) are the mean and covariance before step 1; status0 [N] uint8
-        the flight status of that mean (default AIRBORNE).
-
-        Per step: x- = the physics from (xhat, status), P- = A P A^T + Q; then for each row i of H in order, skipping NaN
-        z: p = P h, s = h^T p + r_i, nu = z_i - h^T x, x += (p / s) nu, P -= (p / s) p^T.
-
-        Returns EkfResult(x [K,N,12] the filtered means, x_pred [K,N,12] the priors, P [N,12,12] the last posterior, var
-        [K,N,12] the posteriors' diagonals, nis [K,N] the steps' sums of nu^2 / s, loglik [N] the sum of
-        -1/2 (nu^2 / s + ln(2 pi s)), status [K,N] and branch [K,N] (step_jacobian's bits) of the filter's own mean, ok
-        [N] bool (False where some s was not finite or <= 0), P_tape [K,N,12,12] with tape=True, else None).  dtype:
-        torch.float64 (default) or torch.float32 (P, var, nis, loglik, P_tape: the float64 values rounded).  Not available
-        under action_arith="float32".  Asynchronous on the current stream; the tensors are buffers of this env,
-        overwritten by its next call with the same K, dtype and tape."""
-        self._check_open()
-        torch = _torch()
-        dtype = self._out_dtype(dtype)
-        model = self._kalman_model("ekf", H, r, Q)
-        M = model[3]
-        io, K, keep = self._rollout_io(actions, None)
-        n = self.num_envs
-        zt = self._ekf_input(z, (K, n, M), "z", keep)
-        xt = self._ekf_input(x0, (12, n), "x0", keep)
-        Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
-        self._start_status(io, status0, keep)
-        io.start_x_dev = xt.data_ptr()
-        tape = bool(tape)
-        out = self._rollout_cache(("ekf", K, dtype, tape), lambda: EkfResult(*self._kalman_tensors(K, n, dtype, tape)))
-        eio = _lib.RolloutEkfIO()
-        self._kalman_wire(eio, dtype, model, Pt, out)
-        eio.z_dev, eio.branch_dev = zt.data_ptr(), out.branch.data_ptr()
-        io.x_dev, io.status_dev = out.x.data_ptr(), out.status.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_ekf(self._ctx, C.byref(io), C.byref(eio), self._stream()))
-        self._keep = keep + list(model[:3])
-        return out
-
-    # -- the bootstrap particle filter over the env step (DESIGN section 21): its host side lives with its streaming
-    #    driver in pf.py and is bound here.  (The list of guarded entry points in tests/test_gpu_output_bounds.py is
-    #    read from this class's `def`s; rollout_pf's guarded-output test is in tests/test_gpu_rollout_pf.py.) --------
+    # -- the rollout families: each lives next to its driver, on the host kit of _wire.py, and is bound here -----------
+    step_jacobian = _rollouts.step_jacobian
+    _rollout_io = _rollouts._rollout_io
+    rollout_states = _rollouts.rollout_states
+    rollout_vjp = _rollouts.rollout_vjp
+    rollout_vjp_params = _rollouts.rollout_vjp_params
+    _mlp_io = _mlp_rollout._mlp_io
+    rollout_mlp_states = _mlp_rollout.rollout_mlp_states
+    rollout_mlp_vjp = _mlp_rollout.rollout_mlp_vjp
+    mlp_param_grad = _mlp_rollout.mlp_param_grad
+    rollout_lqr = _ilqr.rollout_lqr
+    rollout_feedback_states = _ilqr.rollout_feedback_states
+    rollout_mppi_costs = _mppi.rollout_mppi_costs
+    rollout_mppi_update = _mppi.rollout_mppi_update
+    rollout_mppi_temperature = _mppi.rollout_mppi_temperature
+    rollout_mlp_population = _es.rollout_mlp_population
+    es_perturb = _es.es_perturb
+    es_gradient = _es.es_gradient
+    rollout_actor_critic = _ppo.rollout_actor_critic
+    gae = _ppo.gae
+    ppo_grad = _ppo.ppo_grad
+    rollout_ekf = _ekf.rollout_ekf
+    rollout_rts = _ekf.rollout_rts
     rollout_pf = _pf.rollout_pf
-
-    # -- output-feedback rollouts, the feedback law on the filter's estimate (DESIGN section 22): the host side lives with
-    #    its driver in lqg.py and is bound here, as rollout_pf is; its guarded-output test is
-    #    tests/test_gpu_lqg_output_bounds.py --------
     rollout_lqg = _lqg.rollout_lqg
-
-    # -- the unscented Kalman filter over the env step (DESIGN section 23): the host side lives with its streaming driver
-    #    in ukf.py and is bound here, as rollout_pf is; its guarded-output test is
-    #    tests/test_gpu_ukf_output_bounds.py --------
     rollout_ukf = _ukf.rollout_ukf
 
-    # -- the Rauch-Tung-Striebel smoother over the filter's tapes (DESIGN section 20) --------
-    def rollout_rts(self, actions, filt, Q, x0, P0, status0=None, end=None, tape=True, dtype=None):
-        """A Rauch-Tung-Striebel fixed-interval smoother over the tapes of rollout_ekf, K backward steps per env in one
-        kernel: the estimate of every step given the measurements of all K steps, and that of the starting point.  The
-        step Jacobian is applied on the fly at the filter's own points and never stored.  NO env state is read but the
-        configuration and the vehicle, and none changes.
-
-        actions [K,N,A], Q, x0 [12,N], P0 [N,12,12] and status0 are what the filter was given; filt is its EkfResult
-        from rollout_ekf(..., tape=True) in float64 (x, x_pred, status and P_tape are read).  Q should be positive
-        definite: a merely PSD Q can make a prior singular, which clears ok.  end = (x_end [12,N], P_end [N,12,12])
-        gives the smoothed last row (default: the filter's own last row) -- the smoothed starting point of the chunk that
-        follows, for a tape smoothed in chunks (gym_copter_amd.smooth).
-
-        Row K-1 is the given one; then for j = K-2 down to -1 (row -1 is the starting point), with A the step Jacobian at
-        (x_f[j], status_f[j]) under actions[j+1]:  P- = A P_f[j] A^T + Q (the filter's prior, bit for bit),
-        G = P-^-1 A P_f[j] by Cholesky,  x_s[j] = x_f[j] + G^T (x_s[j+1] - x_pred[j+1]),
-        P_s[j] = P_f[j] + G^T (P_s[j+1] - P-) G.
-
-        Returns RtsResult(x [K,N,12] the smoothed means, P_tape [K,N,12,12] their covariances (None with tape=False),
-        var [K,N,12] the covariances' diagonals, x0 [12,N] and P0 [N,12,12] the smoothed starting point, ok [N] bool
-        (False where a Cholesky pivot was <= 0 or not finite; the outputs are written regardless)).  dtype: torch.float64
-        (default) or torch.float32 (P_tape, var, P0: the float64 values rounded).  Not available under
-        action_arith="float32".  Asynchronous on the current stream; the tensors are buffers of this env, overwritten by
-        its next call with the same K, dtype and tape."""
-        self._check_open()
-        torch = _torch()
-        dtype = self._out_dtype(dtype)
-        if self.config.action_arith != _ARITH["float64"]:
-            raise ValueError('rollout_rts is not available under action_arith="float32"')
-        Qd, = self._filter_model("rts", (Q,), lambda: (self._process_noise(Q),))
-        io, K, keep = self._rollout_io(actions, None)
-        n, dev = self.num_envs, self.device
-        if not isinstance(filt, EkfResult):
-            raise ValueError("filt must be the EkfResult of rollout_ekf(..., tape=True)")
-        if filt.P_tape is None:
-            raise ValueError("filt has no P_tape: filter with rollout_ekf(..., tape=True)")
-        if isinstance(filt.P_tape, torch.Tensor) and filt.P_tape.dtype != torch.float64:
-            raise ValueError("filt.P_tape must be float64 (rollout_ekf's default dtype), got %s" % filt.P_tape.dtype)
-        self._check_tape("rollout_ekf", (filt.x, "filt.x", (K, n, 12), torch.float64),
-                         (filt.x_pred, "filt.x_pred", (K, n, 12), torch.float64),
-                         (filt.status, "filt.status", (K, n), torch.uint8),
-                         (filt.P_tape, "filt.P_tape", (K, n, 12, 12), torch.float64))
-        xt = self._ekf_input(x0, (12, n), "x0", keep)
-        Pt = self._ekf_input(P0, (n, 12, 12), "P0", keep)
-        self._start_status(io, status0, keep)
-        io.start_x_dev = xt.data_ptr()
-        rio = _lib.RolloutRtsIO()
-        rio.struct_size = C.sizeof(_lib.RolloutRtsIO)
-        rio.out_dtype = _lib.JAC_F64 if dtype == torch.float64 else _lib.JAC_F32
-        if end is not None:
-            if not isinstance(end, (tuple, list)) or len(end) != 2 or end[0] is None or end[1] is None:
-                raise ValueError("end must be the pair (x_end [12,N], P_end [N,12,12]): both or neither")
-            rio.end_x_dev = self._ekf_input(end[0], (12, n), "end[0]", keep).data_ptr()
-            rio.end_P_dev = self._ekf_input(end[1], (n, 12, 12), "end[1]", keep).data_ptr()
-        rio.x_f_dev, rio.x_pred_dev = filt.x.data_ptr(), filt.x_pred.data_ptr()
-        rio.status_f_dev, rio.P_f_dev = filt.status.data_ptr(), filt.P_tape.data_ptr()
-        rio.Q_dev, rio.P0_dev = Qd.data_ptr(), Pt.data_ptr()
-        tape = bool(tape)
-        out = self._rollout_cache(("rts", K, dtype, tape), lambda: RtsResult(
-            torch.empty((K, n, 12), dtype=torch.float64, device=dev),
-            torch.empty((K, n, 12, 12), dtype=dtype, device=dev) if tape else None,
-            torch.empty((K, n, 12), dtype=dtype, device=dev), torch.empty((12, n), dtype=torch.float64, device=dev),
-            torch.empty((n, 12, 12), dtype=dtype, device=dev), torch.empty(n, dtype=torch.bool, device=dev)))
-        # (no output may overlap an input: the caller's tensors that are this call's own buffers are copied first)
-        mine = {t.data_ptr() for t in out if t is not None}
-        for name in ("end_x_dev", "end_P_dev", "P0_dev"):
-            if getattr(rio, name) in mine:
-                src = next(t for t in keep if t.data_ptr() == getattr(rio, name))
-                cp = src.clone()
-                keep.append(cp)
-                setattr(rio, name, cp.data_ptr())
-        if io.start_x_dev in mine:
-            cp = xt.clone()
-            keep.append(cp)
-            io.start_x_dev = cp.data_ptr()
-        io.x_dev = out.x.data_ptr()
-        rio.var_dev, rio.x0_dev, rio.P0_s_dev = out.var.data_ptr(), out.x0.data_ptr(), out.P0.data_ptr()
-        rio.ok_dev = out.ok.data_ptr()
-        if tape:
-            rio.P_tape_dev = out.P_tape.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_rts(self._ctx, C.byref(io), C.byref(rio), self._stream()))
-        self._keep = keep + [Qd, filt.x, filt.x_pred, filt.status, filt.P_tape]
-        return out
-
-    # -- MPPI: sampled rollouts, their costs and the weighted update (DESIGN section 14) --------
-    def _mppi_small(self, v, name, dtype, nonneg):
-        """sigma / a_ref: a scalar or [A] values, checked on the host and kept on the device: the same values are
-        uploaded once (the MPPI driver passes them every iteration)."""
-        torch = _torch()
-        ad = self.action_dim
-        a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
-        if a.shape not in ((), (ad,)):
-            raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (name, ad, a.shape))
-        a = np.ascontiguousarray(np.broadcast_to(a, (ad,))).astype(dtype)
-        if not np.isfinite(a).all() or (nonneg and not (a >= 0).all()):
-            raise ValueError("%s must be finite%s" % (name, " and >= 0" if nonneg else ""))
-        cache = getattr(self, "_mppi_c", None)
-        if cache is None:
-            cache = self._mppi_c = {}
-        hit = cache.get(name)
-        if hit is None or hit[0] != a.tobytes():
-            hit = cache[name] = (a.tobytes(), torch.from_numpy(a).to(self.device))
-        return hit[1]
-
-    @staticmethod
-    def _mppi_stream(stream):
-        if not isinstance(stream, (int, np.integer)) or isinstance(stream, bool) or not 0 <= int(stream) < 1 << 32:
-            raise ValueError("stream must be an int in [0, 2**32), got %r" % (stream,))
-        return int(stream)
-
-    def _mppi_knots(self, knots, K):
-        """knots=(knot [K], w [K,2]) (mppi_knots' layout), checked on the host and kept on the device: the same table is
-        uploaded once.  Returns the two device tensors."""
-        torch = _torch()
-        try:
-            knot, w = knots
-            knot = np.asarray(knot.detach().cpu() if isinstance(knot, torch.Tensor) else knot)
-            w = np.asarray(w.detach().cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float64)
-        except (TypeError, ValueError):
-            raise ValueError("knots must be a pair (knot [K], w [K,2]) as mppi_knots returns it") from None
-        if knot.shape != (K,) or knot.dtype.kind not in "iu" or w.shape != (K, 2):
-            raise ValueError("knots must be (knot: %d integers, w: shape (%d, 2)), got shapes %s and %s"
-                             % (K, K, knot.shape, w.shape))
-        if int(knot.min()) < 1 or int(knot.max()) + 1 > MPPI_MAX_KNOT:
-            raise ValueError("knot numbers must lie in [1, %d]" % (MPPI_MAX_KNOT - 1))
-        w = np.ascontiguousarray(w.astype(np.float32))
-        if not np.isfinite(w).all():
-            raise ValueError("knot weights must be finite")
-        knot = np.ascontiguousarray(knot.astype(np.uint32))
-        cache = getattr(self, "_mppi_c", None)
-        if cache is None:
-            cache = self._mppi_c = {}
-        tag = knot.tobytes() + w.tobytes()
-        hit = cache.get("knots")
-        if hit is None or hit[0] != tag:
-            # (int32 on the device: the same 32 bits; knot numbers are far below 2^31)
-            hit = cache["knots"] = (tag, torch.from_numpy(knot.view(np.int32)).to(self.device),
-                                    torch.from_numpy(w).to(self.device))
-        return hit[1], hit[2]
-
-    def _mppi_ext(self, knots, K):
-        """(cs_rollout_mppi_ext with the knot table filled in, the tensors it points to)."""
-        ext = _lib.RolloutMppiExt()
-        ext.struct_size = C.sizeof(_lib.RolloutMppiExt)
-        keep = []
-        if knots is not None:
-            kn, kw = self._mppi_knots(knots, K)
-            ext.knot_dev, ext.knot_weights_dev = kn.data_ptr(), kw.data_ptr()
-            keep = [kn, kw]
-        return ext, keep
-
-    def rollout_mppi_costs(self, actions, sigma, samples, x_ref, Q, R, Q_final=None, a_ref=None, reward_weight=0.0,
-                           stream=0, state=None, knots=None):
-        """The costs of P = `samples` noisy copies of the action tape `actions` [K,N,A] per env, one kernel: sample p
-        takes a_k = actions[k-1] + sigma * eps(p, k) in float32 (one multiply, one add), eps the library's counter-based
-        noise -- Irwin-Hall of order 4, mean 0, variance 1 - 2**-32, a pure function of (seed, global env id, `stream`,
-        k, p, component): tests/mppi_ref.py restates it in NumPy bit for bit -- and sample 0 is `actions` itself.  Each
-        copy is rolled out as rollout_states would (same start rules: state=None or get_state()'s layout; the step clips
-        the motors itself) and scored in float64, in registers:
-
-            S = sum_k 1/2 (x_k - x_ref)^T Q_k (x_k - x_ref) + 1/2 (a_k - a_ref)^T R (a_k - a_ref) - reward_weight reward_k
-
-        with Q_K = Q_final when given.  sigma: a scalar or [A], >= 0; x_ref: [12], [N,12] or [K,N,12]; Q [12,12] and
-        R [A,A] symmetric positive semidefinite, shared; a_ref [A] or None (zero); reward_weight >= 0 brings in the
-        task's own reward (rollout_states' float64 reward); `stream` is a nonce in [0, 2**32), for example the MPC
-        iteration.  No state tape and no noise tensor exist.
-
-        knots=(knot [K], w [K,2]) (mppi_knots(K, hold)) makes the noise smooth: step k takes
-        eps~ = float32(float32(w[k][0] eps(p, knot[k])) + float32(w[k][1] eps(p, knot[k] + 1))) in place of eps(p, k) --
-        tests/mppi_smooth_ref.py restates it bit for bit; None, or the white table mppi_knots(K, 1), is the noise above.
-
-        Returns MppiCosts(costs [P,N] float64, best [N] int32: the arg-min over the env's finite costs, the lowest index
-        on ties, -1 if none is finite).  Asynchronous on the current stream; the tensors are buffers of this env,
-        overwritten by its next call with the same P.  No env state changes."""
-        self._check_open()
-        torch = _torch()
-        if not isinstance(samples, (int, np.integer)) or isinstance(samples, bool) \
-                or not 1 <= int(samples) <= _lib.MPPI_MAX_SAMPLES:
-            raise ValueError("samples must be an int in [1, %d], got %r" % (_lib.MPPI_MAX_SAMPLES, samples))
-        P = int(samples)
-        wr = float(reward_weight)
-        if not (wr >= 0.0) or wr == float("inf"):
-            raise ValueError("reward_weight must be finite and >= 0, got %r" % (reward_weight,))
-        Qd, Rd, Qfd = self._lqr_weights(Q, R, Q_final, definite=False)
-        sg = self._mppi_small(sigma, "sigma", np.float32, True)
-        ar = None if a_ref is None else self._mppi_small(a_ref, "a_ref", np.float64, False)
-        io, K, keep = self._rollout_io(actions, state)
-        n, dev = self.num_envs, self.device
-        xr = x_ref if isinstance(x_ref, torch.Tensor) else torch.from_numpy(np.asarray(x_ref, dtype=np.float64))
-        if tuple(xr.shape) == (12,):
-            xr = xr.expand(n, 12)
-        if tuple(xr.shape) not in ((n, 12), (K, n, 12)) or not xr.dtype.is_floating_point:
-            raise ValueError("x_ref must be a floating-point array of shape (12,), (%d, 12) or (%d, %d, 12), got %s"
-                             % (n, K, n, tuple(xr.shape)))
-        xr = xr.detach().to(device=dev, dtype=torch.float64).contiguous()
-        keep.append(xr)
-        mio = _lib.RolloutMppiIO()
-        mio.struct_size = C.sizeof(_lib.RolloutMppiIO)
-        mio.num_samples, mio.noise_stream = P, self._mppi_stream(stream)
-        mio.x_ref_steps = 1 if xr.dim() == 3 else 0
-        mio.reward_weight = wr
-        mio.sigma_dev, mio.x_ref_dev = sg.data_ptr(), xr.data_ptr()
-        mio.a_ref_dev = None if ar is None else ar.data_ptr()
-        mio.Q_dev, mio.R_dev = Qd.data_ptr(), Rd.data_ptr()
-        mio.Q_final_dev = None if Qfd is None else Qfd.data_ptr()
-        out = self._rollout_cache(("mppi_costs", P), lambda: MppiCosts(
-            torch.empty((P, n), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)))
-        mio.costs_dev, mio.best_dev = out.costs.data_ptr(), out.best.data_ptr()
-        ext, kept = (None, []) if knots is None else self._mppi_ext(knots, K)
-        with torch.cuda.device(self.device):
-            if ext is None:
-                _lib.check(self._lib.cs_rollout_mppi_costs(self._ctx, C.byref(io), C.byref(mio), self._stream()))
-            else:
-                _lib.check(self._lib.cs_rollout_mppi_costs_ex(self._ctx, C.byref(io), C.byref(mio), C.byref(ext),
-                                                              self._stream()))
-        self._keep = keep + [Qd, Rd, Qfd, sg, ar] + kept
-        return out
-
-    def rollout_mppi_update(self, actions, costs, sigma, lam, stream=0, knots=None):
-        """The MPPI update, one kernel: per env, with beta = its minimum finite cost, w_p = exp(-(costs[p] - beta) / lam)
-        (0 for a cost that is not finite) and eta = sum_p w_p,
-
-            actions_out[k-1] = clip01(float32(actions[k-1] + (1 / eta) sum_p w_p sigma eps(p, k)))
-
-        in float64 with p ascending, eps drawn again from the counter: `costs` [P,N] float64 is what
-        rollout_mppi_costs(actions, sigma, P, ..., stream=stream) returned for the same actions, sigma and stream.
-        lam > 0 is the temperature: a scalar, or an [N] float64 device tensor with one temperature per env
-        (rollout_mppi_temperature's); an env whose entry is not finite and > 0 keeps its actions and reports ess = 0.
-        knots: the table rollout_mppi_costs was given.  Returns MppiUpdate(actions [K,N,A] float32, ess [N] float64 = eta^2 / sum_p w_p^2:
-        the effective sample size, cost_min [N] = beta).  An env without a finite cost keeps its actions (the same
-        bits) and reports ess = 0, cost_min = inf.  Every sum runs inside one lane in a fixed order: two calls give the
-        same bits.  Asynchronous on the current stream; the tensors are buffers of this env (two sets, so that the
-        result of one call can be the `actions` of the next), overwritten by its second next call with the same K.  No
-        env state changes."""
-        self._check_open()
-        torch = _torch()
-        lam_t = lam if isinstance(lam, torch.Tensor) and lam.dim() > 0 else None
-        if lam_t is None:
-            lam = float(lam)
-            if not (lam > 0.0) or lam == float("inf"):
-                raise ValueError("lam must be finite and > 0, got %r" % (lam,))
-        sg = self._mppi_small(sigma, "sigma", np.float32, True)
-        io, K, keep = self._rollout_io(actions, None)
-        n, ad, dev = self.num_envs, self.action_dim, self.device
-        if lam_t is not None:
-            self._check_tape("rollout_mppi_update", (lam_t, "lam", (n,), torch.float64))
-        if not isinstance(costs, torch.Tensor) or costs.dim() != 2 or not 1 <= costs.shape[0] <= _lib.MPPI_MAX_SAMPLES:
-            raise ValueError("costs must be the [P,%d] float64 device tensor of rollout_mppi_costs" % n)
-        P = int(costs.shape[0])
-        self._check_tape("rollout_mppi_costs", (costs, "costs", (P, n), torch.float64))
-        sets = self._rollout_cache(("mppi_update", K), lambda: [MppiUpdate(
-            torch.empty((K, n, ad), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
-            torch.empty(n, dtype=torch.float64, device=dev)) for _ in range(2)])
-        out = sets[1] if sets[0].actions.data_ptr() == io.actions_dev else sets[0]
-        mio = _lib.RolloutMppiIO()
-        mio.struct_size = C.sizeof(_lib.RolloutMppiIO)
-        mio.num_samples, mio.noise_stream = P, self._mppi_stream(stream)
-        mio.lam = 0.0 if lam_t is not None else lam
-        mio.sigma_dev, mio.costs_dev = sg.data_ptr(), costs.data_ptr()
-        mio.actions_out_dev, mio.ess_dev, mio.cost_min_dev = (t.data_ptr() for t in out)
-        ext, kept = (None, []) if knots is None and lam_t is None else self._mppi_ext(knots, K)
-        if lam_t is not None:
-            ext.lam_dev = lam_t.data_ptr()
-        with torch.cuda.device(self.device):
-            if ext is None:
-                _lib.check(self._lib.cs_rollout_mppi_update(self._ctx, C.byref(io), C.byref(mio), self._stream()))
-            else:
-                _lib.check(self._lib.cs_rollout_mppi_update_ex(self._ctx, C.byref(io), C.byref(mio), C.byref(ext),
-                                                               self._stream()))
-        self._keep = keep + [sg, costs, lam_t] + kept
-        return out
-
-    def rollout_mppi_temperature(self, costs, ess_target, lam_min=1e-6, lam_max=1e6):
-        """The temperature per env at which the MPPI weights of `costs` [P,N] (rollout_mppi_costs') have the effective
-        sample size ess_target, one kernel: with E(lam) = (sum_p w_p)^2 / sum_p w_p^2 over the env's finite costs, 48
-        bisections of ln lam between ln lam_min and ln lam_max, keeping E >= ess_target at the upper end; lam_max where
-        even E(lam_max) < ess_target, lam_min where E(lam_min) >= ess_target, lam_max (and ess 0) for an env without a
-        finite cost.  ess_target >= 1, 0 < lam_min < lam_max.  Returns MppiTemperature(lam [N] float64, for
-        rollout_mppi_update(lam=), ess [N] float64 = E(lam)).  Two calls give the same bits.  Asynchronous on the
-        current stream; the tensors are buffers of this env, overwritten by its next call.  No env state changes."""
-        self._check_open()
-        torch = _torch()
-        n, dev = self.num_envs, self.device
-        target, lo, hi = float(ess_target), float(lam_min), float(lam_max)
-        if not (target >= 1.0) or target == float("inf"):
-            raise ValueError("ess_target must be finite and >= 1, got %r" % (ess_target,))
-        if not (0.0 < lo < hi) or hi == float("inf"):
-            raise ValueError("0 < lam_min < lam_max, both finite, is required, got %r and %r" % (lam_min, lam_max))
-        if not isinstance(costs, torch.Tensor) or costs.dim() != 2 or not 1 <= costs.shape[0] <= _lib.MPPI_MAX_SAMPLES:
-            raise ValueError("costs must be the [P,%d] float64 device tensor of rollout_mppi_costs" % n)
-        P = int(costs.shape[0])
-        self._check_tape("rollout_mppi_costs", (costs, "costs", (P, n), torch.float64))
-        out = self._rollout_cache(("mppi_temperature",), lambda: MppiTemperature(
-            torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)))
-        mio = _lib.RolloutMppiIO()
-        mio.struct_size = C.sizeof(_lib.RolloutMppiIO)
-        mio.num_samples, mio.costs_dev = P, costs.data_ptr()
-        ext = _lib.RolloutMppiExt()
-        ext.struct_size = C.sizeof(_lib.RolloutMppiExt)
-        ext.ess_target, ext.lam_min, ext.lam_max = target, lo, hi
-        ext.lam_out_dev, ext.ess_out_dev = out.lam.data_ptr(), out.ess.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_mppi_temperature(self._ctx, C.byref(mio), C.byref(ext), self._stream()))
-        self._keep = [costs]
-        return out
-
-    # -- population rollouts and evolution strategies (DESIGN section 16) ---------------------
-    @staticmethod
-    def _es_u32(v, name):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 1 << 32:
-            raise ValueError("%s must be an int in [0, 2**32), got %r" % (name, v))
-        return int(v)
-
-    def rollout_mlp_population(self, table, K, hidden, envs_per_member, gamma=1.0, start_x=None, start_status=None,
-                               state=None):
-        """M = table.shape[0] policies, each rolled out closed-loop for K steps on its own E = envs_per_member envs and
-        scored by its episode return, one kernel and no tape: env i runs under theta = table[i // E] ([M,P] float32,
-        every row in gym_copter_amd.mlp's layout for `hidden`); N = M E, E a multiple of 64.  With the outputs
-        rollout_mlp_states(table[m], K, hidden) gives for the same start, and d the first step at which an env is
-        terminated or truncated (K if none):
-
-            returns[i] = sum_{k=1..d} gamma^(k-1) reward_k   (float64, k ascending, the discount a running product)
-            lengths[i] = d,  end_flags[i] = terminated_d | truncated_d << 1,  end_status[i] = status_d
-
-        exactly (the policy's float32 arithmetic and the step are rollout_mlp_states'), and member_returns[m] = the mean
-        of returns over the member's envs, summed in a fixed order (the same bits on every call).  The start is
-        rollout_mlp_states': the stored state (its pending perturbation; a pending NEXT_STEP reset is performed in step
-        1), or an explicit one -- start_x [12,N] float64 with start_status [N] (None: all airborne), or `state`,
-        get_state()'s layout.  With stored starts the members see different envs; give every member the same E start
-        points for common random numbers (gym_copter_amd.es does).
-
-        Returns Population(returns [N] float64, lengths [N] int32, end_flags [N] uint8, end_status [N] uint8,
-        member_returns [M] float64).  Asynchronous on the current stream; the tensors are buffers of this env,
-        overwritten by its next call with the same M.  No env state changes."""
-        self._check_open()
-        torch = _torch()
-        n, dev = self.num_envs, self.device
-        if not isinstance(K, (int, np.integer)) or isinstance(K, bool) or K < 1:
-            raise ValueError("K must be an int >= 1, got %r" % (K,))
-        P = _mlp.num_params(self.obs_dim, self.action_dim, hidden)    # (checks hidden)
-        if not isinstance(envs_per_member, (int, np.integer)) or isinstance(envs_per_member, bool) \
-                or envs_per_member < 64 or envs_per_member % 64:
-            raise ValueError("envs_per_member must be a positive multiple of 64, got %r" % (envs_per_member,))
-        E = int(envs_per_member)
-        if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or table.dim() != 2 \
-                or table.shape[1] != P or table.shape[0] < 1:
-            raise ValueError("table must be a [M,%d] float32 torch tensor (one gym_copter_amd.mlp vector of hidden %d per "
-                             "member), got %s" % (P, hidden, getattr(table, "shape", type(table).__name__)))
-        M = int(table.shape[0])
-        if M * E != n:
-            raise ValueError("members x envs_per_member = %d x %d is not num_envs = %d" % (M, E, n))
-        g = float(gamma)
-        if not np.isfinite(g):
-            raise ValueError("gamma must be finite, got %r" % (gamma,))
-        if start_x is not None:
-            if state is not None:
-                raise ValueError("give start_x (with start_status) or state, not both")
-            state = {"x": start_x,
-                     "status": np.full(n, _lib.STATUS_AIRBORNE, np.uint8) if start_status is None else start_status}
-        elif start_status is not None:
-            raise ValueError("start_status describes an explicit start: start_x is required")
-        tb = table.detach().to(dev).contiguous()
-        io, K, keep = self._rollout_io(None, state, int(K))
-        out = self._rollout_cache(("population", M), lambda: Population(
-            torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-            torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev),
-            torch.empty(M, dtype=torch.float64, device=dev)))
-        pio = _lib.RolloutPopulationIO()
-        pio.struct_size = C.sizeof(_lib.RolloutPopulationIO)
-        pio.hidden, pio.members, pio.envs_per_member, pio.gamma = hidden, M, E, g
-        pio.params_table_dev = tb.data_ptr()
-        pio.returns_dev, pio.lengths_dev, pio.end_flags_dev, pio.end_status_dev, pio.member_returns_dev = (
-            t.data_ptr() for t in out)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_mlp_population(self._ctx, C.byref(io), C.byref(pio), self._stream()))
-        self._keep = keep + [tb]
-        return out
-
-    def _es_io(self, members, num_params, nonce, pair_base):
-        if not isinstance(members, (int, np.integer)) or isinstance(members, bool) \
-                or not 2 <= int(members) <= _lib.ES_MAX_MEMBERS or int(members) % 2:
-            raise ValueError("members must be an even int in [2, %d], got %r" % (_lib.ES_MAX_MEMBERS, members))
-        if not isinstance(num_params, (int, np.integer)) or isinstance(num_params, bool) \
-                or not 1 <= int(num_params) <= _lib.ES_MAX_PARAMS:
-            raise ValueError("num_params must be an int in [1, %d], got %r" % (_lib.ES_MAX_PARAMS, num_params))
-        eio = _lib.EsIO()
-        eio.struct_size = C.sizeof(_lib.EsIO)
-        eio.members, eio.num_params = int(members), int(num_params)
-        eio.noise_stream, eio.pair_base = self._es_u32(nonce, "nonce"), self._es_u32(pair_base, "pair_base")
-        return eio
-
-    def es_perturb(self, params, sigma, members, nonce, pair_base=0):
-        """The mirrored population of an evolution strategy around the centre `params` ([P] float32), one kernel:
-
-            table[2i] = float32(params + float32(sigma eps_i)),   table[2i+1] = float32(params - float32(sigma eps_i))
-
-        for the pairs i = 0 .. members/2 - 1, eps_i [P] the library's counter-based noise -- Irwin-Hall of order 4, mean
-        0, variance 1 - 2**-32, a pure function of (seed, `nonce`, the global pair index pair_base + i, the parameter
-        index): tests/es_ref.py restates it in NumPy bit for bit.  sigma >= 0; members even; nonce and pair_base in
-        [0, 2**32) (pair_base: where this call's pairs sit in a population split over several calls or devices).
-        Returns table [members,P] float32, a buffer of this env overwritten by its next call with the same shape.
-        Asynchronous on the current stream."""
-        self._check_open()
-        torch = _torch()
-        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.dim() != 1:
-            raise ValueError("params must be a 1-D float32 torch tensor, got %s"
-                             % (getattr(params, "dtype", type(params).__name__),))
-        sg = float(sigma)
-        if not (sg >= 0.0) or sg == float("inf"):
-            raise ValueError("sigma must be finite and >= 0, got %r" % (sigma,))
-        eio = self._es_io(members, int(params.shape[0]), nonce, pair_base)
-        th = params.detach().to(self.device).contiguous()
-        table = self._rollout_cache(("es_table", eio.members, eio.num_params), lambda: torch.empty(
-            (eio.members, eio.num_params), dtype=torch.float32, device=self.device))
-        eio.sigma, eio.params_dev, eio.table_dev = sg, th.data_ptr(), table.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_es_perturb(self._ctx, C.byref(eio), self._stream()))
-        self._keep = [th]
-        return table
-
-    def es_gradient(self, weights, nonce, num_params, pair_base=0):
-        """The search gradient of an evolution strategy, g[p] = sum_i (weights[2i] - weights[2i+1]) eps_i[p] in float64,
-        two kernels: `weights` [M] float64 (a device tensor: the shaped fitness of es_perturb's members, for example
-        their centred ranks) and the noise of es_perturb(.., nonce, pair_base) drawn again -- no table is read.  The sum
-        runs in a fixed order (the same bits on every call) and the result is written, not accumulated; the scale
-        1 / (M sigma) is the caller's.  Returns g [num_params] float64, a buffer of this env overwritten by its next call
-        with the same num_params.  Asynchronous on the current stream."""
-        self._check_open()
-        torch = _torch()
-        if not isinstance(weights, torch.Tensor) or weights.dim() != 1:
-            raise ValueError("weights must be a [M] float64 device tensor")
-        M = int(weights.shape[0])
-        eio = self._es_io(M, num_params, nonce, pair_base)
-        self._check_tape("the shaped fitness", (weights, "weights", (M,), torch.float64))
-        g = self._rollout_cache(("es_grad", eio.num_params), lambda: torch.empty(
-            eio.num_params, dtype=torch.float64, device=self.device))
-        eio.weights_dev, eio.grad_dev = weights.data_ptr(), g.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_es_gradient(self._ctx, C.byref(eio), self._stream()))
-        self._keep = [weights]
-        return g
-
-    # -- on-policy actor-critic collection and GAE (DESIGN section 17) ---------------------------
-    def rollout_actor_critic(self, actor, critic, log_std, K, hidden, critic_hidden=None, nonce=0, deterministic=False,
-                             means=False):
-        """K closed-loop steps under a Gaussian MLP policy with a value head, one kernel, with everything a PPO / A2C
-        learner needs of them.  The env ADVANCES (its own auto-reset mode), exactly as step_many would under the
-        returned actions.  actor [P] float32 is a gym_copter_amd.mlp vector of `hidden`; critic [Pv] float32 one with
-        act_dim = 1 and `critic_hidden` (None: `hidden`), or None for no values; log_std [A] float32.  Per step, on the
-        observation o the previous step returned (step 1: the stored state's):
-
-            mu = actor(o), V = critic(o), a = float32(mu + float32(exp(log_std) eps)), eps ~ N(0, 1)
-
-        (deterministic=True: a = mu) and logp = log N(a; mu, exp(log_std)^2) computed in float64 from the stored a and
-        mu.  eps is the library's counter-based Box-Muller draw, a pure function of (seed, `nonce`, global env id, step,
-        component): tests/ppo_ref.py restates it.  Returns ActorCritic(obs [K+1,N,OBS] -- row 0 the stored state's
-        observation, row K the bootstrap observation --, actions [K,N,A], means [K,N,A] or None (means=True), logp [K,N],
-        values [K+1,N] or None, reward [K,N], terminated [K,N], truncated [K,N], live [K,N] bool: False for a next_step
-        reset step, whose action the env ignores).  Asynchronous on the current stream; the tensors are buffers of this
-        env, overwritten by its next call with the same K."""
-        self._check_open()
-        torch = _torch()
-        n, dev, A, od = self.num_envs, self.device, self.action_dim, self.obs_dim
-        if not isinstance(K, (int, np.integer)) or isinstance(K, bool) or K < 1:
-            raise ValueError("K must be an int >= 1, got %r" % (K,))
-        K = int(K)
-        P = _mlp.num_params(od, A, hidden)                                # (checks hidden)
-        if critic_hidden is None:
-            critic_hidden = hidden
-        Pv = _mlp.num_params(od, 1, critic_hidden)
-        nonce = self._es_u32(nonce, "nonce")
-
-        def vec(t, size, name):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (size,):
-                raise ValueError("%s must be a [%d] float32 torch tensor, got %s"
-                                 % (name, size, getattr(t, "shape", type(t).__name__)))
-            return t.detach().to(dev).contiguous()
-        th = vec(actor, P, "actor")
-        tv = vec(critic, Pv, "critic") if critic is not None else None
-        ls = vec(log_std, A, "log_std")
-
-        def make():
-            flags = torch.empty((K, n, 2), dtype=torch.uint8, device=dev)        # interleaved flags
-            return {"obs": torch.empty((K + 1, n, od), dtype=torch.float32, device=dev),
-                    "actions": torch.empty((K, n, A), dtype=torch.float32, device=dev),
-                    "logp": torch.empty((K, n), dtype=torch.float32, device=dev),
-                    "reward": torch.empty((K, n), dtype=torch.float32, device=dev),
-                    "flags": flags, "live": torch.empty((K, n), dtype=torch.uint8, device=dev)}
-        buf = self._rollout_cache(("actor_critic", K), make)
-        if means and "means" not in buf:
-            buf["means"] = torch.empty((K, n, A), dtype=torch.float32, device=dev)
-        if tv is not None and "values" not in buf:
-            buf["values"] = torch.empty((K + 1, n), dtype=torch.float32, device=dev)
-        aio = _lib.RolloutAcIO()
-        aio.struct_size = C.sizeof(_lib.RolloutAcIO)
-        aio.num_steps, aio.hidden, aio.critic_hidden = K, hidden, critic_hidden
-        aio.nonce, aio.deterministic = nonce, 1 if deterministic else 0
-        aio.actor_dev, aio.log_std_dev = th.data_ptr(), ls.data_ptr()
-        aio.critic_dev = tv.data_ptr() if tv is not None else None
-        aio.obs_dev, aio.actions_dev, aio.logp_dev = (buf[k].data_ptr() for k in ("obs", "actions", "logp"))
-        aio.reward_dev, aio.flags_dev, aio.live_dev = (buf[k].data_ptr() for k in ("reward", "flags", "live"))
-        aio.means_dev = buf["means"].data_ptr() if means else None
-        aio.values_dev = buf["values"].data_ptr() if tv is not None else None
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_rollout_actor_critic(self._ctx, C.byref(aio), self._stream()))
-        self._keep = [th, tv, ls]
-        flags = buf["flags"]
-        return ActorCritic(buf["obs"], buf["actions"], buf["means"] if means else None, buf["logp"],
-                           buf["values"] if tv is not None else None, buf["reward"], flags[:, :, 0].view(torch.bool),
-                           flags[:, :, 1].view(torch.bool), buf["live"].view(torch.bool))
-
-    def gae(self, reward, values, terminated, truncated, gamma=0.99, lam=0.95):
-        """Generalised advantage estimation over rollout_actor_critic's tapes, one kernel: reward [K,N] float32, values
-        [K+1,N] float32, terminated and truncated [K,N] bool or uint8 (device tensors) -> (advantages, returns), both
-        [K,N] float32:
-
-            delta_k = r_k + gamma V_{k+1} nd_k - V_k,   adv_k = delta_k + gamma lam nd_k adv_{k+1},   ret_k = adv_k + V_k
-
-        with nd_k = 0 where step k terminated OR truncated its episode (truncation cuts the bootstrap as termination
-        does: the K-step forms return no final observation to bootstrap from) and 1 elsewhere.  float32 in a fixed order,
-        no fused operation: tests/ppo_ref.py gives the same bits in NumPy.  Asynchronous on the current stream; the
-        results are buffers of this env, overwritten by its next call with the same K."""
-        self._check_open()
-        torch = _torch()
-        n, dev = self.num_envs, self.device
-        if not isinstance(reward, torch.Tensor) or reward.dim() != 2:
-            raise ValueError("reward must be a [K,%d] float32 device tensor" % n)
-        K = int(reward.shape[0])
-        self._check_tape("rollout_actor_critic", (reward, "reward", (K, n), torch.float32),
-                         (values, "values", (K + 1, n), torch.float32))
-        g, l = float(gamma), float(lam)
-        with np.errstate(over="ignore"):
-            narrowed = (np.float32(g), np.float32(l), np.float32(g) * np.float32(l))
-        if not np.isfinite(g) or not np.isfinite(l) or not np.all(np.isfinite(narrowed)):
-            raise ValueError("gamma and lam must be finite (in float32, and their product too), got %r and %r"
-                             % (gamma, lam))
-        flags = []
-        for t, name in ((terminated, "terminated"), (truncated, "truncated")):
-            if not isinstance(t, torch.Tensor) or tuple(t.shape) != (K, n) or t.dtype not in (torch.bool, torch.uint8) \
-                    or t.device != dev:
-                raise ValueError("%s must be a [%d,%d] bool or uint8 tensor on %s" % (name, K, n, dev))
-            flags.append(t.view(torch.uint8) if t.dtype == torch.bool else t)
-        # the two columns of one interleaved [K,N,2] array (what rollout_actor_critic returns) are read in place
-        stride = 2 if all(t.stride() == (2 * n, 2) for t in flags) else 1
-        if stride == 1:
-            flags = [t.contiguous() for t in flags]
-        out = self._rollout_cache(("gae", K), lambda: (torch.empty((K, n), dtype=torch.float32, device=dev),
-                                                       torch.empty((K, n), dtype=torch.float32, device=dev)))
-        gio = _lib.GaeIO()
-        gio.struct_size = C.sizeof(_lib.GaeIO)
-        gio.num_steps, gio.flag_stride, gio.gamma, gio.lam = K, stride, g, l
-        gio.reward_dev, gio.values_dev = reward.data_ptr(), values.data_ptr()
-        gio.terminated_dev, gio.truncated_dev = flags[0].data_ptr(), flags[1].data_ptr()
-        gio.advantages_dev, gio.returns_dev = out[0].data_ptr(), out[1].data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_gae(self._ctx, C.byref(gio), self._stream()))
-        self._keep = [reward, values] + flags
-        return out
-
-    def ppo_grad(self, actor, critic, log_std, hidden, critic_hidden, obs, actions, logp, advantages, returns, live=None,
-                 index=None, row_base=0, num_samples=None, clip=0.2, vf_coef=0.5, ent_coef=0.0, normalize=True, out=None,
-                 stats_out=None):
-        """PPO's clipped-surrogate minibatch loss and its gradient, ON THE DEVICE (cs_ppo_grad): what
-        the minibatch step of gym_copter_amd.ppo differentiates, evaluated in float64 from the float32 tapes,
-
-            L = -mean_w min(r A, clip(r, 1 - clip, 1 + clip) A) + vf_coef mean_w (V - ret)^2 / 2 - ent_coef H
-
-        over the minibatch's live samples (w = live), r = exp(logp_new - logp), A the advantages normalised over the
-        minibatch's live samples (normalize=True), H the Gaussian's entropy.  actor [P], critic [Pv] (None: no value
-        term) and log_std [A] are float32 device tensors in gym_copter_amd.mlp's layout for `hidden` / `critic_hidden`.
-        The tapes are what rollout_actor_critic and gae returned -- obs [K,N,OBS] or the [K+1,N,OBS] tape (its first K
-        rows are used), actions [K,N,A], logp, advantages, returns [K,N] float32, live [K,N] bool or uint8 (None: every
-        row live) -- or the same flattened to R rows: obs [R,OBS], actions [R,A], the others [R].  The minibatch is
-        `index`, a contiguous int64 device tensor of row numbers (a slice of torch.randperm; an entry outside [0, R) is
-        skipped by the kernel, a duplicate counts twice), or, with index=None, the `num_samples` (default: all) rows
-        from `row_base` on.  A row is live iff its `live` byte is nonzero: a uint8 tape holding 2 or 255 gives the bits
-        of one holding 1; a dead row, a row the index does not name and an out-of-range sample are never read.  The
-        tapes may be contiguous views that start inside larger buffers (`buf[k:]`), with one condition the library
-        checks: obs must start on a 16-byte boundary.  Every row of a [R,12] tape does; of a [R,10], [R,6] or [R,2] tape
-        only every second row does, and a view from another row is refused with a CopterStepError that names
-        the alignment, before any launch.
-
-        Returns PpoGrad(grad [P + Pv + A] float64: dL / d(actor | critic | log_std), stats [8] float64: PPO_STATS of this
-        module -- live samples, policy loss, value loss, entropy, L, the approximate KL, the clipped share, max |r - 1|),
-        written into `out` / `stats_out` or into new tensors.  The sums run in a fixed order: the same inputs give the
-        same bits.  Asynchronous on the current stream; nothing is read by the host."""
-        self._check_open()
-        torch = _torch()
-        dev, A, od = self.device, self.action_dim, self.obs_dim
-        P = _mlp.num_params(od, A, hidden)                                # (checks hidden)
-        Pv = _mlp.num_params(od, 1, critic_hidden) if critic is not None else 0
-        if critic is None:
-            critic_hidden = 0 if critic_hidden is None else critic_hidden
-            _mlp.num_params(od, 1, critic_hidden)
-
-        def vec(t, size, name):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (size,) \
-                    or t.device != dev:
-                raise ValueError("%s must be a [%d] float32 tensor on %s, got %s"
-                                 % (name, size, dev, getattr(t, "shape", type(t).__name__)))
-            return t.detach().contiguous()
-        th = vec(actor, P, "actor")
-        tv = vec(critic, Pv, "critic") if critic is not None else None
-        ls = vec(log_std, A, "log_std")
-        if not isinstance(actions, torch.Tensor) or actions.dim() not in (2, 3):
-            raise ValueError("actions must be the [K,N,%d] action tape of rollout_actor_critic or its rows [R,%d]"
-                             % (A, A))
-        lead = tuple(actions.shape[:-1])
-        R = int(np.prod(lead))
-        if R < 1:
-            raise ValueError("the tapes hold no rows")
-        if not isinstance(obs, torch.Tensor):
-            raise ValueError("obs must be the obs tape of rollout_actor_critic, a device tensor")
-        if len(lead) == 2 and tuple(obs.shape) == (lead[0] + 1, lead[1], od):
-            obs = obs[:lead[0]]                                           # (the [K+1,N,OBS] tape: a contiguous prefix)
-        tapes = [(obs, "obs", lead + (od,), torch.float32), (actions, "actions", lead + (A,), torch.float32),
-                 (logp, "logp", lead, torch.float32), (advantages, "advantages", lead, torch.float32)]
-        if tv is not None or returns is not None:
-            tapes.append((returns, "returns", lead, torch.float32))
-        self._check_tape("rollout_actor_critic / gae", *tapes)
-        if live is not None:
-            if not isinstance(live, torch.Tensor) or live.dtype not in (torch.bool, torch.uint8):
-                raise ValueError("live must be a bool or uint8 device tensor of shape %s" % (lead,))
-            self._check_tape("rollout_actor_critic", (live, "live", lead, live.dtype))
-            live = live.view(torch.uint8) if live.dtype == torch.bool else live
-        if index is not None:
-            if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.dtype != torch.int64 \
-                    or index.device != dev or not index.is_contiguous() or index.shape[0] < 1:
-                raise ValueError("index must be a contiguous 1-D int64 tensor on %s with at least one entry" % (dev,))
-            if num_samples is not None and int(num_samples) != int(index.shape[0]):
-                raise ValueError("num_samples = %r disagrees with index [%d]" % (num_samples, index.shape[0]))
-            B, base = int(index.shape[0]), 0
-        else:
-            if not isinstance(row_base, (int, np.integer)) or isinstance(row_base, bool):
-                raise ValueError("row_base must be an int, got %r" % (row_base,))
-            base = int(row_base)
-            B = R - base if num_samples is None else num_samples
-            if not isinstance(B, (int, np.integer)) or isinstance(B, bool) or B < 1 or base < 0 or base + B > R:
-                raise ValueError("rows row_base .. row_base + num_samples - 1 must lie in [0, %d), got row_base %r, "
-                                 "num_samples %r" % (R, row_base, num_samples))
-            B = int(B)
-        cl, vf, en = float(clip), float(vf_coef), float(ent_coef)
-        if not np.isfinite(cl) or not cl > 0.0:
-            raise ValueError("clip must be finite and > 0, got %r" % (clip,))
-        if not np.isfinite(vf) or not np.isfinite(en):
-            raise ValueError("vf_coef and ent_coef must be finite, got %r and %r" % (vf_coef, ent_coef))
-        if out is None:
-            out = torch.empty(P + Pv + A, dtype=torch.float64, device=dev)
-        else:
-            self._check_tape("ppo_grad", (out, "out", (P + Pv + A,), torch.float64))
-        if stats_out is None:
-            stats_out = torch.empty(8, dtype=torch.float64, device=dev)
-        else:
-            self._check_tape("ppo_grad", (stats_out, "stats_out", (8,), torch.float64))
-        pio = _lib.PpoGradIO()
-        pio.struct_size = C.sizeof(_lib.PpoGradIO)
-        pio.hidden, pio.critic_hidden, pio.normalize = hidden, critic_hidden, 1 if normalize else 0
-        pio.num_rows, pio.num_samples, pio.row_base = R, B, base
-        pio.clip, pio.vf_coef, pio.ent_coef = cl, vf, en
-        pio.actor_dev, pio.log_std_dev = th.data_ptr(), ls.data_ptr()
-        pio.critic_dev = tv.data_ptr() if tv is not None else None
-        pio.obs_dev, pio.actions_dev, pio.logp_dev = obs.data_ptr(), actions.data_ptr(), logp.data_ptr()
-        pio.advantages_dev = advantages.data_ptr()
-        pio.returns_dev = returns.data_ptr() if returns is not None else None
-        pio.live_dev = live.data_ptr() if live is not None else None
-        pio.index_dev = index.data_ptr() if index is not None else None
-        pio.grad_dev, pio.stats_dev = out.data_ptr(), stats_out.data_ptr()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.cs_ppo_grad(self._ctx, C.byref(pio), self._stream()))
-        self._keep = [th, tv, ls, obs, actions, logp, advantages, returns, live, index]
-        return PpoGrad(out, stats_out)
-
+    # -- Dynamics-level access (reference dynamics/__init__.py public methods) ---------
     def set_motors(self, motors):
         """`substeps` x Dynamics.setMotors(motors[i]) on every env, no task logic."""
         self._check_open()

@@ -2,10 +2,11 @@
 entry point writes outside the arrays it is given, it writes every element of every output, and it leaves its inputs
 unchanged.
 
-The wrappers of gym_copter_amd/vecenv.py allocate every output with torch.empty(..., device=<the env's>), looked up at
-call time.  `with guarded(N) as guard:` replaces torch.empty for the block: an allocation on the guarded device becomes
-the middle of one uint8 backing tensor filled with the byte 0xA5, with a band of the same fill in front of it and behind
-it.  A store past either end of an output lands in a band and stays visible; an element nobody stored still holds the fill.
+CopterVecEnv's wrappers allocate every output with torch.empty(..., device=<the env's>), looked up at call time
+(gym_copter_amd/_wire.py's empty(); step_many and _rollout in vecenv.py).  `with guarded(N) as guard:` replaces
+torch.empty for the block: an allocation on the guarded device becomes the middle of one uint8 backing tensor filled with
+the byte 0xA5, with a band of the same fill in front of it and behind it.  A store past either end of an output lands in
+a band and stays visible; an element nobody stored still holds the fill.
 
     with guarded(env.num_envs) as guard:
         guard.freeze(actions=actions)

@@ -57,6 +57,10 @@ COVERED = {
     "rollout_actor_critic": "test_actor_critic_and_gae", "gae": "test_actor_critic_and_gae",
     "ppo_grad": "test_ppo_grad",
     "rollout_ekf": "test_ekf_and_rts", "rollout_rts": "test_ekf_and_rts",
+    # the families whose guarded test lives with their own tests: "<module>::<test>"
+    "rollout_pf": "test_gpu_rollout_pf::test_outputs_are_written_fully_and_nothing_else",
+    "rollout_lqg": "test_gpu_lqg_output_bounds::test_lqg_outputs_are_written_exactly",
+    "rollout_ukf": "test_gpu_ukf_output_bounds::test_ukf_outputs_are_written_exactly",
 }
 SKIPPED = {
     "rollout_policy": "needs a policy functor compiled with hipcc at run time; it goes through _rollout, whose buffers and "

@@ -182,34 +182,60 @@ def test_another_fill_byte():
 # every entry point is in tests/test_gpu_output_bounds.py
 # ---------------------------------------------------------------------------------------------------------------------
 def _entry_points():
-    """The public methods of CopterVecEnv that the contract covers, read from the source (no device, no library)."""
-    tree = ast.parse(open(os.path.join(ROOT, "gym_copter_amd", "vecenv.py")).read())
-    cls = next(n for n in tree.body if isinstance(n, ast.ClassDef) and n.name == "CopterVecEnv")
-    names = [n.name for n in cls.body if isinstance(n, ast.FunctionDef)]
+    """The public methods of CopterVecEnv that the contract covers: the class's own attributes (no device, no library),
+    whether a method is defined in the class body or bound there from its family's module."""
+    import gym_copter_amd
+    names = [n for n, v in vars(gym_copter_amd.CopterVecEnv).items() if callable(v)]
     return {n for n in names if n.startswith(("rollout_", "es_")) or n in ("gae", "ppo_grad", "mlp_param_grad",
                                                                           "step_jacobian", "step_many")}
+
+
+def _module_functions(module):
+    """(name -> ast.FunctionDef of the test module's top-level functions, alias -> module for its `import x as alias`)"""
+    tree = ast.parse(open(os.path.join(ROOT, "tests", module + ".py")).read())
+    funcs = {n.name: n for n in tree.body if isinstance(n, ast.FunctionDef)}
+    aliases = {a.asname or a.name: a.name for n in tree.body if isinstance(n, ast.Import) for a in n.names}
+    return funcs, aliases
+
+
+def _methods_called(module, test):
+    """The attribute names called in `test` of tests/<module>.py, in the module's own helpers it calls (one level) and
+    in the helpers of another test module it calls as <alias>.<helper>(...)."""
+    funcs, aliases = _module_functions(module)
+    assert test in funcs and test.startswith("test_"), (module, test)
+    calls = [n for n in ast.walk(funcs[test]) if isinstance(n, ast.Call)]
+    for h in {n.func.id for n in calls if isinstance(n.func, ast.Name)} & set(funcs):
+        calls += [n for n in ast.walk(funcs[h]) if isinstance(n, ast.Call)]
+    called = {n.func.attr for n in calls if isinstance(n.func, ast.Attribute)}
+    for n in calls:
+        f = n.func
+        if isinstance(f, ast.Attribute) and isinstance(f.value, ast.Name) and aliases.get(f.value.id, "").startswith("test_"):
+            other = _module_functions(aliases[f.value.id])[0]
+            if f.attr in other:
+                called |= {c.func.attr for c in ast.walk(other[f.attr]) if isinstance(c, ast.Call)
+                           and isinstance(c.func, ast.Attribute)}
+    return called
 
 
 def test_every_entry_point_is_covered():
     import test_gpu_output_bounds as B
     have = _entry_points()
-    assert len(have) >= 24 and {"step_many", "rollout_rts", "es_gradient", "gae"} <= have, sorted(have)
+    assert len(have) >= 27 and {"step_many", "rollout_rts", "es_gradient", "gae", "rollout_pf", "rollout_lqg",
+                                "rollout_ukf"} <= have, sorted(have)
     assert set(B.SKIPPED) <= have and all(reason for reason in B.SKIPPED.values())
     assert not set(B.COVERED) & set(B.SKIPPED)
     missing = have - set(B.COVERED) - set(B.SKIPPED)
-    assert not missing, "entry points without a test in tests/test_gpu_output_bounds.py: %s" % sorted(missing)
+    assert not missing, "entry points without a guarded-output test named in tests/test_gpu_output_bounds.py: %s" \
+        % sorted(missing)
     stale = set(B.COVERED) - have
     assert not stale, "tests/test_gpu_output_bounds.py lists methods CopterVecEnv does not have: %s" % sorted(stale)
-    # the list is not a declaration only: every covered method is called on an env in the test named for it
-    src = open(os.path.join(ROOT, "tests", "test_gpu_output_bounds.py")).read()
-    funcs = {n.name: ast.get_source_segment(src, n) for n in ast.parse(src).body if isinstance(n, ast.FunctionDef)}
+    # the list is not a declaration only: every covered method is called on an env in the test named for it -- a test of
+    # tests/test_gpu_output_bounds.py, or "<module>::<test>" for a family whose guarded test lives with its own tests
     for method, test in B.COVERED.items():
-        assert test in funcs and test.startswith("test_"), (method, test)
-        called = {n.func.attr for n in ast.walk(ast.parse(funcs[test])) if isinstance(n, ast.Call)
-                  and isinstance(n.func, ast.Attribute)}
-        helpers = {n.func.id for n in ast.walk(ast.parse(funcs[test])) if isinstance(n, ast.Call)
-                   and isinstance(n.func, ast.Name)}
-        for h in helpers & set(funcs):                              # (one level of the module's own helpers)
-            called |= {n.func.attr for n in ast.walk(ast.parse(funcs[h])) if isinstance(n, ast.Call)
-                       and isinstance(n.func, ast.Attribute)}
-        assert method in called, "%s does not call env.%s" % (test, method)
+        module, name = test.split("::") if "::" in test else ("test_gpu_output_bounds", test)
+        assert method in _methods_called(module, name), "%s::%s does not call env.%s" % (module, name, method)
+        funcs = _module_functions(module)[0]
+        entered = [i.context_expr for w in ast.walk(funcs[name]) if isinstance(w, ast.With) for i in w.items]
+        assert module == "test_gpu_output_bounds" or any(
+            isinstance(e, ast.Call) and isinstance(e.func, ast.Name) and e.func.id == "guarded" for e in entered), \
+            "%s::%s never enters `with guarded(...)`" % (module, name)

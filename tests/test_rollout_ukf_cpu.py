@@ -35,7 +35,7 @@ def test_entry_point_is_declared_exported_and_bound():
     from gym_copter_amd.ukf import rollout_ukf, ukf, UkfResult
     assert gym_copter_amd.CopterVecEnv.rollout_ukf is rollout_ukf and gym_copter_amd.ukf is ukf
     assert gym_copter_amd.UkfResult is UkfResult and hasattr(ShardedCopterVecEnv, "rollout_ukf")
-    # bound, not defined, in the class body (tests/test_guarded_outputs_cpu.py reads the class's defs)
+    # bound, not defined, in the class body (as every family's wrappers are)
     src = open(os.path.join(ROOT, "gym_copter_amd", "vecenv.py")).read()
     assert re.search(r"^    rollout_ukf = _ukf\.rollout_ukf$", src, re.M) and "def rollout_ukf" not in src
 
