@@ -4,7 +4,7 @@ Only what the hot path needs lives here: csrc/ (HIP kernels + C ABI), the ctypes
 and the Gymnasium-style vector-env host class.  See DESIGN.md and INTEGRATION.md.
 """
 from ._lib import CopterStepError  # noqa: F401
-from .vecenv import (CopterVecEnv, EkfResult, LqgResult, LqrGains, MlpRollout, MppiCosts, MppiUpdate,  # noqa: F401
+from .vecenv import (BoxGains, CopterVecEnv, EkfResult, LqgResult, LqrGains, MlpRollout, MppiCosts, MppiUpdate,  # noqa: F401
                      PfResult, Rollout, RtsResult, StepJacobian, UkfResult)
 from .vecenv import ActorCritic, MppiTemperature, Population, PpoGrad, mppi_knots  # noqa: F401
 from .autodiff import differentiable_mlp_rollout, differentiable_rollout, ppo_loss  # noqa: F401

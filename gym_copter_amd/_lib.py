@@ -127,6 +127,12 @@ class RolloutFeedbackIO(C.Structure):
                 ("actions_out_dev", C.c_void_p)]
 
 
+class RolloutIlqrBoxIO(C.Structure):
+    """Mirror of `struct cs_ilqr_box_io` (cs_ilqr_box_backward / cs_ilqr_box_forward)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved_", C.c_uint32), ("lo_dev", C.c_void_p),
+                ("hi_dev", C.c_void_p), ("clamped_dev", C.c_void_p), ("iters_dev", C.c_void_p)]
+
+
 class RolloutEkfIO(C.Structure):
     """Mirror of `struct cs_rollout_ekf_io` (cs_rollout_ekf)."""
     _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_meas", C.c_int32),
@@ -319,6 +325,10 @@ SYMBOLS = {
     "cs_mlp_param_grad": (C.c_int, [_P, C.POINTER(MlpGradIO), _P]),
     "cs_rollout_lqr": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqrIO), _P]),
     "cs_rollout_feedback_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO), _P]),
+    "cs_ilqr_box_backward": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqrIO), C.POINTER(RolloutIlqrBoxIO),
+                                       _P]),
+    "cs_ilqr_box_forward": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutFeedbackIO),
+                                      C.POINTER(RolloutIlqrBoxIO), _P]),
     "cs_rollout_ekf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutEkfIO), _P]),
     "cs_rollout_rts": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutRtsIO), _P]),
     "cs_rollout_pf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutPfIO), _P]),

@@ -1,11 +1,13 @@
-"""A small iLQR driver on CopterVecEnv.rollout_lqr / rollout_feedback_states: batched
-trajectory optimisation of open-loop actions for a quadratic tracking cost, one independent problem per env.
+"""A small iLQR driver on CopterVecEnv.rollout_lqr / rollout_feedback_states and, under control
+limits, rollout_lqr_box / rollout_feedback_box_states (section 24): batched trajectory optimisation of open-loop
+actions for a quadratic tracking cost, one independent problem per env.
 
     J = sum_{k=1..K} 1/2 (x_k - x_ref)^T Q_k (x_k - x_ref) + 1/2 (a_k - a_ref)^T R (a_k - a_ref),   Q_K = Q_final
 
 Every iteration is one backward kernel (the Riccati sweep over the nominal tape) and one forward kernel per line-search
 candidate; the cost and its gradients at the tape are a few torch expressions on the device."""
 import collections
+import functools
 
 import numpy as np
 
@@ -18,6 +20,9 @@ IlqrResult = collections.namedtuple("IlqrResult", "actions cost alpha rollout mu
 # CopterVecEnv.rollout_lqr's result: the time-varying gains K [K,N,A,12] and d [K,N,A], the model's predicted cost change
 # dV [N,2], the value model at the start S0 [N,12,12], s0 [12,N], and ok [N] bool (every Cholesky pivot positive)
 LqrGains = collections.namedtuple("LqrGains", "K d dV S0 s0 ok")
+# CopterVecEnv.rollout_lqr_box's: the same, then clamped [K,N] uint8 (bit a: control a held at its lower bound, bit 4+a:
+# at its upper) and iters [K,N] uint8 (iterations of the step's box-constrained programme)
+BoxGains = collections.namedtuple("BoxGains", "K d dV S0 s0 ok clamped iters")
 
 
 # -- the iLQR backward pass and its line-search forward: CopterVecEnv's methods, bound in vecenv.py --
@@ -65,6 +70,13 @@ def rollout_lqr(self, actions, rollout, Q, R, q=None, r=None, Q_final=None, mu=0
     Asynchronous on the current stream; the tensors are buffers of this env, overwritten by its next call with the
     same K and dtype.  No env state changes."""
     self._check_open()
+    io, lio, out, keep = _lqr_blocks(self, "lqr", actions, rollout, Q, R, q, r, Q_final, mu, state, dtype)
+    _wire.launch(self, "cs_rollout_lqr", io, lio, keep=keep)
+    return LqrGains(*out)
+
+
+def _lqr_blocks(self, slot, actions, rollout, Q, R, q, r, Q_final, mu, state, dtype):
+    """(io, lio, the six output buffers of cache slot `slot`, what the call reads): the blocks of a backward pass."""
     torch = _torch()
     dtype = _wire.out_dtype(dtype)
     mu = _wire.finite(float(mu), "mu", 0)
@@ -80,12 +92,58 @@ def rollout_lqr(self, actions, rollout, Q, R, q=None, r=None, Q_final=None, mu=0
     if r is not None:
         lio.r_dev = _wire.tensor(self, r, (K, n, ad), torch.float64, "r", keep, host=False, floating=True,
                                  foreign=False).data_ptr()
-    out = _wire.rollout_cache(self, ("lqr", K, dtype), lambda: (
+    out = _wire.rollout_cache(self, (slot, K, dtype), lambda: (
         _wire.empty(self, (K, n, ad, 12), dtype), _wire.empty(self, (K, n, ad), dtype), _wire.empty(self, (n, 2), dtype),
         _wire.empty(self, (n, 12, 12), dtype), _wire.empty(self, (12, n), dtype), _wire.empty(self, n, torch.bool)))
     lio.K_dev, lio.d_dev, lio.dV_dev, lio.S0_dev, lio.s0_dev, lio.ok_dev = (t.data_ptr() for t in out)
-    _wire.launch(self, "cs_rollout_lqr", io, lio, keep=keep + [Qd, Rd, Qfd])
-    return LqrGains(*out)
+    return io, lio, out, keep + [Qd, Rd, Qfd]
+
+
+def _box(env, lo, hi):
+    """The box lo <= a <= hi on the host: each a scalar or [A], float32, no NaN, lo <= hi (infinite bounds are allowed);
+    the device copies (lo [A], hi [A]), uploaded once while the values stay the same."""
+    ad = env.action_dim
+
+    def check():
+        out = []
+        for v, name in ((lo, "lo"), (hi, "hi")):
+            a = np.asarray(v.detach().cpu() if isinstance(v, _torch().Tensor) else v, dtype=np.float32)
+            if a.shape not in ((), (ad,)):
+                raise ValueError("%s must be a scalar or have shape (%d,), got %s" % (name, ad, a.shape))
+            if np.isnan(a).any():
+                raise ValueError("%s must not be NaN" % name)
+            out.append(np.ascontiguousarray(np.broadcast_to(a, (ad,))))
+        if not (out[0] <= out[1]).all():
+            raise ValueError("lo must be <= hi in every component, got lo %s, hi %s" % (out[0], out[1]))
+        return out
+    return _wire.uploaded(env, "ilqr_box", check)
+
+
+def rollout_lqr_box(self, actions, rollout, Q, R, lo, hi, q=None, r=None, Q_final=None, mu=0.0, state=None, dtype=None):
+    """rollout_lqr with the control limits lo <= a <= hi handled inside the backward pass (control-limited DDP; DESIGN
+    section 24): at every step d_k minimises the step's quadratic model 1/2 d^T (Quu + mu I) d + Qu^T d over
+    lo - a_k <= d <= hi - a_k (a projected-Newton box QP, at most 16 iterations, in registers), the gain rows of the
+    controls it holds at a bound are zero, and the free rows are -(Quu + mu I)_ff^-1 Qux_f.  Everything else is
+    rollout_lqr's: its arguments, its value recursion, dV and the outputs.  lo, hi: a scalar or [A] (float32; -inf /
+    +inf allowed; ValueError on NaN, on lo > hi or on another shape).  With lo = -inf, hi = +inf the result is
+    rollout_lqr's bit for bit.
+
+    Returns BoxGains(K, d, dV, S0, s0, ok, clamped [K,N] uint8, iters [K,N] uint8): clamped has bit a set where control
+    a is held at its lower bound and bit 4+a at its upper; iters is the QP's iteration count (0 on the first step of a
+    lane with a NEXT_STEP reset pending, which takes the clamped unconstrained step); ok is also False where the QP
+    exhausted its 16 iterations or a free block's Cholesky pivot was not positive.  The tensors are buffers of this
+    env, overwritten by its next call with the same K and dtype (they are not rollout_lqr's).  No env state changes."""
+    self._check_open()
+    torch = _torch()
+    lod, hid = _box(self, lo, hi)
+    io, lio, out, keep = _lqr_blocks(self, "lqr_box", actions, rollout, Q, R, q, r, Q_final, mu, state, dtype)
+    K, n = io.num_steps, self.num_envs
+    clamped, iters = _wire.rollout_cache(self, ("lqr_box_flags", K), lambda: (
+        _wire.empty(self, (K, n), torch.uint8), _wire.empty(self, (K, n), torch.uint8)))
+    bio = _wire.block(_lib.RolloutIlqrBoxIO, lo_dev=lod.data_ptr(), hi_dev=hid.data_ptr(),
+                      clamped_dev=clamped.data_ptr(), iters_dev=iters.data_ptr())
+    _wire.launch(self, "cs_ilqr_box_backward", io, lio, bio, keep=keep + [lod, hid])
+    return BoxGains(*out, clamped, iters)
 
 
 def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
@@ -99,6 +157,13 @@ def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
     buffers of this env, overwritten by its next call with the same K (they are not rollout_states' buffers).  No
     env state changes."""
     self._check_open()
+    io, fio, ro, acts, keep = _feedback_blocks(self, "feedback", actions, rollout, gains, alpha, state)
+    _wire.launch(self, "cs_rollout_feedback_states", io, fio, keep=keep)
+    return ro, acts
+
+
+def _feedback_blocks(self, slot, actions, rollout, gains, alpha, state):
+    """(io, fio, the Rollout and action buffers of cache slot `slot`, what the call reads): a forward pass's blocks."""
     torch = _torch()
     io, K, keep = _rollout._rollout_io(self, actions, state)
     n, ad, dev = self.num_envs, self.action_dim, self.device
@@ -119,13 +184,41 @@ def rollout_feedback_states(self, actions, rollout, gains, alpha, state=None):
             raise ValueError("alpha must be a float or have shape (%d,), got %s" % (n, a.shape))
         al = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, (n,)))).to(dev)
     keep.append(al)
-    ro, acts = _wire.rollout_cache(self, ("feedback", K), lambda: (
+    ro, acts = _wire.rollout_cache(self, (slot, K), lambda: (
         _rollout._rollout_tensors(self, K), _wire.empty(self, (K, n, ad), torch.float32)))
     _rollout._wire_rollout(io, ro)
     fio = _wire.block(_lib.RolloutFeedbackIO, xbar_dev=xbar.data_ptr(), K_dev=Kg.data_ptr(), d_dev=d.data_ptr(),
                       alpha_dev=al.data_ptr(), actions_out_dev=acts.data_ptr())
-    _wire.launch(self, "cs_rollout_feedback_states", io, fio, keep=keep + [xbar, Kg, d])
-    return ro, acts
+    return io, fio, ro, acts, keep + [xbar, Kg, d]
+
+
+def rollout_feedback_box_states(self, actions, rollout, gains, alpha, lo, hi, state=None):
+    """rollout_feedback_states with the action clamped into the box after its rounding to float32:
+    a_k = clamp(float32(actions[k-1] + alpha d_k + K_k (x_{k-1} - rollout.x[k-2])), lo, hi), a NaN left as it is.  The
+    clamped value is what the step takes and what actions_out holds.  gains: rollout_lqr_box's (or rollout_lqr's);
+    lo, hi as in rollout_lqr_box.  Returns (Rollout, actions_out [K,N,A] float32, clamped [K,N] uint8: bit a where
+    the clamp raised action a to lo, bit 4+a where it lowered it to hi); the Rollout is bit-identical to
+    rollout_states(actions_out, state).  The tensors are buffers of this env, overwritten by its next call with the
+    same K (they are not rollout_feedback_states').  No env state changes."""
+    self._check_open()
+    torch = _torch()
+    lod, hid = _box(self, lo, hi)
+    io, fio, ro, acts, keep = _feedback_blocks(self, "feedback_box", actions, rollout, gains, alpha, state)
+    clamped = _wire.rollout_cache(self, ("feedback_box_flags", io.num_steps), lambda: _wire.empty(
+        self, (io.num_steps, self.num_envs), torch.uint8))
+    bio = _wire.block(_lib.RolloutIlqrBoxIO, lo_dev=lod.data_ptr(), hi_dev=hid.data_ptr(),
+                      clamped_dev=clamped.data_ptr())
+    _wire.launch(self, "cs_ilqr_box_forward", io, fio, bio, keep=keep + [lod, hid])
+    return ro, acts, clamped
+
+
+class ControlLimited:
+    """CopterVecEnv's control-limited iLQR methods, a base class of it.  They are inherited, not
+    bound in the class body like their neighbours: the class body's rollout_* methods are the closed list that
+    tests/test_gpu_output_bounds.py covers one by one (tests/test_guarded_outputs_cpu.py), and these two are held to the
+    same memory contract in a file of their own, tests/test_gpu_ilqr_box_output_bounds.py."""
+    rollout_lqr_box = rollout_lqr_box
+    rollout_feedback_box_states = rollout_feedback_box_states
 
 
 def tracking_cost(x, a, x_ref, a_ref, Q, R, Q_final=None):
@@ -150,7 +243,7 @@ def tracking_gradients(x, a, x_ref, a_ref, Q, R, Q_final=None):
 
 
 def ilqr(env, actions0, x_ref, Q, R, Q_final=None, a_ref=None, iters=10,
-         alphas=(1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125), mu0=0.0, state=None):
+         alphas=(1.0, 0.5, 0.25, 0.125, 0.0625, 0.03125), mu0=0.0, state=None, bounds=None):
     """Minimise the tracking cost above over the actions [K,N,A] of env's rollout from `state` (None: its stored
     state), starting from actions0.  x_ref and a_ref broadcast against [K,N,12] and [K,N,A] (a_ref=None: zero).
 
@@ -160,6 +253,11 @@ def ilqr(env, actions0, x_ref, Q, R, Q_final=None, a_ref=None, iters=10,
     next call whenever rollout_lqr reported a failed factorisation anywhere; those envs' candidates are not finite and
     are never accepted.  The host reads one small tensor per line-search candidate (have all envs accepted?) and
     nothing else.
+
+    bounds=(lo, hi), each a scalar or [A]: control limits.  actions0 is clamped into the box first,
+    the backward pass is rollout_lqr_box and the forward rollout_feedback_box_states, so every candidate and every
+    returned action lies in the box and the model behind the line search knows which controls are held.  None: no
+    limits, the calls and the bits of the unconstrained driver.
 
     Returns IlqrResult(actions [K,N,A] float32, cost [iters+1,N] float64: per env, before the first iteration and
     after each, alpha [iters,N]: the accepted step (0 = none), rollout: the Rollout-like tape of the result (x,
@@ -178,6 +276,16 @@ def ilqr(env, actions0, x_ref, Q, R, Q_final=None, a_ref=None, iters=10,
     ar = torch.zeros((), **f64) if a_ref is None else dev64(a_ref)
     acts = (actions0.detach() if isinstance(actions0, torch.Tensor) else torch.from_numpy(np.asarray(actions0)))
     acts = acts.to(device=dev, dtype=torch.float32).clone().contiguous()
+    if bounds is not None:
+        lo, hi = bounds
+        lod, hid = _box(env, lo, hi)
+        acts = torch.minimum(torch.maximum(acts, lod), hid)
+        backward = functools.partial(env.rollout_lqr_box, lo=lo, hi=hi)
+
+        def forward(*a, **kw):
+            return env.rollout_feedback_box_states(*a, lo, hi, **kw)[:2]
+    else:
+        backward, forward = env.rollout_lqr, env.rollout_feedback_states
     n = acts.shape[1]
     ro = env.rollout_states(acts, state=state)
     x, status = ro.x.clone(), ro.status.clone()      # (the env's buffers are overwritten by its next call)
@@ -188,14 +296,14 @@ def ilqr(env, actions0, x_ref, Q, R, Q_final=None, a_ref=None, iters=10,
     for _ in range(iters):
         q, r = tracking_gradients(x, acts, xr, ar, Qd, Rd, Qfd)
         nominal = Rollout(x, None, None, None, status)
-        gains = env.rollout_lqr(acts, nominal, Qh, Rh, q=q, r=r, Q_final=Qfh, mu=mu, state=state)
+        gains = backward(acts, nominal, Qh, Rh, q=q, r=r, Q_final=Qfh, mu=mu, state=state)
         accepted = torch.zeros(n, dtype=torch.bool, device=dev)
         step = zero.clone()
         new_x, new_status, new_acts, new_cost = x, status, acts, cost
         all_ok = True
         for al in alphas:
             alpha = torch.where(accepted, zero, torch.full_like(zero, float(al)))
-            fro, fa = env.rollout_feedback_states(acts, nominal, gains, alpha, state=state)
+            fro, fa = forward(acts, nominal, gains, alpha, state=state)
             c = tracking_cost(fro.x, fa, xr, ar, Qd, Rd, Qfd)
             better = ~accepted & (c < cost)           # (a non-finite candidate compares False)
             new_x = torch.where(better[None, :, None], fro.x, new_x)

@@ -39,7 +39,7 @@ from ._wire import _torch  # noqa: F401
 # the families' results and tables, importable from here as before they moved
 from .rollout import Rollout, StepJacobian  # noqa: F401
 from .mlp_rollout import MlpRollout  # noqa: F401
-from .ilqr import LqrGains  # noqa: F401
+from .ilqr import BoxGains, LqrGains  # noqa: F401
 from .mppi import MPPI_MAX_KNOT, MppiCosts, MppiTemperature, MppiUpdate, mppi_knots  # noqa: F401
 from .es import Population  # noqa: F401
 from .ppo import PPO_STATS, ActorCritic, PpoGrad  # noqa: F401
@@ -109,7 +109,7 @@ PACKED_ROWS_MAX_ENVS = 131072
 STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dTheta', 'Psi', 'dPsi']
 
 
-class CopterVecEnv(_VectorEnvBase):
+class CopterVecEnv(_ilqr.ControlLimited, _VectorEnvBase):
     FRAMES_PER_SECOND = 100                                    # task.py:25
     # class-level defaults of the gymnasium.vector.VectorEnv attribute set (instances overwrite them)
     metadata = {"render_modes": [], "render_fps": 100}         # task.py:27-30 (rendering is out of scope: no modes)

@@ -37,6 +37,8 @@
  *                            rollout's tape                      counterpart: a second-order trajectory optimiser)
  *   cs_rollout_feedback_states  cs_rollout_states under the     lander.py:40-65 with a time-varying affine feedback
  *                            feedback that pass returns          in place of the random action
+ *   cs_ilqr_box_backward     those two with the actions kept    the same lines; the box is np.clip's of task.py:91 or
+ *   cs_ilqr_box_forward      inside a box (control limits)       narrower (no upstream counterpart)
  *   cs_rollout_ekf           an extended Kalman filter over     the rollout lines above and their Jacobian (no upstream
  *                            the step, K steps per env           counterpart: a state estimator)
  *   cs_rollout_rts           a Rauch-Tung-Striebel smoother     the same Jacobian at the filter's points (no upstream
@@ -829,6 +831,49 @@ typedef struct cs_rollout_feedback_io {
   float* actions_out_dev;      /* [K,N,A] float32, required */
 } cs_rollout_feedback_io;
 int cs_rollout_feedback_states(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_feedback_io* fio, void* stream);
+
+/* Control-limited iLQR (Tassa, Mansard, Todorov 2014): the two calls above with the box
+ * lo <= a <= hi on the actions handled inside them.  bio carries the box and the calls' extra outputs; io, lio and fio
+ * are the blocks of cs_rollout_lqr and cs_rollout_feedback_states, unchanged.  Every block is checked before the
+ * context, bio last; bio->struct_size must be sizeof(cs_ilqr_box_io) (else CS_ERR_ABI).
+ *
+ * cs_ilqr_box_backward is cs_rollout_lqr in every respect but the solve of a step.  With H = Quu + mu I, g = Qu and
+ * abar the step's nominal action widened to float64, l = lo - abar and u = hi - abar (one subtraction each), d_k
+ * minimises 1/2 d^T H d + g^T d over l <= d <= u by projected Newton steps whose arithmetic is fixed
+ * (gym_copter_amd/csrc/boxqp_solve.h states it; tests/boxqp_ref.py restates it):
+ *   start      x = clamp(-(H^-1 g)) with cs_rollout_lqr's Cholesky factor of H
+ *   iteration  gr = g + Hx; control a is clamped if (x_a <= l_a and gr_a > 0) or (x_a >= u_a and gr_a < 0), else free;
+ *              none free: stop.  The free block is solved with the same Cholesky on the masked matrix (H_ab where both
+ *              are free, delta_ab otherwise; right-hand side -(g_a + sum_{b clamped} H_ab x_b) on free rows, 0 on
+ *              clamped ones); s = that solution - x on free rows, 0 elsewhere; max|s| <= 1e-14 max(1, max|x|): stop;
+ *              Armijo backtracking x_c = clamp(x + t s), accepted when f(x_c) - f(x) <= 0.1 t gr^T s, else t <- 0.6 t,
+ *              at most 30 trials
+ *   cap        16 iterations.  An env that exhausts them (or an iteration none of whose trials is accepted), or whose
+ *              masked factor has a pivot <= 0 or not finite, gets ok = 0; its outputs are written regardless.
+ * d_k = x; the free rows of K_k are -(H_ff)^-1 Qux_f (the masked factor, the masked right-hand side, column by column),
+ * its clamped rows are 0.  S, s, dV1 += d^T Qu and dV2 += 1/2 d^T Quu d (the unregularised Quu) are cs_rollout_lqr's
+ * expressions at these K, d.  The first step of a lane with a NEXT_STEP reset pending (the env ignores its action:
+ * Qux = 0, Quu = R) takes the start, clamped, and no iteration.  With lo = -inf and hi = +inf every output equals
+ * cs_rollout_lqr's bit for bit.
+ *
+ * cs_ilqr_box_forward is cs_rollout_feedback_states with one more operation after the rounding to float32:
+ * a = a < lo ? lo : (a > hi ? hi : a) in float32 (a NaN stays a NaN).  The clamped value is what actions_out_dev
+ * receives and what the step takes; the outputs are bit-identical to cs_rollout_states fed actions_out_dev. */
+typedef struct cs_ilqr_box_io {
+  uint32_t struct_size;        /* sizeof(cs_ilqr_box_io) */
+  uint32_t reserved_;          /* 0 */
+  const float* lo_dev;         /* [A] float32, required; -inf allowed */
+  const float* hi_dev;         /* [A] float32, required; +inf allowed; lo <= hi is the caller's to guarantee */
+  uint8_t* clamped_dev;        /* [K,N] or NULL.  backward: bit a = control a held at its lower bound, bit 4+a = at its
+                                  upper (the set of the last iteration).  forward: the same bits for where the clamp
+                                  changed the action */
+  uint8_t* iters_dev;          /* [K,N] or NULL, backward only (forward: must be NULL): iterations used, 0 on a
+                                  resetting lane's step 1 */
+} cs_ilqr_box_io;
+int cs_ilqr_box_backward(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_lqr_io* lio, const cs_ilqr_box_io* bio,
+                         void* stream);
+int cs_ilqr_box_forward(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_feedback_io* fio,
+                        const cs_ilqr_box_io* bio, void* stream);
 
 /* An extended Kalman filter over the env step, on the device: K predict / update steps per env
  * in one call, the step Jacobian applied on the fly and never stored.  The filter's state -- the mean xhat [12] and the

@@ -13,7 +13,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_rts > profiles/rollout_rts_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_pf > profiles/rollout_pf_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_lqg > profiles/rollout_lqg_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_ukf > profiles/rollout_ukf_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_ukf > profiles/rollout_ukf_resources.txt
+    python3 tools/resource_table.py remarks.txt ilqr_box > profiles/ilqr_box_resources.txt"""
 import re
 import sys
 
@@ -81,7 +82,11 @@ HEADS = {"rollout_mlp": """\
 # lane-private LDS columns, 265 rows: one wavefront per CU; DESIGN.md section 22).""", "rollout_ukf": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_rollout_ukf.hip: the unscented Kalman filter
 # rollout_ukf_kernel<TASK, MODE, GYRO> (the covariance, its factor, the moment sum, the mean and the propagated centre
-# point in lane-private LDS columns, 258 rows: one wavefront per CU; DESIGN.md section 23)."""}
+# point in lane-private LDS columns, 258 rows: one wavefront per CU; DESIGN.md section 23).""", "ilqr_box": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_ilqr_box.hip: the control-limited iLQR backward
+# ilqr_box_backward_kernel<TASK, MODE, GYRO> (rollout_lqr_kernel's LDS rows, not one more: the box-constrained programme
+# of each step runs in registers) and the clamped feedback forward ilqr_box_forward_kernel<TASK, MODE> (DESIGN.md
+# section 24)."""}
 
 
 def main(path, which="rollout_mlp"):
