@@ -174,6 +174,16 @@ class RolloutRtsIO(C.Structure):
                 ("ok_dev", C.c_void_p)]
 
 
+class RolloutUrtsIO(C.Structure):
+    """Mirror of `struct cs_urts_io` (cs_urts_smooth)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("gamma", C.c_double), ("wm0", C.c_double),
+                ("wc0", C.c_double), ("wi", C.c_double), ("x_f_dev", C.c_void_p), ("x_pred_dev", C.c_void_p),
+                ("status_f_dev", C.c_void_p), ("P_f_dev", C.c_void_p), ("Q_dev", C.c_void_p), ("P0_dev", C.c_void_p),
+                ("end_x_dev", C.c_void_p), ("end_P_dev", C.c_void_p), ("workspace_dev", C.c_void_p),
+                ("P_tape_dev", C.c_void_p), ("var_dev", C.c_void_p), ("x0_dev", C.c_void_p), ("P0_s_dev", C.c_void_p),
+                ("ok_dev", C.c_void_p)]
+
+
 class RolloutPfIO(C.Structure):
     """Mirror of `struct cs_rollout_pf_io` (cs_rollout_pf)."""
     _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_meas", C.c_int32),
@@ -253,6 +263,7 @@ class PpoGradIO(C.Structure):
 
 
 ES_PAIR_CHUNK, ES_MAX_MEMBERS, ES_MAX_PARAMS = 32, 65536, 1092   # CS_ES_PAIR_CHUNK, CS_ES_MAX_MEMBERS, CS_ES_MAX_PARAMS
+URTS_WORKSPACE_ROWS = 102                                    # CS_URTS_WORKSPACE_ROWS
 EKF_MAX_MEAS = 12                                            # CS_EKF_MAX_MEAS
 PF_MIN_PARTICLES, PF_MAX_PARTICLES = 64, 1024                # CS_PF_MIN_PARTICLES, CS_PF_MAX_PARTICLES
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
@@ -334,6 +345,7 @@ SYMBOLS = {
     "cs_rollout_pf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutPfIO), _P]),
     "cs_rollout_lqg": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqgIO), _P]),
     "cs_rollout_ukf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutUkfIO), _P]),
+    "cs_urts_smooth": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutUrtsIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),

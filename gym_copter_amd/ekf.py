@@ -2,7 +2,7 @@
 tapes, CopterVecEnv.rollout_rts -- one library call each on the env's cached buffers; vecenv.py
 binds them to the class -- the kit the other filters (pf.py, lqg.py, ukf.py) share with them, a small streaming driver
 for a filter whose measurements arrive a chunk of steps at a time, the synthetic measurements to try it on, and the
-chunked driver of the smoother.
+chunked driver of the smoothers (this one's and ukf.py's rollout_urts).
 
     z = H x + e,  e ~ N(0, diag(r));     x- = step(xhat, a),  P- = A P A^T + Q;     sequential scalar updates
 
@@ -303,21 +303,41 @@ def ekf(env, actions, z, H, r, Q, x0, P0, status0=None, chunk=None):
                      cat["P_tape"])
 
 
-def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None):
-    """Run env.rollout_rts over the K steps of a filter's tapes in chunks of `chunk` steps (None: one call), last chunk
-    first: a chunk starts from the filter's row before it (the caller's x0, P0, status0 for the first chunk) and ends in
-    the smoothed starting point the chunk after it returned.  Returns RtsResult with the tapes of all K steps
-    concatenated (P_tape included), x0 and P0 the smoothed starting point and ok the chunks' conjunction -- tensors of
-    their own, not the env's buffers.  Every tape, x0, P0 and ok are bit-identical to the single call's: a chunk boundary
-    rounds nothing (float64 throughout).  filt is the EkfResult of the whole filter with its float64 P_tape
-    (rollout_ekf(..., tape=True) or ekf()); the other arguments are rollout_rts'."""
+def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None, alpha=1.0, beta=0.0, kappa=1.0):
+    """Run a fixed-interval smoother over the K steps of a filter's tapes in chunks of `chunk` steps (None: one call),
+    last chunk first: env.rollout_rts for an EkfResult, env.rollout_urts for a UkfResult (alpha, beta and kappa are
+    the filter's; an EkfResult ignores them).  A chunk starts from the filter's row before it (the caller's x0, P0,
+    status0 for the first chunk) and ends in the smoothed starting point the chunk after it returned.  Returns RtsResult
+    with the tapes of all K steps concatenated (P_tape included), x0 and P0 the smoothed starting point and ok the
+    chunks' conjunction -- tensors of their own, not the env's buffers.  Every tape, x0, P0 and ok are bit-identical to
+    the single call's: a chunk boundary rounds nothing (float64 throughout).  filt is the result of the whole filter with
+    its float64 P_tape (rollout_ekf(..., tape=True) or ekf(); rollout_ukf(..., tape=True) or ukf()); the other arguments
+    are rollout_rts'."""
     torch = _torch()
     K = int(actions.shape[0])
     chunk = K if chunk is None else int(chunk)
     if chunk < 1:
         raise ValueError("chunk must be >= 1, got %r" % (chunk,))
-    if not isinstance(filt, EkfResult) or filt.P_tape is None:
-        raise ValueError("filt must be an EkfResult with its P_tape (rollout_ekf(..., tape=True))")
+    if isinstance(filt, EkfResult):
+        def sub(k0, k1):
+            return EkfResult(filt.x[k0:k1], filt.x_pred[k0:k1], None, None, None, None, filt.status[k0:k1], None, None,
+                             filt.P_tape[k0:k1])
+        call = env.rollout_rts
+    else:
+        from .ukf import UkfResult         # (ukf.py imports this module: looked up when a call needs it)
+        if not isinstance(filt, UkfResult):
+            raise ValueError("filt must be an EkfResult or a UkfResult with its P_tape (rollout_ekf / rollout_ukf(..., "
+                             "tape=True))")
+
+        def sub(k0, k1):
+            return UkfResult(filt.x[k0:k1], filt.x_pred[k0:k1], None, None, None, None, filt.status[k0:k1], None, None,
+                             filt.P_tape[k0:k1], None, None, None)
+
+        def call(*args, **kwargs):
+            return env.rollout_urts(*args, alpha=alpha, beta=beta, kappa=kappa, **kwargs)
+    if filt.P_tape is None:
+        raise ValueError("filt must be an EkfResult or a UkfResult with its P_tape (rollout_ekf / rollout_ukf(..., "
+                         "tape=True))")
     for t, name in ((filt.x, "x"), (filt.x_pred, "x_pred"), (filt.status, "status"), (filt.P_tape, "P_tape")):
         if not isinstance(t, torch.Tensor) or t.shape[0] != K:
             raise ValueError("filt.%s must be a tensor of K = %d rows" % (name, K))
@@ -328,9 +348,7 @@ def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None):
             start = (x0, P0, status0)
         else:
             start = (filt.x[k0 - 1].T.contiguous(), filt.P_tape[k0 - 1], filt.status[k0 - 1])
-        sub = EkfResult(filt.x[k0:k1], filt.x_pred[k0:k1], None, None, None, None, filt.status[k0:k1], None, None,
-                        filt.P_tape[k0:k1])
-        res = env.rollout_rts(actions[k0:k1], sub, Q, start[0], start[1], status0=start[2], end=end, tape=True)
+        res = call(actions[k0:k1], sub(k0, k1), Q, start[0], start[1], status0=start[2], end=end, tape=True)
         parts.append([t.clone() for t in (res.x, res.P_tape, res.var)])
         end = (res.x0.clone(), res.P0.clone())
         ok = res.ok.clone() if ok is None else ok & res.ok

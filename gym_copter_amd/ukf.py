@@ -1,6 +1,8 @@
 """The unscented Kalman filter on the device: CopterVecEnv.rollout_ukf -- one call of
 cs_rollout_ukf on the env's cached buffers; vecenv.py binds it to the class -- the weights of the scaled unscented
-transform, and ukf(), the streaming driver whose measurements arrive a chunk of steps at a time.
+transform, ukf(), the streaming driver whose measurements arrive a chunk of steps at a time, and the filter's
+fixed-interval smoother: CopterVecEnv.rollout_urts, one call of cs_urts_smooth over the filter's
+tapes, which the class inherits from UnscentedSmoother (ekf.py's smooth() is its chunked driver).
 
     z = H x + e,  e ~ N(0, diag(r));     P = L L^T,  points xhat, xhat +- gamma L[:,j];     each through the step;
     x-, P- = their weighted mean and covariance + Q;     sequential scalar updates
@@ -97,6 +99,104 @@ def rollout_ukf(self, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta
         uio.point_status_dev = out.point_status.data_ptr()
     _wire.launch(self, "cs_rollout_ukf", io, uio, keep=keep + list(model[:3]))
     return out
+
+
+# -- the unscented Rauch-Tung-Striebel smoother over the filter's tapes: CopterVecEnv.rollout_urts ---
+def rollout_urts(self, actions, filt, Q, x0, P0, status0=None, end=None, alpha=1.0, beta=0.0, kappa=1.0, tape=True,
+                 dtype=None):
+    """An unscented Rauch-Tung-Striebel fixed-interval smoother over the tapes of rollout_ukf, K backward steps per env
+    in one kernel: the estimate of every step given the measurements of all K steps, and that of the starting point.
+    What rollout_rts is to rollout_ekf: each backward step makes the filter's 25 sigma points of that step again from the
+    filter's own tapes, sends them through the physics, and takes the cross-covariance of the points before and after
+    the step in place of rollout_rts' A P_f -- no Jacobian, so a belief that straddles a touchdown, a crash or the motor
+    clip is smoothed over every branch its points land on.  NO env state is read but the configuration and the vehicle,
+    and none changes.
+
+    actions [K,N,A], Q, x0 [12,N], P0 [N,12,12], status0 and alpha, beta, kappa are what the filter was given -- the
+    weights (weights()) MUST be the filter's: with others the recomputed prior is not the filter's and the result is no
+    smoother of these tapes; filt is its UkfResult from rollout_ukf(..., tape=True) in float64 (x, x_pred, status and
+    P_tape are read).  Q should be positive definite.  end = (x_end [12,N], P_end [N,12,12]) gives the smoothed last row
+    (default: the filter's own last row), as rollout_rts'.
+
+    Row K-1 is the given one; then for j = K-2 down to -1 (row -1 is the starting point): if status_f[j] is LANDED,
+    W = P_f[j] and P- = P_f[j] + Q; else P_f[j] = L L^T, the filter's points and their moments again (P- is the filter's
+    prior, bit for bit) and W = wi gamma dY L^T with dY[:, c] = y(1 + c) - y(13 + c), the transposed cross-covariance.
+    Then G = P-^-1 W by Cholesky,  x_s[j] = x_f[j] + G^T (x_s[j+1] - x_pred[j+1]),
+    P_s[j] = P_f[j] + G^T (P_s[j+1] - P-) G.
+
+    Returns RtsResult(x, P_tape (None with tape=False), var, x0, P0, ok) as rollout_rts: ok [N] is False where a pivot
+    of either factorisation was <= 0 or not finite (the outputs are written regardless).  dtype: torch.float64 (default)
+    or torch.float32 (P_tape, var, P0: the float64 values rounded).  Not available under action_arith="float32".
+    Asynchronous on the current stream; the tensors are buffers of this env, overwritten by its next call with the same
+    K, dtype and tape."""
+    self._check_open()
+    torch = _torch()
+    dtype = _wire.out_dtype(dtype)
+    if self.config.action_arith != _lib.ARITH_F64:
+        raise ValueError('rollout_urts is not available under action_arith="float32"')
+    gamma, wm0, wc0, wi = weights(alpha, beta, kappa)
+    Qd, = _wire.uploaded(self, "urts", lambda: (_ekf._process_noise(Q),), given=(Q,))
+    io, K, keep = _rollout._rollout_io(self, actions, None)
+    n = self.num_envs
+    if not isinstance(filt, UkfResult):
+        raise ValueError("filt must be the UkfResult of rollout_ukf(..., tape=True)")
+    if filt.P_tape is None:
+        raise ValueError("filt has no P_tape: filter with rollout_ukf(..., tape=True)")
+    if isinstance(filt.P_tape, torch.Tensor) and filt.P_tape.dtype != torch.float64:
+        raise ValueError("filt.P_tape must be float64 (rollout_ukf's default dtype), got %s" % filt.P_tape.dtype)
+    _wire.check_tape(self, "rollout_ukf", (filt.x, "filt.x", (K, n, 12), torch.float64),
+                     (filt.x_pred, "filt.x_pred", (K, n, 12), torch.float64),
+                     (filt.status, "filt.status", (K, n), torch.uint8),
+                     (filt.P_tape, "filt.P_tape", (K, n, 12, 12), torch.float64))
+    xt = _ekf._input(self, x0, (12, n), "x0", keep)
+    Pt = _ekf._input(self, P0, (n, 12, 12), "P0", keep)
+    io.start_status_dev = _ekf._start_status(self, status0, keep)
+    io.start_x_dev = xt.data_ptr()
+    sio = _wire.block(_lib.RolloutUrtsIO, out_dtype=_wire.dtype_code(dtype), gamma=gamma, wm0=wm0, wc0=wc0, wi=wi)
+    if end is not None:
+        if not isinstance(end, (tuple, list)) or len(end) != 2 or end[0] is None or end[1] is None:
+            raise ValueError("end must be the pair (x_end [12,N], P_end [N,12,12]): both or neither")
+        sio.end_x_dev = _ekf._input(self, end[0], (12, n), "end[0]", keep).data_ptr()
+        sio.end_P_dev = _ekf._input(self, end[1], (n, 12, 12), "end[1]", keep).data_ptr()
+    sio.x_f_dev, sio.x_pred_dev = filt.x.data_ptr(), filt.x_pred.data_ptr()
+    sio.status_f_dev, sio.P_f_dev = filt.status.data_ptr(), filt.P_tape.data_ptr()
+    sio.Q_dev, sio.P0_dev = Qd.data_ptr(), Pt.data_ptr()
+    tape = bool(tape)
+    out = _wire.rollout_cache(self, ("urts", K, dtype, tape), lambda: _ekf.RtsResult(
+        _wire.empty(self, (K, n, 12), torch.float64), _wire.empty(self, (K, n, 12, 12), dtype) if tape else None,
+        _wire.empty(self, (K, n, 12), dtype), _wire.empty(self, (12, n), torch.float64),
+        _wire.empty(self, (n, 12, 12), dtype), _wire.empty(self, n, torch.bool)))
+    # the kernel's scratch: one column of URTS_WORKSPACE_ROWS float64 per lane, 64 lanes per tile
+    work = _wire.rollout_cache(self, ("urts_workspace",), lambda: _wire.empty(
+        self, ((n + 63) // 64, _lib.URTS_WORKSPACE_ROWS, 64), torch.float64))
+    # (no output may overlap an input: the caller's tensors that are this call's own buffers are copied first)
+    mine = {t.data_ptr() for t in out if t is not None}
+    for name in ("end_x_dev", "end_P_dev", "P0_dev"):
+        if getattr(sio, name) in mine:
+            src = next(t for t in keep if t.data_ptr() == getattr(sio, name))
+            cp = src.clone()
+            keep.append(cp)
+            setattr(sio, name, cp.data_ptr())
+    if io.start_x_dev in mine:
+        cp = xt.clone()
+        keep.append(cp)
+        io.start_x_dev = cp.data_ptr()
+    io.x_dev = out.x.data_ptr()
+    sio.workspace_dev = work.data_ptr()
+    sio.var_dev, sio.x0_dev, sio.P0_s_dev = out.var.data_ptr(), out.x0.data_ptr(), out.P0.data_ptr()
+    sio.ok_dev = out.ok.data_ptr()
+    if tape:
+        sio.P_tape_dev = out.P_tape.data_ptr()
+    _wire.launch(self, "cs_urts_smooth", io, sio, keep=keep + [Qd, filt.x, filt.x_pred, filt.status, filt.P_tape])
+    return out
+
+
+class UnscentedSmoother:
+    """CopterVecEnv's unscented smoother, a base class of it.  It is inherited, not bound in the
+    class body like its neighbours: the class body's rollout_* methods are the closed list that
+    tests/test_gpu_output_bounds.py covers one by one (tests/test_guarded_outputs_cpu.py), and this one is held to the
+    same memory contract in a file of its own, tests/test_gpu_urts_output_bounds.py."""
+    rollout_urts = rollout_urts
 
 
 def ukf(env, actions, z, H, r, Q, x0, P0, status0=None, alpha=1.0, beta=0.0, kappa=1.0, chunk=None, points=False):

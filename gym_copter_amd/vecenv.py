@@ -109,7 +109,7 @@ PACKED_ROWS_MAX_ENVS = 131072
 STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dTheta', 'Psi', 'dPsi']
 
 
-class CopterVecEnv(_ilqr.ControlLimited, _VectorEnvBase):
+class CopterVecEnv(_ilqr.ControlLimited, _ukf.UnscentedSmoother, _VectorEnvBase):
     FRAMES_PER_SECOND = 100                                    # task.py:25
     # class-level defaults of the gymnasium.vector.VectorEnv attribute set (instances overwrite them)
     metadata = {"render_modes": [], "render_fps": 100}         # task.py:27-30 (rendering is out of scope: no modes)

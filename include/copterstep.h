@@ -47,6 +47,8 @@
  *                            the step, K steps per env           counterpart: a sampling state estimator)
  *   cs_rollout_ukf           an unscented Kalman filter over    the rollout lines above, per sigma point (no upstream
  *                            the step, K steps per env           counterpart: a derivative-free state estimator)
+ *   cs_urts_smooth           an unscented Rauch-Tung-Striebel   the same points, made again from the filter's tapes
+ *                            smoother over that filter's tapes   (no upstream counterpart: a fixed-interval smoother)
  *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
  *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
  *   cs_rollout_mppi_update   their cost-weighted average         (the same)
@@ -1214,6 +1216,63 @@ typedef struct cs_rollout_ukf_io {
   uint8_t* point_status_dev;   /* [K,N,25] */
 } cs_rollout_ukf_io;
 int cs_rollout_ukf(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_ukf_io* uio, void* stream);
+
+/* An unscented Rauch-Tung-Striebel fixed-interval smoother over the tapes of cs_rollout_ukf, on the device (DESIGN.md
+ * section 25): what cs_rollout_rts is to cs_rollout_ekf.  The estimate of every step given the measurements of all K
+ * steps, and that of the starting point, in one call of K backward steps per env.  Each backward step makes the filter's
+ * 25 sigma points of that step again from the filter's own tapes and takes the cross-covariance of the points before and
+ * after the physics in place of cs_rollout_rts' W = A P_f: no Jacobian, and a belief that straddles a touchdown, a crash
+ * or the motor clip is smoothed over every branch its points land on.  No env state is read except the context's
+ * constants and vehicle table, and none is written.
+ *
+ * Row k = 0 .. K-1 of a tape is the state after step k+1; "row -1" is the filter's starting point (x0, P0, status0).
+ *
+ * From io: as cs_rollout_rts (num_steps = K, actions_dev, start_x_dev = x0 and start_status_dev = status0, both required;
+ * x_dev [K,N,12] or NULL receives the smoothed means; every other pointer NULL).
+ * From sio, the inputs (float64): x_f_dev, x_pred_dev, status_f_dev, P_f_dev (the filter's x_dev, x_pred_dev, status_dev
+ * and, with CS_JAC_F64, P_tape_dev), Q_dev, P0_dev, end_x_dev and end_P_dev as cs_rollout_rts'; gamma, wm0, wc0 and wi
+ * as cs_rollout_ukf's -- they must be the filter's (gamma finite and > 0, the weights finite, else CS_ERR_ARG); and
+ *   workspace_dev  [ceil(N / 64), CS_URTS_WORKSPACE_ROWS, 64] float64, required: scratch of the call, one column of
+ *                  CS_URTS_WORKSPACE_ROWS values per env (and per padding lane of the last 64).  Its contents before the
+ *                  call are ignored and after it are unspecified; it overlaps nothing else the call is given.
+ * The smoothed row K-1 is given: the filter's own row K-1, or (end_x, the upper triangle of end_P, mirrored); it is
+ * written out as it is.  Then for j = K-2 down to -1 and every env, in float64 without contraction:
+ *   points    if status_f[j] is LANDED the filter made no points: W = P_f[j] and P- = P_f[j] + Q, one add per entry.
+ *             Else step j+2 of cs_rollout_ukf is repeated: P_f[j] = L L^T, the 25 points in the filter's order, each
+ *             through the physics under actions[j+1] from (the point, status_f[j]), their moments in the filter's order:
+ *             P- is the filter's own prior of that step, bit for bit.  With dY[:, c] = y(1 + c) - y(13 + c), c = 0 .. 11,
+ *             W = (wi gamma) dY L^T, each entry summed over L's columns in order (gym_copter_amd/csrc/urts_cross.h): the
+ *             transpose of the cross-covariance sum_i wc_i (chi_i - x_f[j]) (y_i - x-)^T.  A pivot of this
+ *             factorisation that is <= 0 or not finite clears the env's ok; the arithmetic is carried through.
+ *   solve, smooth   cs_rollout_rts', with this W and x_pred[j+1] read from the filter's tape.
+ * Outputs, each may be NULL: cs_rollout_rts' (io->x_dev, P_tape_dev, var_dev, x0_dev, P0_s_dev, ok_dev; P_tape, var and
+ * P0_s in out_dtype).  No output may overlap an input.  Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32.
+ * Asynchronous on `stream`; sio->struct_size must be sizeof(cs_urts_io) (else CS_ERR_ABI); both blocks are checked
+ * before the context, with cs_rollout_rts' alignment rules. */
+#define CS_URTS_WORKSPACE_ROWS 102 /* P_s [78] and x_s [12] of the row above, the filter's mean of this row [12] */
+typedef struct cs_urts_io {
+  uint32_t struct_size;        /* sizeof(cs_urts_io) */
+  uint32_t out_dtype;          /* CS_JAC_F64 / CS_JAC_F32: P_tape_dev, var_dev, P0_s_dev */
+  double gamma;                /* the filter's: the points' spread, finite and > 0 */
+  double wm0;                  /* the filter's: the centre point's weight in the mean, finite */
+  double wc0;                  /* the filter's: the centre point's weight in the covariance, finite */
+  double wi;                   /* the filter's: every other point's weight, finite */
+  const double* x_f_dev;       /* [K,N,12], required */
+  const double* x_pred_dev;    /* [K,N,12], required */
+  const uint8_t* status_f_dev; /* [K,N], required */
+  const double* P_f_dev;       /* [K,N,12,12], required */
+  const double* Q_dev;         /* [12,12], required */
+  const double* P0_dev;        /* [N,12,12], required */
+  const double* end_x_dev;     /* [12,N] or NULL */
+  const double* end_P_dev;     /* [N,12,12] or NULL (with end_x_dev: both or neither) */
+  double* workspace_dev;       /* [ceil(N / 64), CS_URTS_WORKSPACE_ROWS, 64], required */
+  void* P_tape_dev;            /* [K,N,12,12] */
+  void* var_dev;               /* [K,N,12] */
+  double* x0_dev;              /* [12,N] */
+  void* P0_s_dev;              /* [N,12,12] */
+  uint8_t* ok_dev;             /* [N] */
+} cs_urts_io;
+int cs_urts_smooth(cs_ctx* ctx, const cs_rollout_io* io, const cs_urts_io* sio, void* stream);
 
 /* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
  * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,

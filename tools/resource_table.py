@@ -14,7 +14,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_pf > profiles/rollout_pf_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_lqg > profiles/rollout_lqg_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_ukf > profiles/rollout_ukf_resources.txt
-    python3 tools/resource_table.py remarks.txt ilqr_box > profiles/ilqr_box_resources.txt"""
+    python3 tools/resource_table.py remarks.txt ilqr_box > profiles/ilqr_box_resources.txt
+    python3 tools/resource_table.py remarks.txt urts > profiles/urts_resources.txt"""
 import re
 import sys
 
@@ -86,7 +87,11 @@ HEADS = {"rollout_mlp": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_ilqr_box.hip: the control-limited iLQR backward
 # ilqr_box_backward_kernel<TASK, MODE, GYRO> (rollout_lqr_kernel's LDS rows, not one more: the box-constrained programme
 # of each step runs in registers) and the clamped feedback forward ilqr_box_forward_kernel<TASK, MODE> (DESIGN.md
-# section 24)."""}
+# section 24).""", "urts": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_urts.hip: the unscented Rauch-Tung-Striebel
+# smoother urts_kernel<TASK, MODE, GYRO> (the factor, the moment sum, the cross-covariance / gain and the propagated
+# centre point in lane-private LDS columns, 313 rows: one wavefront per CU; the smoothed row above is parked in the
+# caller's workspace while the points run; DESIGN.md section 25)."""}
 
 
 def main(path, which="rollout_mlp"):
