@@ -6,7 +6,7 @@ and the Gymnasium-style vector-env host class.  See DESIGN.md and INTEGRATION.md
 from ._lib import CopterStepError  # noqa: F401
 from .vecenv import (BoxGains, CopterVecEnv, EkfResult, LqgResult, LqrGains, MlpRollout, MppiCosts, MppiUpdate,  # noqa: F401
                      PfResult, Rollout, RtsResult, StepJacobian, UkfResult)
-from .vecenv import ActorCritic, MppiTemperature, Population, PpoGrad, mppi_knots  # noqa: F401
+from .vecenv import ActorCritic, MppiTemperature, Population, PpoGrad, RolloutTangents, mppi_knots  # noqa: F401
 from .autodiff import differentiable_mlp_rollout, differentiable_rollout, ppo_loss  # noqa: F401
 from . import mlp  # noqa: F401
 from .ilqr import ilqr  # noqa: F401
@@ -17,6 +17,7 @@ from .lqg import lqg, measurement_noise  # noqa: F401
 from .ukf import ukf  # noqa: F401
 from .es import es  # noqa: F401
 from .ppo import ppo  # noqa: F401
+from .sysid import IdentifyResult, identify  # noqa: F401
 from .spaces import box_class as _box_class
 
 # The Box class the envs' spaces are instances of: gymnasium.spaces.Box when Gymnasium is importable (so that

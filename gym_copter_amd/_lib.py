@@ -94,6 +94,14 @@ class RolloutParamIO(C.Structure):
                 ("g_vehicle_dev", C.c_void_p), ("g_force_dev", C.c_void_p)]
 
 
+class JvpIO(C.Structure):
+    """Mirror of `struct cs_jvp_io` (cs_jvp_rollout)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_dirs", C.c_int32),
+                ("reserved_", C.c_uint32), ("t_actions_dev", C.c_void_p), ("t_x0_dev", C.c_void_p),
+                ("t_vehicle_dev", C.c_void_p), ("t_force_dev", C.c_void_p), ("vehicle_dev", C.c_void_p),
+                ("t_x_dev", C.c_void_p), ("t_reward_dev", C.c_void_p)]
+
+
 class RolloutMlpIO(C.Structure):
     """Mirror of `struct cs_rollout_mlp_io` (cs_rollout_mlp_states / cs_rollout_mlp_vjp)."""
     _fields_ = [("struct_size", C.c_uint32), ("hidden", C.c_int32), ("params_dev", C.c_void_p),
@@ -263,6 +271,7 @@ class PpoGradIO(C.Structure):
 
 
 ES_PAIR_CHUNK, ES_MAX_MEMBERS, ES_MAX_PARAMS = 32, 65536, 1092   # CS_ES_PAIR_CHUNK, CS_ES_MAX_MEMBERS, CS_ES_MAX_PARAMS
+JVP_MAX_DIRS = 64                                            # CS_JVP_MAX_DIRS
 URTS_WORKSPACE_ROWS = 102                                    # CS_URTS_WORKSPACE_ROWS
 EKF_MAX_MEAS = 12                                            # CS_EKF_MAX_MEAS
 PF_MIN_PARTICLES, PF_MAX_PARTICLES = 64, 1024                # CS_PF_MIN_PARTICLES, CS_PF_MAX_PARTICLES
@@ -329,6 +338,7 @@ SYMBOLS = {
     "cs_rollout_vjp": (C.c_int, [_P, C.POINTER(RolloutIO), _P]),
     "cs_rollout_states_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutParamIO), _P]),
     "cs_rollout_vjp_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutParamIO), _P]),
+    "cs_jvp_rollout": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(JvpIO), _P]),
     "cs_rollout_mlp_states": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMlpIO), _P]),
     "cs_rollout_mlp_vjp": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMlpIO), _P]),
     "cs_rollout_mlp_vjp_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMlpIO), C.POINTER(RolloutMlpExIO),

@@ -28,6 +28,7 @@ def _function():
             # (the vehicle is saved, not kept as an attribute: autograd then refuses a backward after an in-place change
             # of it, so the backward may skip re-checking the table the forward's rollout_states checked)
             ctx.save_for_backward(actions, x, status, vehicle)
+            ctx.save_for_forward(actions, x, status, vehicle)   # (what jvp needs: the same tape)
             ctx.env, ctx.state = env, state
             ctx.params = vehicle is not None or force is not None
             ctx.want = (x0 is not None, vehicle is not None and vehicle.requires_grad, force is not None)
@@ -49,6 +50,18 @@ def _function():
             return (ga.to(actions.dtype), g0.clone() if (want_x0 and g0 is not None) else None,
                     gv.clone() if want_v else None, gf.clone() if want_f else None, None, None)
 
+        @staticmethod
+        def jvp(ctx, t_actions, t_x0, t_vehicle, t_force, *_):
+            # forward mode (torch.autograd.forward_ad): the tangents of x and reward, CopterVecEnv.rollout_jvp
+            actions, x, status, vehicle = ctx.saved_tensors
+            if t_actions is None and t_x0 is None and t_vehicle is None and t_force is None:
+                return torch.zeros_like(x), torch.zeros_like(x[..., 0]), None, None, None
+            t = ctx.env.rollout_jvp(actions, Rollout(x, None, None, None, status), t_actions=t_actions, t_x0=t_x0,
+                                    t_vehicle=t_vehicle, t_force=t_force, state=ctx.state, vehicle=vehicle,
+                                    dtype=torch.float64, check_vehicle=False)
+            # (copies: the env's buffers are overwritten by its next call)
+            return t.x.clone(), t.reward.clone(), None, None, None
+
     _FN = RolloutFunction
     return _FN
 
@@ -65,19 +78,26 @@ def differentiable_rollout(env, actions, state=None, vehicle=None):
     vehicle: a [12,N] float64 device tensor of the vehicle rows (env.VEHICLE_ROWS) to roll out with instead of the env's
     own (rollout_states(..., vehicle=)); when it requires grad it receives dL / d vehicle, and a state["force"] that
     requires grad (float64 [3,N]) receives dL / d force (CopterVecEnv.rollout_vjp_params).  With
-    neither, the rollout is differentiated with respect to the actions and x0 only, as without them."""
+    neither, the rollout is differentiated with respect to the actions and x0 only, as without them.
+
+    Forward mode: under torch.autograd.forward_ad.dual_level(), duals on `actions`, state["x"], `vehicle` or
+    state["force"] come out with tangents on x and reward (CopterVecEnv.rollout_jvp)."""
     torch = _torch()
     if not isinstance(actions, torch.Tensor) or actions.dtype != torch.float32:
         raise ValueError("actions must be a float32 torch tensor of shape (K, %d, %d)" % (env.num_envs, env.action_dim))
     if actions.device != env.device:
         raise ValueError("actions must be on %s, got %s" % (env.device, actions.device))
+
+    def wanted(t):  # a gradient (reverse mode) or a tangent (a dual tensor of torch.autograd.forward_ad) is asked for
+        return isinstance(t, torch.Tensor) and (t.requires_grad or
+                                                torch.autograd.forward_ad.unpack_dual(t).tangent is not None)
     x0 = None
-    if state is not None and isinstance(state.get("x"), torch.Tensor) and state["x"].requires_grad:
+    if state is not None and wanted(state.get("x")):
         if state["x"].dtype != torch.float64:
             raise ValueError("state['x'] must be float64 to receive a gradient, got %s" % state["x"].dtype)
         x0 = state["x"]
     force = None
-    if state is not None and isinstance(state.get("force"), torch.Tensor) and state["force"].requires_grad:
+    if state is not None and wanted(state.get("force")):
         if state["force"].dtype != torch.float64:
             raise ValueError("state['force'] must be float64 to receive a gradient, got %s" % state["force"].dtype)
         force = state["force"]

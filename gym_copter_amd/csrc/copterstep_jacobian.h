@@ -66,6 +66,11 @@ struct ParamView {
 // (outside stream order: the first call with an override or a parameter gradient allocates)
 int param_view(cs_ctx* ctx, const char* who, bool want_coef, bool want_gcoef, ParamView* out);
 
+// (copterstep_rollout_grad.hip) the DevState a call with a vehicle override launches on: `vehicle_dev` [12, n] folded
+// into pv.coef_dev on `stream` (nullptr: *out = s0), as cs_rollout_states_ex folds it
+int override_vehicle(const ParamView& pv, const double* vehicle_dev, const DevState& s0, hipStream_t stream,
+                     const char* who, DevState* out);
+
 // (copterstep_api.hip) a context's scratch of workgroup partials, one buffer per user: cs_mlp_param_grad
 // (copterstep_mlp_grad.hip), cs_es_gradient (copterstep_rollout_es.hip) and cs_ppo_grad (copterstep_ppo_grad.hip).
 // `bytes` is what the first call allocates (refused while `stream` is being captured) and cs_destroy releases; every

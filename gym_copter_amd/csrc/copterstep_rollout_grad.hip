@@ -243,6 +243,14 @@ int override_state(const ParamView& pv, const cs_rollout_param_io* pio, const De
 
 }  // namespace
 
+// override_state for cs_jvp_rollout (copterstep_jvp.hip), whose block carries its own vehicle_dev
+int override_vehicle(const ParamView& pv, const double* vehicle_dev, const DevState& s0, hipStream_t stream,
+                     const char* who, DevState* out) {
+  cs_rollout_param_io pio{};
+  pio.vehicle_dev = vehicle_dev;
+  return override_state(pv, &pio, s0, stream, who, out);
+}
+
 // the argument block, checked before the context (a caller's layout error is reported as such, without a device)
 int check_rollout_io(const cs_rollout_io* io, const char* who, bool vjp) {
   const std::string w(who);

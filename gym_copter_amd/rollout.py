@@ -256,3 +256,75 @@ def _vjp(self, actions, rollout, gx, gr, state, dtype, params=False, vehicle=Non
     pio.g_vehicle_dev, pio.g_force_dev = gv.data_ptr(), gf.data_ptr()
     _wire.launch(self, "cs_rollout_vjp_ex", io, pio, keep=keep)
     return ga, g0, gv, gf
+
+
+# CopterVecEnv.rollout_jvp's result (device tensors, [D, K, N, ...]; without the D axis for inputs without it)
+RolloutTangents = collections.namedtuple("RolloutTangents", "x reward")
+
+
+def rollout_jvp(self, actions, rollout, t_actions=None, t_x0=None, t_vehicle=None, t_force=None, state=None,
+                vehicle=None, dtype=None, check_vehicle=True):
+    """Forward-mode tangents of a rollout: D input directions pushed through the K steps, RolloutTangents(x [D,K,N,12]
+    = the tangent of rollout.x, reward [D,K,N] = the tangent of rollout.reward).  The direction axis leads: t_actions
+    [D,K,N,A] (on the actions as step() receives them), t_x0 [D,12,N] (on state["x"], or on the stored start's decoded
+    words), t_vehicle [D,12,N] (on the vehicle rows VEHICLE_ROWS) and t_force [D,3,N] newtons (on the start's pending
+    force), float64, each None = zero, at least one given, all with the same D.  Inputs without the direction axis mean
+    D = 1, and the outputs then come back without it.  `rollout`, `state` and `vehicle` are rollout_vjp_params': the
+    tape rollout_states(actions, state, vehicle=) returned, its start and its override.
+
+    The linear map is the one whose transpose rollout_vjp / rollout_vjp_params apply, at the tape's points (DESIGN
+    section 26): <gx, t_x> + <gr, t_reward> = <g_actions, t_actions> + <g_x0, t_x0> + <g_vehicle, t_vehicle> + <g_force,
+    t_force> per env.  A pending NEXT_STEP reset zeroes that env's x0, first-action and force tangents; the force
+    tangent is exactly 0 where none is pending or it never integrates; vehicle rows that do not enter the configuration
+    contribute exactly 0.  With t_vehicle, t_force or vehicle: not available with action_arith="float32".  dtype:
+    torch.float64 (default) or torch.float32 (the float64 values rounded).  Asynchronous on the current stream; the
+    returned tensors are buffers of this env, overwritten by the next call with the same D, K and dtype."""
+    self._check_open()
+    torch = _torch()
+    dtype = _wire.out_dtype(dtype)
+    io, K, keep = _rollout_io(self, actions, state)
+    n, ad = self.num_envs, self.action_dim
+    _tape(self, io, rollout, K)
+    given = [("t_actions", t_actions, (K, n, ad)), ("t_x0", t_x0, (12, n)),
+             ("t_vehicle", t_vehicle, (len(self.VEHICLE_ROWS), n)), ("t_force", t_force, (3, n))]
+    dims = {name: (len(t.shape) if hasattr(t, "shape") else np.ndim(t)) - len(shape)
+            for name, t, shape in given if t is not None}
+    if not dims:
+        raise ValueError("rollout_jvp needs at least one of t_actions, t_x0, t_vehicle, t_force")
+    if set(dims.values()) - {0, 1} or len(set(dims.values())) != 1:
+        raise ValueError("the input tangents must all have the direction axis [D, ...] or all lack it (D = 1): %s"
+                         % ", ".join("%s must have shape (D,) + %s or %s" % (name, shape, shape)
+                                     for name, t, shape in given if t is not None))
+    batched = set(dims.values()) == {1}
+    D = None
+    ptrs = {}
+    for name, t, shape in given:
+        if t is None:
+            continue
+        d = int(t.shape[0] if hasattr(t, "shape") else np.shape(t)[0]) if batched else 1
+        if D is None:
+            D = d
+        if d != D or D < 1 or D > _lib.JVP_MAX_DIRS:
+            raise ValueError("%s: the input tangents must share one D in [1, %d], got %d and %d"
+                             % (name, _lib.JVP_MAX_DIRS, D, d))
+        tt = _wire.tensor(self, t, ((D,) if batched else ()) + shape, torch.float64, name, keep, floating=True,
+                          non_blocking=True)
+        ptrs[name] = tt.data_ptr()
+    jio = _wire.block(_lib.JvpIO, out_dtype=_wire.dtype_code(dtype), num_dirs=D,
+                      t_actions_dev=ptrs.get("t_actions"), t_x0_dev=ptrs.get("t_x0"),
+                      t_vehicle_dev=ptrs.get("t_vehicle"), t_force_dev=ptrs.get("t_force"))
+    if vehicle is not None:
+        jio.vehicle_dev = _param_io(self, vehicle, keep, check=check_vehicle).vehicle_dev
+    out = _wire.rollout_cache(self, ("jvp", D, K, dtype), lambda: RolloutTangents(
+        _wire.empty(self, (D, K, n, 12), dtype), _wire.empty(self, (D, K, n), dtype)))
+    jio.t_x_dev, jio.t_reward_dev = out.x.data_ptr(), out.reward.data_ptr()
+    _wire.launch(self, "cs_jvp_rollout", io, jio, keep=keep)
+    return out if batched else RolloutTangents(out.x[0], out.reward[0])
+
+
+class ForwardTangents:
+    """CopterVecEnv's forward-mode rollout tangents, a base class of it.  It is inherited, not bound
+    in the class body like its neighbours: the class body's rollout_* methods are the closed list that
+    tests/test_gpu_output_bounds.py covers one by one (tests/test_guarded_outputs_cpu.py), and this one is held to the
+    same memory contract in tests/test_gpu_jvp.py."""
+    rollout_jvp = rollout_jvp

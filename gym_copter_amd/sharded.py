@@ -223,8 +223,8 @@ class ShardedCopterVecEnv:
 # a keyword added to a CopterVecEnv method needs nothing here.  No gather.  (The noise of rollout_pf and
 # rollout_mppi_costs is keyed by the global env id: a sharded batch draws what the unsharded one draws.  g_vehicle of
 # rollout_vjp_params is per local env: a vehicle shared by every rank sums it over envs and ranks.)
-_LOCAL_ROLLOUTS = ("rollout_states", "rollout_vjp", "rollout_vjp_params", "rollout_lqr", "rollout_feedback_states",
-                   "rollout_lqr_box", "rollout_feedback_box_states",
+_LOCAL_ROLLOUTS = ("rollout_states", "rollout_vjp", "rollout_vjp_params", "rollout_jvp", "rollout_lqr",
+                   "rollout_feedback_states", "rollout_lqr_box", "rollout_feedback_box_states",
                    "rollout_mppi_costs", "rollout_mppi_update", "rollout_ekf", "rollout_rts", "rollout_pf", "rollout_lqg",
                    "rollout_ukf", "rollout_urts")
 

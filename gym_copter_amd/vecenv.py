@@ -37,7 +37,7 @@ from . import lqg as _lqg
 from . import ukf as _ukf
 from ._wire import _torch  # noqa: F401
 # the families' results and tables, importable from here as before they moved
-from .rollout import Rollout, StepJacobian  # noqa: F401
+from .rollout import Rollout, RolloutTangents, StepJacobian  # noqa: F401
 from .mlp_rollout import MlpRollout  # noqa: F401
 from .ilqr import BoxGains, LqrGains  # noqa: F401
 from .mppi import MPPI_MAX_KNOT, MppiCosts, MppiTemperature, MppiUpdate, mppi_knots  # noqa: F401
@@ -109,7 +109,7 @@ PACKED_ROWS_MAX_ENVS = 131072
 STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dTheta', 'Psi', 'dPsi']
 
 
-class CopterVecEnv(_ilqr.ControlLimited, _ukf.UnscentedSmoother, _VectorEnvBase):
+class CopterVecEnv(_ilqr.ControlLimited, _ukf.UnscentedSmoother, _rollouts.ForwardTangents, _VectorEnvBase):
     FRAMES_PER_SECOND = 100                                    # task.py:25
     # class-level defaults of the gymnasium.vector.VectorEnv attribute set (instances overwrite them)
     metadata = {"render_modes": [], "render_fps": 100}         # task.py:27-30 (rendering is out of scope: no modes)

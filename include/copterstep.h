@@ -670,6 +670,65 @@ typedef struct cs_rollout_param_io {
 int cs_rollout_states_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_param_io* pio, void* stream);
 int cs_rollout_vjp_ex(cs_ctx* ctx, const cs_rollout_io* io, const cs_rollout_param_io* pio, void* stream);
 
+/* Forward-mode tangents of a rollout (the lines differentiated are cs_rollout_vjp's:
+ * dynamics/__init__.py:114-197, :249-302; envs/task.py:77-137; envs/lander.py:46-74).  Where cs_rollout_vjp /
+ * cs_rollout_vjp_ex pull ONE cotangent back through the K steps, cs_jvp_rollout pushes D input directions forward: the
+ * shape for problems with a handful of inputs and K x 12 outputs (system identification by Gauss-Newton, disturbance
+ * estimation, the sensitivity of a plan to the vehicle, Gauss-Newton Hessian-vector products J^T (J v)).
+ *   t_actions_dev  [D,K,N,A] float64  tangent of the actions as cs_step receives them (the clip's derivative is 1 on
+ *                                     [0, 1], 0 outside), or NULL = zero
+ *   t_x0_dev       [D,12,N]  float64  tangent of the start state (an explicit start's x; with the stored start: the
+ *                                     decoded words), or NULL
+ *   t_vehicle_dev  [D,12,N]  float64  tangents of the raw rows of cs_set_vehicle_params (B, D, M, L, Ix, Iy, Iz, Jr,
+ *                                     maxrpm, G, rho, C_L), or NULL
+ *   t_force_dev    [D,3,N]   float64  newtons: tangent of the start's pending force (an explicit start's
+ *                                     start_force_dev, or the stored start's pending perturbation), or NULL
+ *   vehicle_dev    [12,N]             the vehicle of THIS call, exactly as cs_rollout_param_io's: the one that the
+ *                                     cs_rollout_states_ex that made the tape was given, or NULL = the env's own
+ *   t_x_dev        [D,K,N,12] out     tangent of x_dev row k;  t_reward_dev [D,K,N] out: tangent of reward_dev
+ * in out_dtype (CS_JAC_F64, or CS_JAC_F32: the float64 values rounded).  At least one input tangent and at least one
+ * output must be given; t_x_dev must be 16-byte aligned.  1 <= num_dirs <= CS_JVP_MAX_DIRS.
+ *
+ * io is used as cs_rollout_vjp uses it -- the same K, actions and start point; io->x_dev and io->status_dev are the
+ * forward's tape, READ, both required; a stored start is decoded again, so the env must not have been stepped, reset or
+ * set in between -- except that io's reward_dev, terminated_dev, truncated_dev, gx_dev, gr_dev, g_actions_dev and
+ * g_x0_dev must be NULL.  Every refusal is CS_ERR_ARG (CS_ERR_ABI for a wrong struct_size), its message starts with
+ * "cs_jvp_rollout:" and names the member; the blocks are checked before the context.
+ *
+ * The linear map is exactly the one whose transpose cs_rollout_vjp and cs_rollout_vjp_ex apply, at the tape's points:
+ * for every env, <gx, t_x> + <gr, t_reward> = <g_actions, t_actions> + <g_x0, t_x0> + <g_vehicle, t_vehicle> +
+ * <g_force, t_force>.  The storage rounding of the float32 modes is straight-through.  LANDED (task.py:86-87), ground
+ * contact, LEVELING (dynamics/__init__.py:174-175) and CRASHED rows behave as in cs_step_jacobian.  A lane with a
+ * NEXT_STEP reset pending at a stored start has its x0, first-action and force tangents zeroed by that reset; the steps
+ * after it still carry the vehicle tangent, including d(2 / M) times the new episode's draw.  The force tangent is
+ * exactly 0 where no force is pending (consumed, or an explicit start without start_force_dev) and where the force
+ * never integrates.  Vehicle rows that do not enter the configuration contribute exactly 0: B under CS_THRUST_LIFT, rho
+ * and C_L under CS_THRUST_B, Jr without rotor_gyro.  The reward tangent of step k is grad shaping(x_k) . t_x_k minus
+ * grad shaping(x_{k-1}) . t_x_{k-1} wherever the backward differentiates prev_shaping (lander.py:59-62; every step but
+ * the first, and the first of an explicit start without start_prev_shaping_dev); it is zero where the backward gives
+ * no reward gradient: a tilt, a prev_shaping of None, a reset, and the Hover tasks.
+ *
+ * With t_vehicle_dev, t_force_dev or vehicle_dev the call is refused under action_arith = CS_ARITH_F32, as
+ * cs_rollout_vjp_ex is; the plain tangents use the float64 motor law's derivative there, as cs_rollout_vjp does.  A
+ * vehicle_dev uses the context's scratch table as cs_rollout_states_ex does (first use allocates: outside graph
+ * capture; such calls on one context are ordered on one stream).  Nothing of the env is written.  Asynchronous on
+ * `stream`. */
+#define CS_JVP_MAX_DIRS 64
+typedef struct cs_jvp_io {
+  uint32_t struct_size;          /* sizeof(cs_jvp_io) */
+  uint32_t out_dtype;            /* CS_JAC_F64 / CS_JAC_F32: t_x_dev, t_reward_dev */
+  int32_t num_dirs;              /* D: 1 .. CS_JVP_MAX_DIRS */
+  uint32_t reserved_;            /* 0 */
+  const double* t_actions_dev;   /* [D,K,N,A] or NULL */
+  const double* t_x0_dev;        /* [D,12,N] or NULL */
+  const double* t_vehicle_dev;   /* [D,12,N] or NULL */
+  const double* t_force_dev;     /* [D,3,N] newtons, or NULL */
+  const double* vehicle_dev;     /* [12,N] float64 raw vehicle for this call, or NULL */
+  void* t_x_dev;                 /* [D,K,N,12] */
+  void* t_reward_dev;            /* [D,K,N] */
+} cs_jvp_io;
+int cs_jvp_rollout(cs_ctx* ctx, const cs_rollout_io* io, const cs_jvp_io* jio, void* stream);
+
 /* Differentiable CLOSED-LOOP rollouts under a fused MLP policy: analytic policy gradients
  * (backpropagation through the simulator) without a Python loop.  The loop replaced is lander.py:40-65 with a policy in
  * place of the random action -- observe, act, step -- K times.  A closed-loop rollout is K calls of cs_step with auto-reset

@@ -15,7 +15,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_lqg > profiles/rollout_lqg_resources.txt
     python3 tools/resource_table.py remarks.txt rollout_ukf > profiles/rollout_ukf_resources.txt
     python3 tools/resource_table.py remarks.txt ilqr_box > profiles/ilqr_box_resources.txt
-    python3 tools/resource_table.py remarks.txt urts > profiles/urts_resources.txt"""
+    python3 tools/resource_table.py remarks.txt urts > profiles/urts_resources.txt
+    python3 tools/resource_table.py remarks.txt rollout_jvp > profiles/rollout_jvp_resources.txt"""
 import re
 import sys
 
@@ -91,7 +92,10 @@ HEADS = {"rollout_mlp": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_urts.hip: the unscented Rauch-Tung-Striebel
 # smoother urts_kernel<TASK, MODE, GYRO> (the factor, the moment sum, the cross-covariance / gain and the propagated
 # centre point in lane-private LDS columns, 313 rows: one wavefront per CU; the smoothed row above is parked in the
-# caller's workspace while the points run; DESIGN.md section 25)."""}
+# caller's workspace while the points run; DESIGN.md section 25).""", "rollout_jvp": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_jvp.hip: the forward-mode rollout tangents
+# rollout_jvp_kernel<TASK, MODE, GYRO, PARAM> (6 KiB of LDS for the tangent rows; PARAM builds keep the direction
+# block's 2 x 11 coefficient tangents in lane-private LDS columns, 11 KiB more; DESIGN.md section 26)."""}
 
 
 def main(path, which="rollout_mlp"):
