@@ -5,14 +5,14 @@ and the Gymnasium-style vector-env host class.  See DESIGN.md and INTEGRATION.md
 """
 from ._lib import CopterStepError  # noqa: F401
 from .vecenv import (BoxGains, CopterVecEnv, EkfResult, LqgResult, LqrGains, MlpRollout, MppiCosts, MppiUpdate,  # noqa: F401
-                     PfResult, Rollout, RtsResult, StepJacobian, UkfResult)
+                     PfPaths, PfResult, PfSmoothResult, Rollout, RtsResult, StepJacobian, UkfResult)
 from .vecenv import ActorCritic, MppiTemperature, Population, PpoGrad, RolloutTangents, mppi_knots  # noqa: F401
 from .autodiff import differentiable_mlp_rollout, differentiable_rollout, ppo_loss  # noqa: F401
 from . import mlp  # noqa: F401
 from .ilqr import ilqr  # noqa: F401
 from .mppi import mppi  # noqa: F401
 from .ekf import ekf, measure, smooth  # noqa: F401
-from .pf import pf  # noqa: F401
+from .pf import pf, pf_smooth  # noqa: F401
 from .lqg import lqg, measurement_noise  # noqa: F401
 from .ukf import ukf  # noqa: F401
 from .es import es  # noqa: F401

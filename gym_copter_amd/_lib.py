@@ -206,6 +206,17 @@ class RolloutPfIO(C.Structure):
                 ("wq_tape_dev", C.c_void_p), ("anc_tape_dev", C.c_void_p)]
 
 
+class PfSmoothIO(C.Structure):
+    """Mirror of `struct cs_pf_smooth_io` (cs_pf_smooth)."""
+    _fields_ = [("struct_size", C.c_uint32), ("out_dtype", C.c_uint32), ("num_particles", C.c_int32),
+                ("num_paths", C.c_int32), ("nonce", C.c_uint32), ("first_step", C.c_uint32),
+                ("part_tape_dev", C.c_void_p), ("pstatus_tape_dev", C.c_void_p), ("lw_tape_dev", C.c_void_p),
+                ("wq_tape_dev", C.c_void_p), ("Linv_dev", C.c_void_p), ("end_idx_dev", C.c_void_p),
+                ("part_in_dev", C.c_void_p), ("pstatus_in_dev", C.c_void_p), ("lw_in_dev", C.c_void_p),
+                ("idx_dev", C.c_void_p), ("var_dev", C.c_void_p), ("idx0_dev", C.c_void_p), ("ok_dev", C.c_void_p),
+                ("logb_tape_dev", C.c_void_p), ("bwq_tape_dev", C.c_void_p)]
+
+
 class RolloutMppiIO(C.Structure):
     """Mirror of `struct cs_rollout_mppi_io` (cs_rollout_mppi_costs / cs_rollout_mppi_update)."""
     _fields_ = [("struct_size", C.c_uint32), ("num_samples", C.c_int32), ("noise_stream", C.c_uint32),
@@ -275,6 +286,7 @@ JVP_MAX_DIRS = 64                                            # CS_JVP_MAX_DIRS
 URTS_WORKSPACE_ROWS = 102                                    # CS_URTS_WORKSPACE_ROWS
 EKF_MAX_MEAS = 12                                            # CS_EKF_MAX_MEAS
 PF_MIN_PARTICLES, PF_MAX_PARTICLES = 64, 1024                # CS_PF_MIN_PARTICLES, CS_PF_MAX_PARTICLES
+PFS_MAX_PATHS = 1024                                         # CS_PFS_MAX_PATHS
 MPPI_MAX_SAMPLES = 65535                                     # CS_MPPI_MAX_SAMPLES
 MLP_MAX_HIDDEN = 64                                          # CS_MLP_MAX_HIDDEN
 # cs_step_jacobian branch bits (include/copterstep.h: CS_JAC_*)
@@ -356,6 +368,7 @@ SYMBOLS = {
     "cs_rollout_lqg": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutLqgIO), _P]),
     "cs_rollout_ukf": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutUkfIO), _P]),
     "cs_urts_smooth": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutUrtsIO), _P]),
+    "cs_pf_smooth": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(PfSmoothIO), _P]),
     "cs_rollout_mppi_costs": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_update": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO), _P]),
     "cs_rollout_mppi_costs_ex": (C.c_int, [_P, C.POINTER(RolloutIO), C.POINTER(RolloutMppiIO),

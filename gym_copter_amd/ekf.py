@@ -303,7 +303,8 @@ def ekf(env, actions, z, H, r, Q, x0, P0, status0=None, chunk=None):
                      cat["P_tape"])
 
 
-def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None, alpha=1.0, beta=0.0, kappa=1.0):
+def smooth(env, actions, filt, Q, x0=None, P0=None, status0=None, chunk=None, alpha=1.0, beta=0.0, kappa=1.0, paths=256,
+           nonce=0):
     """Run a fixed-interval smoother over the K steps of a filter's tapes in chunks of `chunk` steps (None: one call),
     last chunk first: env.rollout_rts for an EkfResult, env.rollout_urts for a UkfResult (alpha, beta and kappa are
     the filter's; an EkfResult ignores them).  A chunk starts from the filter's row before it (the caller's x0, P0,
@@ -312,8 +313,17 @@ def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None, alpha=1.0, b
     chunks' conjunction -- tensors of their own, not the env's buffers.  Every tape, x0, P0 and ok are bit-identical to
     the single call's: a chunk boundary rounds nothing (float64 throughout).  filt is the result of the whole filter with
     its float64 P_tape (rollout_ekf(..., tape=True) or ekf(); rollout_ukf(..., tape=True) or ukf()); the other arguments
-    are rollout_rts'."""
+    are rollout_rts'.
+
+    A PfResult (rollout_pf(..., tape=True) or pf()) goes to pf.pf_smooth, the backward-simulation smoother, with `paths`
+    trajectories per env and the draws' `nonce`; it returns PfPaths.  The particle set before step 1 is not on a tape,
+    so x0, P0 and status0 are not used there (and are required for the other two)."""
     torch = _torch()
+    from .pf import PfResult, pf_smooth    # (pf.py imports this module: looked up when a call needs it)
+    if isinstance(filt, PfResult):
+        return pf_smooth(env, actions, filt, Q, paths=paths, nonce=nonce, chunk=chunk)
+    if x0 is None or P0 is None:
+        raise ValueError("x0 and P0 (the filter's starting point) are required to smooth an EkfResult or a UkfResult")
     K = int(actions.shape[0])
     chunk = K if chunk is None else int(chunk)
     if chunk < 1:
@@ -327,7 +337,7 @@ def smooth(env, actions, filt, Q, x0, P0, status0=None, chunk=None, alpha=1.0, b
         from .ukf import UkfResult         # (ukf.py imports this module: looked up when a call needs it)
         if not isinstance(filt, UkfResult):
             raise ValueError("filt must be an EkfResult or a UkfResult with its P_tape (rollout_ekf / rollout_ukf(..., "
-                             "tape=True))")
+                             "tape=True)), or a PfResult with its tapes")
 
         def sub(k0, k1):
             return UkfResult(filt.x[k0:k1], filt.x_pred[k0:k1], None, None, None, None, filt.status[k0:k1], None, None,

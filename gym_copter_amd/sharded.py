@@ -226,7 +226,7 @@ class ShardedCopterVecEnv:
 _LOCAL_ROLLOUTS = ("rollout_states", "rollout_vjp", "rollout_vjp_params", "rollout_jvp", "rollout_lqr",
                    "rollout_feedback_states", "rollout_lqr_box", "rollout_feedback_box_states",
                    "rollout_mppi_costs", "rollout_mppi_update", "rollout_ekf", "rollout_rts", "rollout_pf", "rollout_lqg",
-                   "rollout_ukf", "rollout_urts")
+                   "rollout_ukf", "rollout_urts", "rollout_pf_smooth")
 
 
 def _local_rollout(name):

@@ -44,7 +44,7 @@ from .mppi import MPPI_MAX_KNOT, MppiCosts, MppiTemperature, MppiUpdate, mppi_kn
 from .es import Population  # noqa: F401
 from .ppo import PPO_STATS, ActorCritic, PpoGrad  # noqa: F401
 from .ekf import EkfResult, RtsResult  # noqa: F401
-from .pf import PfResult  # noqa: F401
+from .pf import PfPaths, PfResult, PfSmoothResult  # noqa: F401
 from .lqg import LqgResult  # noqa: F401
 from .ukf import UkfResult  # noqa: F401
 from .spaces import gymnasium_api
@@ -109,7 +109,8 @@ PACKED_ROWS_MAX_ENVS = 131072
 STATE_NAMES_12 = ['X', 'dX', 'Y', 'dY', 'Z', 'dZ', 'Phi', 'dPhi', 'Theta', 'dTheta', 'Psi', 'dPsi']
 
 
-class CopterVecEnv(_ilqr.ControlLimited, _ukf.UnscentedSmoother, _rollouts.ForwardTangents, _VectorEnvBase):
+class CopterVecEnv(_ilqr.ControlLimited, _ukf.UnscentedSmoother, _pf.ParticleSmoother, _rollouts.ForwardTangents,
+                   _VectorEnvBase):
     FRAMES_PER_SECOND = 100                                    # task.py:25
     # class-level defaults of the gymnasium.vector.VectorEnv attribute set (instances overwrite them)
     metadata = {"render_modes": [], "render_fps": 100}         # task.py:27-30 (rendering is out of scope: no modes)

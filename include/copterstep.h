@@ -49,6 +49,8 @@
  *                            the step, K steps per env           counterpart: a derivative-free state estimator)
  *   cs_urts_smooth           an unscented Rauch-Tung-Striebel   the same points, made again from the filter's tapes
  *                            smoother over that filter's tapes   (no upstream counterpart: a fixed-interval smoother)
+ *   cs_pf_smooth             a backward-simulation smoother     the rollout lines above, per taped particle (no upstream
+ *                            over the particle filter's tapes    counterpart: sampled smoothed trajectories)
  *   cs_rollout_mppi_costs    P noisy copies of an action tape   lander.py:40-65 with sampled actions (no upstream
  *                            rolled out and scored              counterpart: a sampling-based trajectory optimiser)
  *   cs_rollout_mppi_update   their cost-weighted average         (the same)
@@ -1332,6 +1334,83 @@ typedef struct cs_urts_io {
   uint8_t* ok_dev;             /* [N] */
 } cs_urts_io;
 int cs_urts_smooth(cs_ctx* ctx, const cs_rollout_io* io, const cs_urts_io* sio, void* stream);
+
+/* A backward-simulation particle smoother over the tapes of cs_rollout_pf, on the device: forward
+ * filtering, backward simulation.  S trajectories ("paths") per env are drawn backwards through the filter's taped
+ * particle sets; every earlier particle is reweighted by its filter weight times the transition density to the path's
+ * next point.  What cs_rollout_rts is to cs_rollout_ekf, for the filter that keeps a belief on both sides of a branch
+ * of the step.  No env state is read except the context's constants and vehicle table, and none is written.  Everything
+ * is float64 without contraction unless stated.
+ *
+ * From io: num_steps = K, actions_dev [K,N,A] (the filter's), x_dev [K,N,12] or NULL (the smoothed means); every other
+ * pointer of io must be NULL.  From sio, per env and row k = 0 .. K-1 (row k is the filter's step first_step + k):
+ *   X_k[i] = part_tape_dev[k,env,i] (the prior particles), s_k[i] = pstatus_tape_dev[k,env,i], lw_k[i] =
+ *   lw_tape_dev[k,env,i], wq_tape_dev (read at row K-1 only, and only without end_idx_dev): the filter's tapes;
+ *   Linv_dev [12,12]: the inverse of the filter's Lq, lower triangular (the upper triangle is not read);
+ *   P = num_particles (the filter's), S = num_paths in 1 .. CS_PFS_MAX_PATHS, nonce, first_step (the filter's).
+ *
+ * Row K-1.  b[K-1,m] = end_idx_dev[env,m] mod P when end_idx_dev is given, else drawn (below) from the integer weights
+ *   wq_tape[K-1].
+ * For k = K-2 down to 0:
+ *   (mu_i, sigma_i) is the physics of step k+1 from (X_k[i], s_k[i]) under actions[k+1], without noise: the code
+ *   cs_rollout_pf propagates with (clip, motor law, the env's vehicle, `substeps` calls, the status machine, skipped for
+ *   a LANDED particle) -- mu_i is cs_rollout_states' row from that point, bit for bit in float64 storage.
+ *   y_i = Linv mu_i: row r is sum_{j <= r} Linv[r][j] mu_i[j], j ascending, the first term starting the sum, one multiply
+ *   and one add per term (gym_copter_amd/csrc/pfs_draw.h).
+ *   For path m: xt = X_{k+1}[b[k+1,m]], st = s_{k+1}[b[k+1,m]], yt = Linv xt;
+ *     d2 = sum_j (yt_j - y_i,j)^2, j ascending, the first term starting the sum;
+ *     logb_i = lw_k[i] + (-0.5 d2) if sigma_i == st, else -inf: the flight status is a deterministic part of the
+ *     transition.  A non-finite value counts as -inf.
+ *     mx = max_i logb_i.  If mx is -inf the env's ok is 0 and e_i = 1 for every i (as the filter's dead step); else
+ *     e_i = exp(logb_i - mx).  bwq_i = (uint32) rint(e_i 2^24), and b[k,m] is drawn from bwq.
+ * Row -1 (optional).  With a start set part_in_dev [N,P,12], pstatus_in_dev [N,P], lw_in_dev [N,P] (all three or none:
+ *   the prior particles of the step before this call's first, rows of the filter's tapes) one more backward step is made
+ *   from it under actions[0]; its indices go to idx0_dev [N,S].  A tape is smoothed in chunks, last chunk first, by
+ *   passing a later chunk's idx0 as the earlier chunk's end_idx.
+ * Draw.  With C the inclusive cumulative sum of the integer weights, S1 = C[P-1] and u = the top 24 bits of the first
+ *   Philox word of (g, nonce, kg, m, slot 13) of cs_rollout_pf's noise -- kg = first_step + k is the global index of the
+ *   row being drawn (first_step - 1 for row -1), the path m stands in the key's particle field -- the index is the
+ *   smallest p with (C[p] << 24) > u S1 (both sides < 2^58); P - 1 if every weight is 0.  A pure function of the seed,
+ *   the global env id, the nonce, the global row and the path: it does not depend on S, P, the batch, the sharding or
+ *   the chunking.
+ * Estimates per row, equal weights over the S paths: the mean of X_k[b[k,m]] and the variance about that mean (summed
+ *   and divided by S).  The order of the sums is fixed (no atomics): the same inputs give the same bits on every call.
+ * Outputs, each may be NULL; var in out_dtype (CS_JAC_F64, or CS_JAC_F32: the float64 values rounded):
+ *   idx_dev [K,N,S] int32 = b          io->x_dev [K,N,12] float64      var_dev [K,N,12]
+ *   idx0_dev [N,S] int32 (needs the start set, else CS_ERR_ARG)        ok_dev [N] uint8
+ * and two diagnostic tapes:
+ *   logb_tape_dev [K,N,S,P] float64: logb of rows 0 .. K-2; row K-1 holds lw_tape[K-1] (for every path) when it is
+ *                 drawn, and is NOT written when end_idx_dev is given
+ *   bwq_tape_dev [K,N,S,P] int32: bwq of rows 0 .. K-2; row K-1 holds wq_tape[K-1] when it is drawn, and is NOT written
+ *                 when end_idx_dev is given
+ * No output may overlap an input.  Refused (CS_ERR_ARG) under action_arith = CS_ARITH_F32.  Asynchronous on `stream`;
+ * sio->struct_size must be sizeof(cs_pf_smooth_io) (else CS_ERR_ABI, checked first); both blocks are checked before the
+ * context.  Every array is aligned to its element size. */
+#define CS_PFS_MAX_PATHS 1024
+typedef struct cs_pf_smooth_io {
+  uint32_t struct_size;            /* sizeof(cs_pf_smooth_io) */
+  uint32_t out_dtype;              /* CS_JAC_F64 / CS_JAC_F32: var_dev */
+  int32_t num_particles;           /* P, the filter's: a power of two in CS_PF_MIN_PARTICLES .. CS_PF_MAX_PARTICLES */
+  int32_t num_paths;               /* S, 1 .. CS_PFS_MAX_PATHS */
+  uint32_t nonce;                  /* the second counter word of every draw */
+  uint32_t first_step;             /* >= 1: the global index of row 0's step (the filter's first_step) */
+  const double* part_tape_dev;     /* [K,N,P,12], required */
+  const uint8_t* pstatus_tape_dev; /* [K,N,P], required */
+  const double* lw_tape_dev;       /* [K,N,P], required */
+  const uint32_t* wq_tape_dev;     /* [K,N,P], required without end_idx_dev */
+  const double* Linv_dev;          /* [12,12] lower triangular, required */
+  const int32_t* end_idx_dev;      /* [N,S] or NULL */
+  const double* part_in_dev;       /* [N,P,12] (the start set: all three or none) */
+  const uint8_t* pstatus_in_dev;   /* [N,P] */
+  const double* lw_in_dev;         /* [N,P] */
+  int32_t* idx_dev;                /* [K,N,S] */
+  void* var_dev;                   /* [K,N,12] */
+  int32_t* idx0_dev;               /* [N,S] */
+  uint8_t* ok_dev;                 /* [N] */
+  double* logb_tape_dev;           /* [K,N,S,P] */
+  int32_t* bwq_tape_dev;           /* [K,N,S,P] */
+} cs_pf_smooth_io;
+int cs_pf_smooth(cs_ctx* ctx, const cs_rollout_io* io, const cs_pf_smooth_io* sio, void* stream);
 
 /* MPPI (model-predictive path integral control) on the device: zeroth-order, sampling-based
  * trajectory optimisation, which sees across the branches of the step that have no useful derivative (touchdown, crash,

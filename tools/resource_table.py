@@ -16,7 +16,8 @@ AGPRs | scratch B/lane | waves/SIMD | LDS B/block, the layout of profiles/*_reso
     python3 tools/resource_table.py remarks.txt rollout_ukf > profiles/rollout_ukf_resources.txt
     python3 tools/resource_table.py remarks.txt ilqr_box > profiles/ilqr_box_resources.txt
     python3 tools/resource_table.py remarks.txt urts > profiles/urts_resources.txt
-    python3 tools/resource_table.py remarks.txt rollout_jvp > profiles/rollout_jvp_resources.txt"""
+    python3 tools/resource_table.py remarks.txt rollout_jvp > profiles/rollout_jvp_resources.txt
+    python3 tools/resource_table.py remarks.txt pf_smooth > profiles/pf_smooth_resources.txt"""
 import re
 import sys
 
@@ -95,7 +96,11 @@ HEADS = {"rollout_mlp": """\
 # caller's workspace while the points run; DESIGN.md section 25).""", "rollout_jvp": """\
 # make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_jvp.hip: the forward-mode rollout tangents
 # rollout_jvp_kernel<TASK, MODE, GYRO, PARAM> (6 KiB of LDS for the tangent rows; PARAM builds keep the direction
-# block's 2 x 11 coefficient tangents in lane-private LDS columns, 11 KiB more; DESIGN.md section 26)."""}
+# block's 2 x 11 coefficient tangents in lane-private LDS columns, 11 KiB more; DESIGN.md section 26).""", "pf_smooth": """\
+# make report (hipcc -Rpass-analysis=kernel-resource-usage), copterstep_pf_smooth.hip: the backward-simulation particle
+# smoother pf_smooth_kernel<TASK, MODE, GYRO> (one workgroup of min(P, 256) lanes per env; the whitened particles, their
+# log-weights and statuses and two rows of path indices in dynamic LDS, 108 P + 16 656 bytes per workgroup -- not part
+# of the static figure below; DESIGN.md section 27)."""}
 
 
 def main(path, which="rollout_mlp"):
